@@ -19,7 +19,12 @@ of the sharded LPIPS scalars, identical greedy commits everywhere.
 one (distance x exp(S x position)): the greedy order then leaves the balanced tree and the speculative frontier needs
 several small rounds — reported through census_per_transition.frontier_rounds / speculation_hit_rate.
 
-The JSON line also carries
+A plain run sets up, warms up, times the --steps transitions and prints the JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = wall milliseconds of one timed transition, config, census).  --dump-outputs DIR
+also writes what the last timed transition returned (frames.npy, tree_fracts.npy); the inputs are seeded, so two
+builds given the same arguments can be compared output for output.  With --full the JSON line also carries
+  phases_per_transition — hipEvents around the program launches of one extra transition;
+  secondary     — cfg 2 under a skewed metric, elide_dead_steps, a chain of transitions, cfg 3 / 4 / 5 at full width;
   roofline      — the dominant kernel family (MFMA GEMM / implicit-GEMM conv / halo-tile conv): algorithmic
                   FLOPs per transition / its device time, measured live with hipEvents between the ops of an
                   eager replay of the same launch programs, against the 2.5 PFLOP/s dense fp16 MFMA peak;
@@ -76,7 +81,61 @@ def parse():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="entry-path check without a GPU (tests/test_dist_cpu.py): spawn / join the ranks, verify the world size, "
                          "print the JSON line with value null, run no workload")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-phase split, rooflines, secondary lines, CPU baseline "
+                         "(each still switched off by its --no-* option); a plain run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy: frames.npy (float32 "
+                         "[frames, H, W, 3], 0..255; above 60 MiB a fixed strided sample, frames_sample.npy) and tree_fracts.npy (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def device_synthetic_provider(seed, device):
+    """The UNet's seeded synthetic weights with SyntheticProvider's exact values, finished on the GPU: the normal deviates
+    are drawn on the host from the same streams (unscaled: x 1.0 + 0.0 is exact), then scaled, shifted and rounded to fp16
+    on the device - elementwise fp32 / fp16 operations, bit-identical to the host's - and handed out as device tensors, so
+    the UNet's packing (fp16-exact products and sums in fp64, permutes, concatenations) runs there too.  A plain run needs
+    this: the host path spends about a minute per process in single-threaded tensor passes over 2.6 G values."""
+    import latentblending_amd.native.weights as W
+
+    class DeviceSynthetic(W.SyntheticProvider):
+        def _draw(self, name, shape, std, mean=0.0):
+            z = W._seeded(name, shape, 1.0, self.seed).to(device)
+            return z.mul_(std).add_(mean).half().float()
+
+        def weight(self, name, shape, fan_in, gain=1.0):
+            return self._draw(name, shape, gain / math.sqrt(fan_in))
+
+        def bias(self, name, n):
+            return self._draw(name, (n,), 0.02)
+
+        def norm_weight(self, name, n):
+            return self._draw(name, (n,), 0.05, mean=1.0)
+
+    return DeviceSynthetic(seed)
+
+
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def dump_outputs(out_dir, imgs, tree_fracts):
+    """What one timed transition returns to its caller: the frames (float32 [frames, H, W, 3], 0..255) and the tree's
+    fractions (float64).  Frames beyond DUMP_LIMIT_BYTES are written as a fixed strided sample of their flattened
+    values, frames_sample.npy, instead."""
+    import numpy as np
+    from latentblending_amd.native.frames import materialise_frames
+    os.makedirs(out_dir, exist_ok=True)
+    materialise_frames(imgs)
+    frames = np.stack([np.asarray(im) for im in imgs]).astype(np.float32)
+    if frames.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frames.npy"), frames)
+    else:
+        stride = -(-frames.nbytes // DUMP_LIMIT_BYTES)
+        np.save(os.path.join(out_dir, "frames_sample.npy"), np.ascontiguousarray(frames.reshape(-1)[::stride]))
+    np.save(os.path.join(out_dir, "tree_fracts.npy"), np.asarray([float(f) for f in tree_fracts], dtype=np.float64))
 
 
 def respawn_under_torchrun(args):
@@ -793,19 +852,27 @@ def _run():
     assert world == args.gpus, (f"--gpus {args.gpus} but the job has {world} rank(s): start it as `python bench.py --gpus N` "
                                 f"(re-executes itself under torch.distributed.run) or `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`")
 
+    import numpy as np
     import latentblending_amd.native as N
     from latentblending_amd import BlendingEngine
 
+    # the same inputs every run: the single-GPU ancestral noise comes from torch's device RNG, the engine's host-side
+    # draws from numpy's global RNG
+    np.random.seed(0)
+    torch.manual_seed(0)
     # seeded synthetic SDXL weights from the product's own provider; rank 0 keeps the fp32 copies so
     # that the cpu_baseline leg can time the oracle on exactly the same parameters
     base = args.config == "cfg3"
-    want_cpu = rank == 0 and world == 1 and (args.torch_baseline or not args.no_cpu_baseline) and not base
+    want_cpu = rank == 0 and world == 1 and (args.torch_baseline or (args.full and not args.no_cpu_baseline)) and not base
     t0 = time.perf_counter()
     # LB_SYNTH_CACHE=<dir>: keep the generated (seeded, fp16-rounded) tensors in a scratch file between the several
     # processes of a profiling session - the same values, a few seconds instead of a minute of CPU random draws
     cdir = os.environ.get("LB_SYNTH_CACHE")
     cfile = (lambda s: os.path.join(cdir, f"lb_synth_seed{s}.pt")) if cdir else (lambda s: None)
-    unet_prov = N.SyntheticProvider(0, keep=want_cpu, cache_file=cfile(0))
+    if want_cpu or cdir:        # host tensors: the fp32 copies the CPU legs time / the scratch-file cache
+        unet_prov = N.SyntheticProvider(0, keep=want_cpu, cache_file=cfile(0))
+    else:                       # the same values, finished on the GPU (device_synthetic_provider)
+        unet_prov = device_synthetic_provider(0, f"cuda:{local_rank}")
     vae_prov = N.SyntheticProvider(1, keep=want_cpu, cache_file=cfile(1))
     pipe = N.NativeSDXLPipe(turbo=not base, unet_provider=unet_prov, vae_provider=vae_prov, device=f"cuda:{local_rank}",
                             allow_synthetic=True)      # ("data": "synthetic" in the JSON line)
@@ -857,7 +924,7 @@ def _run():
         pipe.stats[k] = 0
     be.stats.clear()
     farm_counts = {}
-    if world > 1 and rank == 0 and not args.no_roofline and args.warmup > 0:
+    if world > 1 and rank == 0 and args.full and not args.no_roofline and args.warmup > 0:
         # a farmed transition cannot be repeated by rank 0 alone (collectives), so rank 0 counts its own program
         # launches during the timed transitions (programs exist after the warm-up) and profiles them afterwards
         install_launch_counters(pipe, farm_counts)
@@ -871,6 +938,8 @@ def _run():
         frames = len(imgs)
     barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, imgs, be.tree_fracts)
     per_rank_ms = None
     if world > 1:
         mine = torch.tensor([dt / max(args.steps, 1) * 1e3], device="cuda")
@@ -921,12 +990,12 @@ def _run():
                    "census_per_transition": per_transition, "weights_gen_s": round(t_weights, 1),
                    "cold_start_s": None if cold_start_s is None else round(cold_start_s, 2)},
     }
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         try:
             out["phases_per_transition"] = phase_split(pipe, be)
         except Exception as exc:
             out["phases_error"] = repr(exc)
-    if rank == 0 and world == 1 and not args.no_roofline:      # (needs a solo transition: no collectives)
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:      # (needs a solo transition: no collectives)
         # launches of every (program, batch) per transition: one more transition with counting wrappers
         step_launch_counts = {}
         install_launch_counters(pipe, step_launch_counts)
@@ -934,9 +1003,9 @@ def _run():
         torch.cuda.synchronize()
         out["roofline"], out["rooflines"] = roofline_blocks(gemm_family_profile(pipe, step_launch_counts), step_launch_counts,
                                                             f"cuda:{local_rank}")
-    if rank == 0 and world == 1 and not base and not args.no_secondary and not args.metric_skew:
+    if rank == 0 and world == 1 and args.full and not base and not args.no_secondary and not args.metric_skew:
         out["secondary"] = secondary_lines(pipe, args, branches)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not base:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not base:
         out["cpu_baseline"] = cpu_baseline(unet_w, vae_w, per_transition)
     if world > 1:
         dist.destroy_process_group()

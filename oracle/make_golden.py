@@ -27,6 +27,8 @@ Fixtures
 
   guidance_chain.json  (round 6) two chained SDXL-base transitions, one level 3 x 6 stems: the mid-dampened guidance scale each
                   transition leaves behind (the LAST COMMITTED branch's) and the second transition computed under it
+  crossfeed_chain.json / .npz  two chained SDXL-Turbo transitions with branch-1 crossfeed, swap_forward + recycle_img1:
+                  tree, call census and every frame (uint8, whole) - the frozen side of the live differential test
 
     python -m oracle.make_golden frames      # regenerate one fixture
 """
@@ -433,6 +435,34 @@ def guidance_chain_fixture(ref):
             "list_nmb_stems": [6], "segments": segs}
 
 
+CROSSFEED_PROMPTS = ["a", "b", "c"]
+
+
+def crossfeed_chain_fixture(ref):
+    """Two chained SDXL-Turbo transitions (swap_forward + recycle_img1, example_multi_trans.py:39-58) with
+    set_branch1_crossfeed(0.3, 0.5, 0.5), 3 branches, seeds [5, 6] then [6, 7]: every frame of both transitions (uint8,
+    stored whole in crossfeed_chain.npz), the last transition's tree_fracts and the UNet call count of the chain."""
+    p = tiny_pipe(turbo=True)
+    np.random.seed(0)
+    frames = []
+    with H.cuda_is_identity():
+        be = ref.BlendingEngine(p)
+        be.set_dimensions((128, 128))
+        be.set_branching(nmb_max_branches=3)
+        be.set_branch1_crossfeed(0.3, 0.5, 0.5)
+        for i in range(2):
+            if i == 0:
+                be.set_prompt1(CROSSFEED_PROMPTS[0]); be.set_prompt2(CROSSFEED_PROMPTS[1])
+            else:
+                be.swap_forward(); be.set_prompt2(CROSSFEED_PROMPTS[i + 1])
+            p.noise.reset()
+            frames.append(np.stack([np.asarray(f) for f in be.run_transition(recycle_img1=i > 0, fixed_seeds=[5 + i, 6 + i])]))
+    np.savez_compressed(os.path.join(OUT, "crossfeed_chain.npz"), frames=np.stack(frames).astype(np.uint8))
+    return {"prompts": CROSSFEED_PROMPTS, "crossfeed": [0.3, 0.5, 0.5], "nmb_max_branches": 3, "seeds": [[5, 6], [6, 7]],
+            "frames_per_transition": [len(f) for f in frames], "tree_fracts": [float(f) for f in be.tree_fracts],
+            "unet_calls": p.unet.calls, "noise_draws": p.noise.draws}
+
+
 def key_frames(seed, n, h, w):
     rng = np.random.RandomState(seed)
     return [rng.randint(0, 256, size=(h, w, 3)).astype(np.uint8) for _ in range(n)]
@@ -459,7 +489,7 @@ def main():
     only = set(sys.argv[1:])
     makers = [("planner", lambda: planner_fixture(ref)), ("slerp", lambda: slerp_fixture(ref)), ("scheduler", scheduler_fixture),
               ("tree", lambda: tree_fixture(ref)), ("configs", lambda: configs_fixture(ref)), ("frames", lambda: frames_fixture(ref)),
-              ("guidance_chain", lambda: guidance_chain_fixture(ref))]
+              ("guidance_chain", lambda: guidance_chain_fixture(ref)), ("crossfeed_chain", lambda: crossfeed_chain_fixture(ref))]
     for name, make in makers:
         if only and name not in only:
             continue
