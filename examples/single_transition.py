@@ -16,3 +16,4 @@ engine.set_prompt2("a quiet harbour at dawn, watercolor")
 frames = engine.run_transition(fixed_seeds=[420, 421])
 print(f"{len(frames)} frames, fractions {engine.tree_fracts}")
 engine.write_movie_transition("transition.avi", duration_transition=4)
+# engine.write_movie_transition("transition.avi", duration_transition=4, encoder="device")   # blend + JPEG-encode on the GPU

@@ -247,6 +247,22 @@ int lb_frames_lerp_u8(const void* frames, const int* left_dev, const double* w_d
                       long frame_bytes, void* stream);
 int lb_copy_d2d(void* dst, const void* src, long bytes, void* stream);
 
+/* ---- movie frames: baseline JPEG on the device (replaces lunar_tools.MovieSaver.write_frame behind
+ *      blending_engine.py:698-706: the reference pipes raw frames to an ffmpeg process on the host).  SOF0, 8 bit, three
+ *      components, JFIF YCbCr; subsampling 0 = 4:2:0 (16x16 MCU, chroma = mean of each 2x2 cell, partial MCUs filled by edge
+ *      replication), 1 = 4:4:4.  H and W multiples of 8, otherwise the launchers fail with a message. ---------------- */
+/* Stage 1.  frames [n][H][W][3] uint8; qtables [2][64] uint16 (luma, chroma; natural order); coef int16: per frame the
+ * Y, Cb, Cr planes (whole MCUs), blocks in raster order, 64 values per block in zigzag order.  fp32, round half away from zero. */
+int lb_jpeg_dct_quant_u8(const void* frames_u8, const void* qtables_u16, void* coef_i16, int n, int H, int W, int subsampling,
+                         void* stream);
+long lb_jpeg_coefficient_count(int n, int H, int W, int subsampling);   /* int16 values stage 1 writes; -1: unsupported size */
+/* Stage 2.  Annex K.3 Huffman tables; one restart interval per MCU row (DRI = MCUs per row), RSTm after every interval but the
+ * last.  out: the frames' scan data back to back (frame f: frame_bytes[f] bytes, at the sum of the counts before it); an interval
+ * that would cross out_capacity is not written while frame_bytes still holds the true sizes (the caller compares and retries). */
+int lb_jpeg_entropy(const void* coef_i16, void* workspace, void* out, long out_capacity, void* frame_bytes_i32, int n, int H, int W,
+                    int subsampling, void* stream);
+long lb_jpeg_workspace_bytes(int n, int H, int W, int subsampling);     /* worst case of the tables for any int16 input; -1: size */
+
 /* ---- launch programs (the MI355X-native stand-in for the reference's optional stable-fast
  *      compile, blending_engine.py:88-96): record the launchers above once, replay them from
  *      C++ or as one hipGraph ------------------------------------------------------------ */

@@ -24,6 +24,7 @@ from __future__ import annotations
 import os
 import platform
 import time
+import warnings
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -93,6 +94,7 @@ class BlendingEngine:
         #                                     the same way (re-renders of one transition, a metric with a positional bias): the skewed
         #                                     bench line needs ONE round instead of two
         self._level_priors = {}             # (idx_injection, stems) -> [(f_left, f_right, f_mid)] in the order the level was committed
+        self.movie_encoder = "host"         # write_movie_transition: "host" (movie writer on the CPU) or "device" (HIP JPEG encoder, AVI written here)
         self.fuse_anchor_round = True       # single-level trees: first round shares the anchors' UNet batches
         self.fuse_recycled_anchor = True    # ... also when an anchor is recycled (swap_forward chains, precomputed key frames): the
         #                                     fused wavefront takes the stored trajectory as given and denoises only the other one
@@ -951,8 +953,18 @@ class BlendingEngine:
             leaf = img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
             leaf.save(os.path.join(dp_img, f"lowres_img_{str(i).zfill(4)}.jpg"))
 
-    def write_movie_transition(self, fp_movie, duration_transition, fps=30):
-        """Linearly in-between the frames to ``duration_transition*fps`` frames and write a movie."""
+    def write_movie_transition(self, fp_movie, duration_transition, fps=30, encoder=None):
+        """Linearly in-between the frames to ``duration_transition*fps`` frames and write a movie.
+
+        ``encoder`` (default: ``self.movie_encoder``, initially "host"): "host" encodes every frame with the movie writer on the
+        host; "device" blends AND JPEG-encodes the frames on the GPU (``csrc/jpeg.hip``) and writes the Motion-JPEG AVI itself,
+        so only compressed bytes leave the device.  "device" needs device-resident key frames of a size that is a multiple of 8
+        both ways; otherwise it warns once and takes the host path."""
+        encoder = self.movie_encoder if encoder is None else encoder
+        if encoder not in ("host", "device"):
+            raise ValueError(f"write_movie_transition: encoder must be 'host' or 'device', not {encoder!r}")
+        if encoder == "device" and self._write_movie_transition_device(fp_movie, duration_transition, fps):
+            return
         from .movie import MovieSaver, fill_up_frames_linear_interpolation
         frames = fill_up_frames_linear_interpolation(self.tree_final_imgs, duration_transition, fps)
         if os.path.isfile(fp_movie):
@@ -961,6 +973,24 @@ class BlendingEngine:
         for frame in tqdm(frames, disable=not self.verbose):
             saver.write_frame(frame)
         saver.finalize()
+
+    def _write_movie_transition_device(self, fp_movie, duration_transition, fps) -> bool:
+        """The "device" path of ``write_movie_transition``; False (after one warning, nothing written, numpy's RNG untouched)
+        when it does not apply."""
+        from .movie import AviMovieSaver
+        from .utils import inbetween_frames_device
+        h, w = self.dh.height_img, self.dh.width_img
+        frames = inbetween_frames_device(self.tree_final_imgs, int(round(duration_transition * fps))) if h % 8 == 0 and w % 8 == 0 else None
+        if frames is None or list(frames.shape[1:3]) != [h, w]:
+            warnings.warn("write_movie_transition: encoder='device' needs device-resident key frames whose height and width are "
+                          "multiples of 8; encoding on the host", UserWarning, stacklevel=3)
+            return False
+        if os.path.isfile(fp_movie):
+            os.remove(fp_movie)
+        saver = AviMovieSaver(fp_movie, fps=fps, shape_hw=[h, w])
+        saver.write_frames_device(frames)
+        saver.finalize()
+        return True
 
     def get_state_dict(self):
         """Scalar settings of the engine (the upstream list has a missing comma and names

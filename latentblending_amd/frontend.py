@@ -157,7 +157,8 @@ class BlendingVariableHolder:
         return self.get_list_images_movie()
 
     # ---- gradio_ui.py:222-262: the chain over the edited list, one part per segment, concatenated ----
-    def generate_movie(self, t_per_segment=10, fps: int = 30):
+    def generate_movie(self, t_per_segment=10, fps: int = 30, movie_encoder: Optional[str] = None):
+        """``movie_encoder``: "host" / "device" for the parts' ``write_movie_transition`` (None: the session's setting)."""
         from .replay import run_multi_transition
         if len(self.data) < 2:
             raise ValueError("generate_movie: the movie needs at least two images (add_image_to_video)")
@@ -166,7 +167,8 @@ class BlendingVariableHolder:
         with self.session.bound() as be:
             run_multi_transition(be, [it["prompt"] for it in self.data], [it["seed"] for it in self.data], self.fp_movie,
                                  duration_single_trans=t_per_segment,
-                                 list_negative_prompts=[it["negative_prompt"] for it in self.data], fps=fps, dp_parts=self.dp_out)
+                                 list_negative_prompts=[it["negative_prompt"] for it in self.data], fps=fps, dp_parts=self.dp_out,
+                                 movie_encoder=movie_encoder)
         print(f"DONE! MOVIE SAVED IN {self.fp_movie}")
         return self.fp_movie
 

@@ -111,6 +111,10 @@ SIGNATURES = {
     "lb_frames_lerp_u8": (_i, [_vp, _vp, _vp, _vp, _l, _l, _vp]),
     "lb_gather_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "lb_copy_d2d": (_i, [_vp, _vp, _l, _vp]),
+    "lb_jpeg_dct_quant_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "lb_jpeg_coefficient_count": (_l, [_i, _i, _i, _i]),
+    "lb_jpeg_entropy": (_i, [_vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _vp]),
+    "lb_jpeg_workspace_bytes": (_l, [_i, _i, _i, _i]),
     "lb_program_create": (_vp, []),
     "lb_program_destroy": (None, [_vp]),
     "lb_program_begin_record": (_i, [_vp]),
@@ -131,7 +135,7 @@ STUDY_SIGNATURES = {
     "lb_conv_halo_set_study": (None, [_i]),
 }
 
-_NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes",
+_NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
              "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan", "lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
              "lb_program_destroy", "lb_program_num_ops", "lb_program_op_name"}
 

@@ -407,3 +407,108 @@ def frames_lerp_u8(frames: torch.Tensor, left, weights) -> torch.Tensor:
         api.lb_frames_lerp_u8(frames.data_ptr(), left_d[k0:].data_ptr(), w_d[k0:].data_ptr(), out[k0:].data_ptr(), k1 - k0, fb,
                               stream_ptr())
     return out
+
+
+# -------------------------------------------------------------------------- movie frames -----
+_JPEG_WORKSPACE_BUDGET = 1 << 30        # bytes of entropy-coder workspace per chunk of frames (slots are sized for the worst case)
+_JPEG_QTABLES: dict = {}
+_JPEG_PINNED: dict = {}
+
+
+def _jpeg_qtables(quality: int, device) -> torch.Tensor:
+    """[2][64] uint16 on the device, natural order (one upload per quality and device)."""
+    key = (int(quality), str(device))
+    if key not in _JPEG_QTABLES:
+        from ..jpeg import jpeg_tables
+        _JPEG_QTABLES[key] = torch.tensor(jpeg_tables(quality), dtype=torch.int16).to(device)      # values <= 255
+    return _JPEG_QTABLES[key]
+
+
+def _jpeg_frames(frames_u8: torch.Tensor):
+    assert frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.dim() == 4 and frames_u8.shape[-1] == 3, \
+        "jpeg: [n, H, W, 3] uint8 frames on the device"
+    frames_u8 = frames_u8.contiguous()
+    n, h, w, _ = frames_u8.shape
+    return frames_u8, n, h, w
+
+
+def jpeg_dct_quant_into(frames_u8: torch.Tensor, qtables: torch.Tensor, coef: torch.Tensor, subsampling_code: int) -> None:
+    """Stage 1 launcher on caller-owned buffers (capturable)."""
+    n, h, w, _ = frames_u8.shape
+    api.lb_jpeg_dct_quant_u8(frames_u8.data_ptr(), qtables.data_ptr(), coef.data_ptr(), n, h, w, subsampling_code, stream_ptr())
+
+
+def jpeg_entropy_into(coef: torch.Tensor, workspace: torch.Tensor, out: torch.Tensor, frame_bytes: torch.Tensor, n: int, h: int,
+                      w: int, subsampling_code: int) -> None:
+    """Stage 2 launcher (entropy coding, scan, compaction) on caller-owned buffers (capturable)."""
+    api.lb_jpeg_entropy(coef.data_ptr(), workspace.data_ptr(), out.data_ptr(), out.numel(), frame_bytes.data_ptr(), n, h, w,
+                        subsampling_code, stream_ptr())
+
+
+def jpeg_coefficients_u8(frames_u8: torch.Tensor, quality: int = 92, subsampling: str = "4:2:0") -> torch.Tensor:
+    """Quantised DCT coefficients of [n, H, W, 3] uint8 device frames: int16 [n, blocks, 64] - per frame the Y, Cb, Cr planes
+    (whole MCUs), blocks in raster order, zigzag order inside a block."""
+    from ..jpeg import subsampling_code
+    code = subsampling_code(subsampling)
+    frames_u8, n, h, w = _jpeg_frames(frames_u8)
+    count = api.lb_jpeg_coefficient_count(n, h, w, code)
+    coef = torch.empty((n, max(count, 0) // (64 * n), 64), dtype=torch.int16, device=frames_u8.device)
+    jpeg_dct_quant_into(frames_u8, _jpeg_qtables(quality, frames_u8.device), coef, code)      # (raises for an unsupported size)
+    return coef
+
+
+def _jpeg_to_host(t: torch.Tensor, nbytes: int):
+    """memoryview of the first nbytes of a uint8 device tensor, through one page-locked staging buffer that grows on demand."""
+    key = t.device.index
+    pinned = _JPEG_PINNED.get(key)
+    if pinned is None or pinned.numel() < nbytes:
+        pinned = _JPEG_PINNED[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+    pinned[:nbytes].copy_(t[:nbytes], non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    return memoryview(pinned.numpy())[:nbytes]
+
+
+def jpeg_scan_from_coefficients(coef: torch.Tensor, h: int, w: int, subsampling: str = "4:2:0") -> List[bytes]:
+    """Entropy-coded scan data (restart markers in place, no header, no EOI) of every frame of a stage-1 tensor."""
+    from ..jpeg import subsampling_code
+    code = subsampling_code(subsampling)
+    n = coef.shape[0]
+    assert coef.dtype == torch.int16 and coef.is_cuda and coef.is_contiguous()
+    assert coef.numel() == api.lb_jpeg_coefficient_count(n, h, w, code), "jpeg: coefficient tensor does not match (n, H, W, subsampling)"
+    dev = coef.device
+    workspace = torch.empty(api.lb_jpeg_workspace_bytes(n, h, w, code), dtype=torch.uint8, device=dev)
+    frame_bytes = torch.empty(n, dtype=torch.int32, device=dev)
+    capacity = n * (h * w + 4096)                  # ~3x what quality 92 needs on noisy frames; the true sizes come back either way
+    while True:
+        out = torch.empty(capacity, dtype=torch.uint8, device=dev)
+        jpeg_entropy_into(coef, workspace, out, frame_bytes, n, h, w, code)
+        sizes = frame_bytes.cpu().tolist()
+        total = sum(sizes)
+        if total <= capacity:
+            break
+        capacity = total                           # (rare: quality ~100 on noise) once more with the exact size
+    host = _jpeg_to_host(out, total)
+    scans, pos = [], 0
+    for s in sizes:
+        scans.append(bytes(host[pos:pos + s]))
+        pos += s
+    return scans
+
+
+def jpeg_encode_u8(frames_u8: torch.Tensor, quality: int = 92, subsampling: str = "4:2:0") -> List[bytes]:
+    """Complete baseline JPEG files (header + scan + EOI) of [n, H, W, 3] uint8 device frames, encoded on the device in chunks of
+    frames; only the compressed bytes are copied to the host.  Raises RuntimeError for a size the kernels do not take."""
+    from ..jpeg import EOI, jpeg_header, subsampling_code
+    code = subsampling_code(subsampling)
+    frames_u8, n, h, w = _jpeg_frames(frames_u8)
+    per_frame = api.lb_jpeg_workspace_bytes(1, h, w, code)
+    if per_frame <= 0:
+        raise RuntimeError(f"jpeg_encode_u8: unsupported frame size {h} x {w} (height and width must be multiples of 8)")
+    header = jpeg_header(h, w, int(quality), subsampling)
+    chunk = max(1, min(n, 1024, _JPEG_WORKSPACE_BUDGET // per_frame))
+    out: List[bytes] = []
+    for k0 in range(0, n, chunk):
+        part = frames_u8[k0:k0 + chunk]
+        coef = jpeg_coefficients_u8(part, quality, subsampling)
+        out.extend(b"".join((header, scan, EOI)) for scan in jpeg_scan_from_coefficients(coef, h, w, subsampling))
+    return out

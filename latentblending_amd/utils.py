@@ -65,6 +65,54 @@ def _device_frame_stack(list_imgs):
     return torch.stack([f.contiguous() for f in frames])
 
 
+def _insert_plan(n_gaps: int, nmb_frames_target) -> Optional[np.ndarray]:
+    """Frames to insert into each of ``n_gaps`` gaps so that the total is ``nmb_frames_target``: ``floor(mean)`` plus a random
+    0/1 (the reference's scheme and its use of ``np.random.rand``, so a seeded numpy RNG reproduces it).  None: nothing to insert."""
+    n_missing = nmb_frames_target - n_gaps - 1
+    if n_missing < 1:
+        return None
+
+    mean_insert = n_missing / n_gaps
+    base = np.floor(mean_insert)
+    threshold = 1 - (mean_insert - base)
+    tries = 0
+    while True:
+        draw = np.random.rand(n_gaps)
+        per_gap = np.where(draw > threshold, 1.0, 0.0) + base
+        if per_gap.sum() == n_missing:
+            break
+        tries += 1
+        if tries > 100000:
+            print("add_frames_linear_interp: issue with inserting the right number of frames")
+            break
+    return per_gap.astype(np.int32)
+
+
+def _lerp_plan(per_gap):
+    """(left key frame, weight of the right one) of every output frame but the last key frame."""
+    left, weights = [], []
+    for g in range(len(per_gap)):
+        for w in np.linspace(0, 1, per_gap[g] + 2)[:-1]:        # w = 0 reproduces the key frame itself
+            left.append(g)
+            weights.append(float(w))
+    return left, weights
+
+
+def inbetween_frames_device(list_imgs, nmb_frames_target: int):
+    """``add_frames_linear_interp(list_imgs, nmb_frames_target=...)`` for device-resident key frames, with the result left on
+    the device: uint8 ``[n, H, W, 3]``, last key frame included (same frames, same single use of ``np.random.rand``).
+    None - before the RNG is touched - when the key frames are not device-resident frames of one size."""
+    dev = _device_frame_stack(list_imgs)
+    if dev is None:
+        return None
+    per_gap = _insert_plan(len(list_imgs) - 1, nmb_frames_target)
+    if per_gap is None:
+        return dev
+    from .hip import ops
+    left, weights = _lerp_plan(per_gap)
+    return torch.cat([ops.frames_lerp_u8(dev, left, weights), dev[-1:]])
+
+
 def add_frames_linear_interp(list_imgs: List[np.ndarray],
                              fps_target: Optional[Number] = None,
                              duration_target: Optional[Number] = None,
@@ -82,33 +130,14 @@ def add_frames_linear_interp(list_imgs: List[np.ndarray],
         nmb_frames_target = fps_target * duration_target
 
     n_gaps = len(list_imgs) - 1
-    n_missing = nmb_frames_target - n_gaps - 1
-    if n_missing < 1:
+    per_gap = _insert_plan(n_gaps, nmb_frames_target)
+    if per_gap is None:
         return list_imgs
-
-    mean_insert = n_missing / n_gaps
-    base = np.floor(mean_insert)
-    threshold = 1 - (mean_insert - base)
-    tries = 0
-    while True:
-        draw = np.random.rand(n_gaps)
-        per_gap = np.where(draw > threshold, 1.0, 0.0) + base
-        if per_gap.sum() == n_missing:
-            break
-        tries += 1
-        if tries > 100000:
-            print("add_frames_linear_interp: issue with inserting the right number of frames")
-            break
-    per_gap = per_gap.astype(np.int32)
 
     dev = _device_frame_stack(list_imgs)
     if dev is not None:                 # key frames resident in HBM (native pipe): blend them there, one copy back
         from .hip import ops
-        left, weights = [], []
-        for g in range(n_gaps):
-            for w in np.linspace(0, 1, per_gap[g] + 2)[:-1]:        # w = 0 reproduces the key frame itself
-                left.append(g)
-                weights.append(float(w))
+        left, weights = _lerp_plan(per_gap)
         blended = ops.frames_lerp_u8(dev, left, weights).cpu().numpy()
         return [blended[k] for k in range(blended.shape[0])] + [dev[-1].cpu().numpy()]
 
