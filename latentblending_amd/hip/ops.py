@@ -240,14 +240,17 @@ def fold_layernorm(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.T
 
 # ------------------------------------------------------------------------------ norms ------
 def groupnorm_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float,
-                   silu: bool) -> torch.Tensor:
-    """x: [B, H, W, C] (or [B, HW, C]) fp16 / fp32 -> fp16."""
+                   silu: bool, ldx: Optional[int] = None, ldy: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x: [B, H, W, C] (or [B, HW, C]) fp16 / fp32 -> fp16.  ``ldx`` / ``ldy``: pixel strides in elements (default C: dense);
+    ``out``: caller-owned fp16 output whose pixels are ``ldy`` apart."""
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
-    y = torch.empty(x.shape, dtype=F16, device=x.device)
+    y = torch.empty(x.shape, dtype=F16, device=x.device) if out is None else out
     ws = torch.empty(api.lb_groupnorm_workspace_bytes(B, groups) // 8, dtype=F64, device=x.device)
     api.lb_groupnorm_nhwc(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws.data_ptr(),
-                          B, HW, C, C, C, groups, eps, int(silu), int(x.dtype == F32), stream_ptr())
+                          B, HW, C, C if ldx is None else ldx, C if ldy is None else ldy, groups, eps, int(silu),
+                          int(x.dtype == F32), stream_ptr())
     return y
 
 
@@ -276,15 +279,18 @@ def conv_ch_stat_rows(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3) 
 
 
 def groupnorm_from_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, silu: bool,
-                         ch_stats: torch.Tensor, rows_per_sample: int) -> torch.Tensor:
+                         ch_stats: torch.Tensor, rows_per_sample: int, ldx: Optional[int] = None, ldy: Optional[int] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """GroupNorm of x [B, H, W, C] whose (sum, sum of squares) per (64-pixel row block, channel) the producing conv left in
-    ``ch_stats`` ([C, B * rows_per_sample, 2] fp32, channel-major, LB_GEMM_CH_STATS)."""
+    ``ch_stats`` ([C, B * rows_per_sample, 2] fp32, channel-major, LB_GEMM_CH_STATS).  ``ldx`` / ``ldy`` / ``out`` as in
+    ``groupnorm_nhwc``."""
     B, C_ = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C_)
-    y = torch.empty(x.shape, dtype=F16, device=x.device)
+    y = torch.empty(x.shape, dtype=F16, device=x.device) if out is None else out
     ws = torch.empty(api.lb_groupnorm_workspace_bytes(B, groups) // 8, dtype=F64, device=x.device)
     api.lb_groupnorm_from_stats(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ch_stats.data_ptr(), ws.data_ptr(),
-                                B, HW, C_, C_, C_, groups, eps, int(silu), int(x.dtype == F32), rows_per_sample, stream_ptr())
+                                B, HW, C_, C_ if ldx is None else ldx, C_ if ldy is None else ldy, groups, eps, int(silu),
+                                int(x.dtype == F32), rows_per_sample, stream_ptr())
     return y
 
 
@@ -393,7 +399,7 @@ def maxpool3s2(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def frames_lerp_u8(frames: torch.Tensor, left, weights) -> torch.Tensor:
+def frames_lerp_u8(frames: torch.Tensor, left, weights, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames: [n_key, H, W, 3] uint8 on the device; out[k] = uint8((1 - w[k]) * frames[left[k]] + w[k] * frames[left[k] + 1])
     in float64 with a truncating cast (reference utils.py:97 as numpy >= 2 evaluates it on the movie's key frames)."""
     assert frames.dtype == torch.uint8 and frames.is_contiguous()
@@ -401,11 +407,82 @@ def frames_lerp_u8(frames: torch.Tensor, left, weights) -> torch.Tensor:
     fb = frames[0].numel()
     left_d = torch.tensor(list(left), dtype=torch.int32, device=frames.device)
     w_d = torch.tensor(list(weights), dtype=F64, device=frames.device)
-    out = torch.empty((n_out,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
+    if out is None:
+        out = torch.empty((n_out,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
     for k0 in range(0, n_out, 65535):
         k1 = min(n_out, k0 + 65535)
         api.lb_frames_lerp_u8(frames.data_ptr(), left_d[k0:].data_ptr(), w_d[k0:].data_ptr(), out[k0:].data_ptr(), k1 - k0, fb,
                               stream_ptr())
+    return out
+
+
+def cast_f16_to_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    assert x.dtype == F16 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=F32, device=x.device)
+    api.lb_cast_f16_to_f32(x.data_ptr(), out.data_ptr(), x.numel(), stream_ptr())
+    return out
+
+
+def cast_f32_to_f16(x: torch.Tensor, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16(saturate(x * mul)): values beyond the fp16 range come back as +-65504."""
+    assert x.dtype == F32 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=F16, device=x.device)
+    api.lb_cast_f32_to_f16(x.data_ptr(), out.data_ptr(), x.numel(), float(mul), stream_ptr())
+    return out
+
+
+def fill_f32_(x: torch.Tensor, value: float) -> torch.Tensor:
+    assert x.dtype == F32 and x.is_contiguous()
+    api.lb_fill_f32(x.data_ptr(), x.numel(), float(value), stream_ptr())
+    return x
+
+
+def lpips_prep_u8(img: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """img: [..., 3] uint8 -> fp16 [..., 8]: the LPIPS scaling layer on 2 x / 255 - 1, channels 3..7 zero."""
+    assert img.dtype == torch.uint8 and img.is_contiguous() and img.shape[-1] == 3
+    if out is None:
+        out = torch.empty(tuple(img.shape[:-1]) + (8,), dtype=F16, device=img.device)
+    api.lb_lpips_prep_u8(img.data_ptr(), out.data_ptr(), img.numel() // 3, stream_ptr())
+    return out
+
+
+def lpips_tap(feats_a: Sequence[torch.Tensor], feats_b: Sequence[torch.Tensor], lin: torch.Tensor, acc: torch.Tensor,
+              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acc[pair] += mean over pixels of sum_c lin[c] * (a / (|a| + eps) - b / (|b| + eps))^2 for up to 16 pairs of [HW, C] fp16
+    features; ``acc``: fp32, at least one slot per pair, zeroed by the caller before the first tap."""
+    assert len(feats_a) == len(feats_b) and 0 < len(feats_a) <= 16 and acc.dtype == F32 and acc.numel() >= len(feats_a)
+    hw, c = feats_a[0].shape[-2], feats_a[0].shape[-1]
+    assert all(t.dtype == F16 and t.is_contiguous() and t.shape[-2:] == (hw, c) for t in list(feats_a) + list(feats_b))
+    if workspace is None:
+        workspace = torch.empty(16 * 128, dtype=F32, device=acc.device)
+    pa, keep_a = _ptr_array(feats_a)
+    pb, keep_b = _ptr_array(feats_b)
+    api.lb_lpips_tap(pa, pb, lin.data_ptr(), acc.data_ptr(), workspace.data_ptr(), len(feats_a), hw, c, stream_ptr())
+    return acc
+
+
+def embed_tokens(ids: torch.Tensor, tok_emb: torch.Tensor, pos_emb: torch.Tensor, seq: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r] = tok_emb[clamp(ids[r], 0, vocab - 1)] + pos_emb[r % seq] (CLIPTextEmbeddings); ids: int32 [rows]."""
+    assert ids.dtype == torch.int32 and tok_emb.dtype == F16 and pos_emb.dtype == F16
+    assert tok_emb.is_contiguous() and pos_emb.is_contiguous() and pos_emb.shape[0] >= seq
+    rows, (vocab, c) = ids.numel(), tok_emb.shape
+    if out is None:
+        out = torch.empty(rows, c, dtype=F16, device=ids.device)
+    api.lb_embed_tokens_f16(ids.data_ptr(), tok_emb.data_ptr(), pos_emb.data_ptr(), out.data_ptr(), rows, seq, c, vocab,
+                            stream_ptr())
+    return out
+
+
+def gather_rows(src: torch.Tensor, rows_idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = src[rows_idx[i]]; src: fp16 [rows, C] whose rows may be further apart than C; rows_idx: int32."""
+    assert src.dtype == F16 and rows_idx.dtype == torch.int32 and src.stride(1) == 1
+    n, c = rows_idx.numel(), src.shape[1]
+    if out is None:
+        out = torch.empty(n, c, dtype=F16, device=src.device)
+    api.lb_gather_rows_f16(src.data_ptr(), rows_idx.data_ptr(), out.data_ptr(), n, c, src.stride(0), stream_ptr())
     return out
 
 

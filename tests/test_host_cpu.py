@@ -980,3 +980,60 @@ def test_negative_prompt_semantics_follow_diffusers(cpu_backend):
     assert torch.equal(emb[1], p.encode_prompt("x", negative_prompt="")[1])          # holder default "" -> encoded ""
     dh.set_negative_prompt(["ugly", "ignored second entry"])
     assert torch.equal(dh.get_text_embedding("a reef")[1], p.encode_prompt("x", negative_prompt="ugly")[1])
+
+
+# ------------------------------------------------------------------ the guarded-buffer helper of the memory-contract tests
+@pytest.mark.parametrize("dtype", [torch.float16, torch.float32, torch.float64, torch.uint8, torch.int16])
+def test_guard_helper_detects_every_kind_of_stray_or_missing_write(dtype):
+    """tests/_guard.py on CPU tensors: a clean write passes; one element in a pad column, one in each guard and one valid element
+    left unwritten each make the matching assertion raise (a checker that cannot fail checks nothing)."""
+    from _guard import FRONT, guarded, poisoned
+    rows, cols, ld = 5, 12, 20
+
+    def fresh():
+        view, chk = guarded(rows, cols, ld, dtype, "cpu", back_rows=3)
+        assert view.shape == (rows, cols) and view.stride() == (ld, 1) and view.dtype == dtype
+        assert chk.bits.numel() * chk.bits.element_size() % 256 == 0 and FRONT * chk.bits.element_size() % 256 == 0
+        assert chk.bits.numel() - FRONT - rows * ld >= 3 * ld + 4096
+        return view, chk, chk.bits.view(dtype)
+
+    one = torch.ones((), dtype=dtype)
+    view, chk, flat = fresh()
+    chk.assert_intact("empty")
+    chk.assert_untouched("empty")
+    with pytest.raises(AssertionError, match="never written"):
+        chk.assert_fully_written("empty")
+    view.copy_(torch.arange(rows * cols).reshape(rows, cols).to(dtype))          # a clean write
+    chk.assert_intact("clean")
+    chk.assert_fully_written("clean")
+    with pytest.raises(AssertionError, match="refused"):
+        chk.assert_untouched("clean")
+    # one valid element left unwritten
+    view, chk, flat = fresh()
+    view.fill_(1)
+    flat[FRONT + 3 * ld + 7] = chk.bits.view(dtype)[0]
+    with pytest.raises(AssertionError, match=r"1 element\(s\).*row 3, column 7"):
+        chk.assert_fully_written("hole")
+    chk.assert_intact("hole")
+    # one element into a pad column, one into each guard
+    for where, index, told in (("pad", FRONT + 2 * ld + cols, "row 2, column 12 (pad columns)"),
+                               ("front", FRONT - 1, "row -1, column 19 (front guard)"),
+                               ("back", FRONT + rows * ld, "row 5, column 0 (back guard)"),
+                               ("back end", None, "back guard")):
+        view, chk, flat = fresh()
+        view.fill_(1)
+        flat[flat.numel() - 1 if index is None else index] = one
+        with pytest.raises(AssertionError) as err:
+            chk.assert_intact(where)
+        assert "1 element(s)" in str(err.value) and told in str(err.value), str(err.value)
+        chk.assert_fully_written(where)
+    # a second sentinel (uint8 outputs, where 0xA5 is a legal value)
+    view, chk = guarded(rows, cols, ld, torch.uint8, "cpu", sentinel=0x5A)
+    assert int(chk.bits[0]) == 0x5A and int(view[0, 0]) == 0x5A
+    # poisoned operands: data inside, the pad value in the pad columns and in the rows behind
+    if dtype.is_floating_point:
+        t = torch.arange(rows * cols).reshape(rows, cols).to(dtype)
+        v = poisoned(t, rows, cols, ld, float("nan"), extra_rows=4)
+        assert v.stride() == (ld, 1) and torch.equal(v, t)
+        whole = torch.as_strided(v, (rows + 4, ld), (ld, 1))
+        assert torch.isnan(whole[:rows, cols:]).all() and torch.isnan(whole[rows:]).all()
