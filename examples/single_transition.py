@@ -17,3 +17,4 @@ frames = engine.run_transition(fixed_seeds=[420, 421])
 print(f"{len(frames)} frames, fractions {engine.tree_fracts}")
 engine.write_movie_transition("transition.avi", duration_transition=4)
 # engine.write_movie_transition("transition.avi", duration_transition=4, encoder="device")   # blend + JPEG-encode on the GPU
+# engine.write_movie_transition("transition_1080p.avi", duration_transition=4, encoder="device", size_output=(1920, 1080))   # ... at another size

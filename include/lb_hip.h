@@ -263,6 +263,18 @@ int lb_jpeg_entropy(const void* coef_i16, void* workspace, void* out, long out_c
                     int subsampling, void* stream);
 long lb_jpeg_workspace_bytes(int n, int H, int W, int subsampling);     /* worst case of the tables for any int16 input; -1: size */
 
+/* ---- movie frames at another size: Pillow's 8-bit resampler (Image.resize with BOX / BILINEAR / BICUBIC / LANCZOS,
+ *      reducing_gap=None) byte for byte; the reference leaves movie sizes to lunar_tools' ffmpeg writer.
+ *      src [n][Hin][Win][3], tmp [n][Hin][Wout][3], dst [n][Hout][Wout][3] uint8, contiguous.  Per axis (x: Win -> Wout, y: Hin ->
+ *      Hout) the host tables of latentblending_amd/resample.py: start / count [size_out] and coef [size_out][kmax] int32 on the
+ *      device, 22-bit fixed point; out = clip8((2^21 + sum_{k < count} in[start + k] * coef[k]) >> 22) in int32.  A horizontal pass
+ *      src -> tmp, then a vertical pass tmp -> dst; an axis that keeps its size is skipped (its tables and tmp may then be null), and
+ *      with both unchanged dst is a copy of src.  Windows are clamped to the source on the device; kmax >= max(count) is the
+ *      caller's contract.  n <= 65535, Hout <= 65535, every frame below 2^31 bytes, kmax_x <= 12287. */
+int lb_resample_u8(const void* src, void* tmp, void* dst, int n, int Hin, int Win, int Hout, int Wout,
+                   const int* start_x, const int* count_x, const int* coef_x, int kmax_x,
+                   const int* start_y, const int* count_y, const int* coef_y, int kmax_y, void* stream);
+
 /* ---- launch programs (the MI355X-native stand-in for the reference's optional stable-fast
  *      compile, blending_engine.py:88-96): record the launchers above once, replay them from
  *      C++ or as one hipGraph ------------------------------------------------------------ */

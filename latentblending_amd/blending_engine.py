@@ -95,6 +95,8 @@ class BlendingEngine:
         #                                     bench line needs ONE round instead of two
         self._level_priors = {}             # (idx_injection, stems) -> [(f_left, f_right, f_mid)] in the order the level was committed
         self.movie_encoder = "host"         # write_movie_transition: "host" (movie writer on the CPU) or "device" (HIP JPEG encoder, AVI written here)
+        self.movie_size = None              # write_movie_transition / write_imgs_transition: output size (W, H); None = the render size
+        self.movie_resample = "bicubic"     # ... and the filter that gets the key frames there: "box", "bilinear", "bicubic", "lanczos"
         self.fuse_anchor_round = True       # single-level trees: first round shares the anchors' UNet batches
         self.fuse_recycled_anchor = True    # ... also when an anchor is recycled (swap_forward chains, precomputed key frames): the
         #                                     fused wavefront takes the stored trajectory as given and denoises only the other one
@@ -946,45 +948,82 @@ class BlendingEngine:
         return self.dh.get_text_embedding(prompt)
 
     # ------------------------------------------------------------------ output ------------
-    def write_imgs_transition(self, dp_img):
-        """Write the transition frames as ``lowres_img_XXXX.jpg`` into ``dp_img``."""
+    def _movie_output(self, size_output, resample):
+        """(output size (W, H) or None, filter name) of the movie / image writers: the arguments, else ``movie_size`` /
+        ``movie_resample``.  ValueError for a size that is not two positive integers or an unknown filter."""
+        from .resample import check_filter, check_size
+        size = self.movie_size if size_output is None else size_output
+        filt = check_filter(self.movie_resample if resample is None else resample)
+        return (None if size is None else check_size(size, "size_output")), filt
+
+    def write_imgs_transition(self, dp_img, size_output=None, resample=None):
+        """Write the transition frames as ``lowres_img_XXXX.jpg`` into ``dp_img``; with ``size_output=(W, H)`` resized as
+        ``write_movie_transition`` resizes its key frames (on the device when the frames live there, then one copy back)."""
+        size, filt = self._movie_output(size_output, resample)
+        imgs = self.tree_final_imgs
+        if size is not None:
+            from .utils import resize_frames_device, resize_frames_host
+            dev = resize_frames_device(imgs, (size[1], size[0]), filt)
+            imgs = list(dev.cpu().numpy()) if dev is not None else resize_frames_host(imgs, (size[1], size[0]), filt)
         os.makedirs(dp_img, exist_ok=True)
-        for i, img in enumerate(self.tree_final_imgs):
+        for i, img in enumerate(imgs):
             leaf = img if isinstance(img, Image.Image) else Image.fromarray(np.asarray(img))
             leaf.save(os.path.join(dp_img, f"lowres_img_{str(i).zfill(4)}.jpg"))
 
-    def write_movie_transition(self, fp_movie, duration_transition, fps=30, encoder=None):
+    def write_movie_transition(self, fp_movie, duration_transition, fps=30, encoder=None, size_output=None, resample=None):
         """Linearly in-between the frames to ``duration_transition*fps`` frames and write a movie.
 
         ``encoder`` (default: ``self.movie_encoder``, initially "host"): "host" encodes every frame with the movie writer on the
         host; "device" blends AND JPEG-encodes the frames on the GPU (``csrc/jpeg.hip``) and writes the Motion-JPEG AVI itself,
-        so only compressed bytes leave the device.  "device" needs device-resident key frames of a size that is a multiple of 8
-        both ways; otherwise it warns once and takes the host path."""
+        so only compressed bytes leave the device.  "device" needs device-resident key frames and a movie size that is a multiple
+        of 8 both ways; otherwise it warns once and takes the host path.
+
+        ``size_output=(W, H)`` (default: ``self.movie_size``, initially None = the render size; the order of ``set_dimensions``)
+        writes the movie at another size: the KEY frames are resized with ``resample`` ("box", "bilinear", "bicubic", "lanczos";
+        default ``self.movie_resample``, initially "bicubic") exactly as ``PIL.Image.resize`` does it - on the host by Pillow, on
+        the device by ``csrc/resample.hip`` - and the in-betweening then runs at the output size as before."""
         encoder = self.movie_encoder if encoder is None else encoder
         if encoder not in ("host", "device"):
             raise ValueError(f"write_movie_transition: encoder must be 'host' or 'device', not {encoder!r}")
-        if encoder == "device" and self._write_movie_transition_device(fp_movie, duration_transition, fps):
+        size, filt = self._movie_output(size_output, resample)
+        if encoder == "device" and self._write_movie_transition_device(fp_movie, duration_transition, fps, size, filt):
             return
         from .movie import MovieSaver, fill_up_frames_linear_interpolation
-        frames = fill_up_frames_linear_interpolation(self.tree_final_imgs, duration_transition, fps)
+        imgs, h, w = self.tree_final_imgs, self.dh.height_img, self.dh.width_img
+        if size is not None:
+            from .utils import resize_frames_host
+            w, h = size
+            imgs = resize_frames_host(imgs, (h, w), filt)
+        frames = fill_up_frames_linear_interpolation(imgs, duration_transition, fps)
         if os.path.isfile(fp_movie):
             os.remove(fp_movie)
-        saver = MovieSaver(fp_movie, fps=fps, shape_hw=[self.dh.height_img, self.dh.width_img])
+        saver = MovieSaver(fp_movie, fps=fps, shape_hw=[h, w])
         for frame in tqdm(frames, disable=not self.verbose):
             saver.write_frame(frame)
         saver.finalize()
 
-    def _write_movie_transition_device(self, fp_movie, duration_transition, fps) -> bool:
+    def _write_movie_transition_device(self, fp_movie, duration_transition, fps, size=None, filt="bicubic") -> bool:
         """The "device" path of ``write_movie_transition``; False (after one warning, nothing written, numpy's RNG untouched)
-        when it does not apply."""
+        when it does not apply.  With an output size the key frames are resized on the device first; an output size that is no
+        multiple of 8 is still resized and blended there and handed to ``write_frames_device``, which encodes it on the host."""
         from .movie import AviMovieSaver
-        from .utils import inbetween_frames_device
-        h, w = self.dh.height_img, self.dh.width_img
-        frames = inbetween_frames_device(self.tree_final_imgs, int(round(duration_transition * fps))) if h % 8 == 0 and w % 8 == 0 else None
-        if frames is None or list(frames.shape[1:3]) != [h, w]:
-            warnings.warn("write_movie_transition: encoder='device' needs device-resident key frames whose height and width are "
-                          "multiples of 8; encoding on the host", UserWarning, stacklevel=3)
-            return False
+        from .utils import inbetween_frames_device, resize_frames_device
+        n_frames = int(round(duration_transition * fps))
+        if size is None:
+            h, w = self.dh.height_img, self.dh.width_img
+            frames = inbetween_frames_device(self.tree_final_imgs, n_frames) if h % 8 == 0 and w % 8 == 0 else None
+            if frames is None or list(frames.shape[1:3]) != [h, w]:
+                warnings.warn("write_movie_transition: encoder='device' needs device-resident key frames whose height and width are "
+                              "multiples of 8; encoding on the host", UserWarning, stacklevel=3)
+                return False
+        else:
+            w, h = size
+            keys = resize_frames_device(self.tree_final_imgs, (h, w), filt)
+            frames = inbetween_frames_device(keys, n_frames) if keys is not None else None
+            if frames is None:
+                warnings.warn("write_movie_transition: encoder='device' needs device-resident key frames of one size and an output "
+                              "frame of a multiple of 16 bytes; resizing and encoding on the host", UserWarning, stacklevel=3)
+                return False
         if os.path.isfile(fp_movie):
             os.remove(fp_movie)
         saver = AviMovieSaver(fp_movie, fps=fps, shape_hw=[h, w])

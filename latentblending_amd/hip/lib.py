@@ -115,6 +115,7 @@ SIGNATURES = {
     "lb_jpeg_coefficient_count": (_l, [_i, _i, _i, _i]),
     "lb_jpeg_entropy": (_i, [_vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _vp]),
     "lb_jpeg_workspace_bytes": (_l, [_i, _i, _i, _i]),
+    "lb_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "lb_program_create": (_vp, []),
     "lb_program_destroy": (None, [_vp]),
     "lb_program_begin_record": (_i, [_vp]),

@@ -589,3 +589,58 @@ def jpeg_encode_u8(frames_u8: torch.Tensor, quality: int = 92, subsampling: str 
         coef = jpeg_coefficients_u8(part, quality, subsampling)
         out.extend(b"".join((header, scan, EOI)) for scan in jpeg_scan_from_coefficients(coef, h, w, subsampling))
     return out
+
+
+_RESAMPLE_TABLES: dict = {}
+
+
+def _resample_tables(hin: int, win: int, hout: int, wout: int, filter: str, device):
+    """((start, count, coef, kmax) for x, the same for y) on the device; None for an axis that keeps its size.  One upload per
+    (sizes, filter, device)."""
+    key = (hin, win, hout, wout, filter, str(device))
+    if key not in _RESAMPLE_TABLES:
+        from ..resample import resample_tables
+
+        def axis(size_in, size_out):
+            if size_in == size_out:
+                return None
+            start, count, coef = resample_tables(size_in, size_out, filter)
+            return (torch.from_numpy(start).to(device), torch.from_numpy(count).to(device),
+                    torch.from_numpy(coef).contiguous().to(device), int(coef.shape[1]))
+        _RESAMPLE_TABLES[key] = (axis(win, wout), axis(hin, hout))
+    return _RESAMPLE_TABLES[key]
+
+
+def resample_u8_into(frames: torch.Tensor, tmp: Optional[torch.Tensor], out: torch.Tensor, tables_x, tables_y) -> None:
+    """The launcher on caller-owned buffers (capturable): frames [n, Hin, Win, 3] -> out [n, Hout, Wout, 3] through tmp
+    [n, Hin, Wout, 3]; ``tables_*`` = (start, count, coef, kmax) on the device, None for an axis that keeps its size (tmp may be
+    None unless both axes change).  At most 65535 frames."""
+    n, hin, win, _ = frames.shape
+    hout, wout = out.shape[1:3]
+    sx, cx, kx, kmx = tables_x if tables_x is not None else (None, None, None, 0)
+    sy, cy, ky, kmy = tables_y if tables_y is not None else (None, None, None, 0)
+    api.lb_resample_u8(frames.data_ptr(), _ptr(tmp), out.data_ptr(), n, hin, win, hout, wout, _ptr(sx), _ptr(cx), _ptr(kx), kmx,
+                       _ptr(sy), _ptr(cy), _ptr(ky), kmy, stream_ptr())
+
+
+def resample_u8(frames: torch.Tensor, size_hw, filter: str = "bicubic", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[n, Hin, Win, 3] uint8 device frames resized to ``size_hw = (Hout, Wout)``: Pillow's ``Image.resize`` with ``filter``
+    ("box", "bilinear", "bicubic", "lanczos") and ``reducing_gap=None``, byte for byte."""
+    from ..resample import check_filter, check_size
+    check_filter(filter)
+    hout, wout = check_size(size_hw, "size_hw")
+    assert frames.dtype == torch.uint8 and frames.is_cuda and frames.dim() == 4 and frames.shape[-1] == 3, \
+        "resample_u8: [n, H, W, 3] uint8 frames on the device"
+    frames = frames.contiguous()
+    n, hin, win, _ = frames.shape
+    dev = frames.device
+    if out is None:
+        out = torch.empty((n, hout, wout, 3), dtype=torch.uint8, device=dev)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, hout, wout, 3) and out.device == dev
+    tx, ty = _resample_tables(hin, win, hout, wout, filter, dev)
+    chunk = min(n, 65535)
+    tmp = torch.empty((chunk, hin, wout, 3), dtype=torch.uint8, device=dev) if tx is not None and ty is not None else None
+    for k0 in range(0, n, 65535):
+        k1 = min(n, k0 + 65535)
+        resample_u8_into(frames[k0:k1], None if tmp is None else tmp[:k1 - k0], out[k0:k1], tx, ty)
+    return out

@@ -50,7 +50,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          duration_single_trans: float = 10, list_negative_prompts: Optional[Sequence[str]] = None,
                          fps: int = 30, dp_parts: str = ".", keep_parts: bool = True,
                          on_segment: Optional[Callable[[int, List], None]] = None,
-                         pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None) -> List[List]:
+                         pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
+                         movie_size=None, movie_resample: Optional[str] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -66,6 +67,7 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     frames, order of ancestral noise draws).
 
     ``movie_encoder``: "host" / "device" for every part's ``write_movie_transition`` (None: the engine's ``movie_encoder``).
+    ``movie_size`` / ``movie_resample``: its ``size_output=(W, H)`` / ``resample=`` (None: the engine's ``movie_size`` / ``movie_resample``).
     """
     n = len(list_prompts)
     if n < 2:
@@ -106,7 +108,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
             on_segment(i, frames)
         if fp_movie is not None:
             fp_part = os.path.join(dp_parts, f"tmp_part_{str(i).zfill(3)}.mp4")
-            be.write_movie_transition(fp_part, duration_single_trans, fps=fps, encoder=movie_encoder)
+            be.write_movie_transition(fp_part, duration_single_trans, fps=fps, encoder=movie_encoder, size_output=movie_size,
+                                      resample=movie_resample)
             parts.append(fp_part)
     if fp_movie is not None:
         from .movie import concatenate_movies
@@ -134,11 +137,12 @@ def _precompute_chain(be, list_prompts, list_seeds, list_negative_prompts):
 
 def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_single_trans: float = 10,
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
-                   movie_encoder: Optional[str] = None) -> List[List]:
+                   movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None) -> List[List]:
     """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain."""
     header, items = load_movie_json(fp_json)
     be.set_dimensions((header["width"], header["height"]))
     be.set_num_inference_steps(header["num_inference_steps"])
     return run_multi_transition(be, [it["prompt"] for it in items], [it["seed"] for it in items], fp_movie,
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
-                                dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder)
+                                dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
+                                movie_size=movie_size, movie_resample=movie_resample)

@@ -36,7 +36,8 @@ _ENGINE_FIELDS = ("prompt1", "prompt2", "text_embedding1", "text_embedding2", "n
                   "branch1_crossfeed_power", "branch1_crossfeed_range", "branch1_crossfeed_decay",
                   "parental_crossfeed_power", "parental_crossfeed_range", "parental_crossfeed_decay",
                   "num_inference_steps", "list_idx_injection", "list_nmb_stems", "image1_lowres", "image2_lowres",
-                  "multi_transition_img_first", "multi_transition_img_last", "_preset_anchor_frames", "stats", "movie_encoder")
+                  "multi_transition_img_first", "multi_transition_img_last", "_preset_anchor_frames", "stats", "movie_encoder",
+                  "movie_size", "movie_resample")
 # holder attributes that follow them
 _HOLDER_FIELDS = ("negative_prompt", "guidance_scale", "num_inference_steps", "width_img", "height_img", "width_latent",
                   "height_latent")

@@ -56,7 +56,11 @@ def interpolate_linear(p0, p1, fract_mixing):
 
 def _device_frame_stack(list_imgs):
     """[n, H, W, 3] uint8 device tensor when every frame is a device-resident ``DeviceImage`` of one size whose byte
-    count the kernel accepts (multiple of 16), else None (host path)."""
+    count the kernel accepts (multiple of 16), else None (host path).  A uint8 device tensor of that shape is taken as it is."""
+    if isinstance(list_imgs, torch.Tensor):
+        t = list_imgs
+        ok = t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[0] > 0 and t.shape[-1] == 3 and t[0].numel() % 16 == 0
+        return t.contiguous() if ok else None
     frames = [getattr(im, "_lb_u8", None) for im in list_imgs]
     if not frames or any(f is None or not f.is_cuda or f.shape != frames[0].shape for f in frames):
         return None
@@ -111,6 +115,39 @@ def inbetween_frames_device(list_imgs, nmb_frames_target: int):
     from .hip import ops
     left, weights = _lerp_plan(per_gap)
     return torch.cat([ops.frames_lerp_u8(dev, left, weights), dev[-1:]])
+
+
+def resize_frames_device(list_imgs, size_hw, filter: str = "bicubic"):
+    """Device-resident frames (a list of ``DeviceImage`` of one size, or a uint8 ``[n, H, W, 3]`` device tensor) resized to
+    ``size_hw = (H, W)`` on the device as ``PIL.Image.resize`` does it with ``filter`` ("box", "bilinear", "bicubic", "lanczos") and
+    ``reducing_gap=None``, byte for byte: uint8 ``[n, H, W, 3]``, left on the device.  None when the frames are not device-resident
+    frames of one size; ValueError for an unknown filter or a size that is not positive."""
+    from .resample import check_filter, check_size
+    check_filter(filter)
+    size_hw = check_size(size_hw, "size_hw")
+    if isinstance(list_imgs, torch.Tensor):
+        t = list_imgs
+        dev = t if t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[0] > 0 and t.shape[-1] == 3 else None
+    else:
+        frames = [getattr(im, "_lb_u8", None) for im in list_imgs]
+        if not frames or any(f is None or not f.is_cuda or f.shape != frames[0].shape for f in frames):
+            dev = None
+        else:
+            dev = torch.stack([f.contiguous() for f in frames])
+    if dev is None:
+        return None
+    from .hip import ops
+    return ops.resample_u8(dev, size_hw, filter)
+
+
+def resize_frames_host(list_imgs, size_hw, filter: str = "bicubic") -> list:
+    """The same resize on the host: every frame (PIL image or uint8 H x W x 3 array) through ``PIL.Image.resize``."""
+    from PIL import Image
+    from .resample import check_size, pil_filter
+    h, w = check_size(size_hw, "size_hw")
+    flt = pil_filter(filter)
+    return [(im if isinstance(im, Image.Image) else Image.fromarray(np.asarray(im))).resize((w, h), flt, reducing_gap=None)
+            for im in list_imgs]
 
 
 def add_frames_linear_interp(list_imgs: List[np.ndarray],
