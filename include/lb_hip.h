@@ -223,6 +223,7 @@ int lb_sinusoid_f16(const float* vals_dev, int rows, int per_row, int val_stride
 int lb_copy_cols_f16(const void* src, void* dst, long rows, int cols, int ld_src, int ld_dst,
                      int dst_off, void* stream);
 int lb_cast_f16_to_f32(const void* x, void* y, long n, void* stream);
+/* y = fp16(x * mul) saturated to +-65504 (also for +-inf); a NaN stays a NaN; mul = 0 is read as 1 */
 int lb_cast_f32_to_f16(const void* x, void* y, long n, float mul, void* stream);
 int lb_nchw_to_nhwc_f16(const void* x, void* y, int B, int C, int HW, int ld, float mul, void* stream);
 int lb_nhwc_to_nchw_f16(const void* x, void* y, int B, int C, int HW, int ld, void* stream);

@@ -350,10 +350,11 @@ __global__ void __launch_bounds__(256) attn_fwd_d64_kernel(const LbAttnParams p)
 // self-attention (profiles/r04_attention_pmc.json): 233 VALU instructions per (wave, tile) = 1,063 issue cycles (a wave64 VALU
 // instruction occupies its SIMD for 4 cycles, v_exp_f32 for 8) against 576 cycles of MFMA - with three waves per SIMD the VALU
 // pipe is 75 % busy and the matrix pipe 40 %: the kernel is VALU-bound, not matrix-bound.  What went:
-//   * the 32 v_fma (score * scale * log2e - max) per tile: Q is multiplied by scale * log2e ONCE in the prologue (one extra fp16
-//     rounding of Q, of the size of the rounding the projection already applied), and -max enters as the ACCUMULATOR INPUT of the
-//     first QK^T MFMA, so the matrix pipe returns (score - max) in the exp2 domain and the probabilities are v_exp_f32 of the
-//     accumulators as they are;
+//   * the 32 v_fma (score * scale * log2e - max) per tile: -max enters as the ACCUMULATOR INPUT of the first QK^T MFMA, so the matrix
+//     pipe returns (score - max).  Q is multiplied ONCE in the prologue by the power-of-two part of scale * log2e (exact in fp16);
+//     the remaining factor in [1, 2) multiplies the accumulators in front of v_exp_f32 (packed fp32 multiplies, two scores each).
+//     (Until the value-range tests Q carried the whole factor, rounded to fp16: that rounding moves a score by up to
+//     2^-11 sum_d |q_d k_d| scale log2e - several per cent on the probabilities of tying keys once scores reach the hundreds.)
 //   * the two ds_bpermute round trips of every row-max: v_permlane16_swap / v_permlane32_swap (VALU, no LDS crossbar);
 //   * ~50 instructions of per-tile bookkeeping: 64-bit address arithmetic behind exec-masked branches for every direct-to-LDS
 //     request (now a uniform base + a 32-bit running offset clamped to the last row - rows past the sequence re-read the last row,
@@ -409,8 +410,11 @@ __global__ void __launch_bounds__(256) attn_fwd_d64_stream_kernel(const LbAttnPa
 
     const int nt = (p.Skv + KT - 1) / KT;
     // ---- prologue: Q fragments (b operand: k = d = 32 s + 8 g .. +8) first, then tiles 0 .. NS-2 in flight; Q is carried into the
-    //      exp2 domain here: q * (scale * log2 e), rounded to fp16 once ----
+    //      score domain here: scale * log2(e) = sc_frac * sc_pow2 with sc_pow2 a power of two and 1 <= sc_frac < 2; q * sc_pow2 is
+    //      EXACT in fp16, and sc_frac multiplies the fp32 accumulators in front of v_exp_f32 (running maximum, ATT_DEFER and the
+    //      accumulator input of QK^T live in the accumulators' domain, i.e. exp2 units / sc_frac) ----
     const float sc = p.scale * 1.44269504088896340736f;
+    const float sc_pow2 = __uint_as_float(__float_as_uint(sc) & 0xff800000u), sc_frac = sc / sc_pow2, defer = ATT_DEFER / sc_frac;
     f16x8 qraw[QG][2];      // (rows past Sq re-read the last row - never stored: no exec-masked load blocks, see attn_fwd_d64_kernel)
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
@@ -428,7 +432,7 @@ __global__ void __launch_bounds__(256) attn_fwd_d64_stream_kernel(const LbAttnPa
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) qf[qg][s][e] = (f16)((float)qraw[qg][s][e] * sc);
+            for (int e = 0; e < 8; ++e) qf[qg][s][e] = (f16)((float)qraw[qg][s][e] * sc_pow2);
 
     // ---- loop-invariant LDS offsets (halves, relative to the stage base): as in attn_fwd_d64_kernel ----
     int koff[2];
@@ -504,11 +508,11 @@ __global__ void __launch_bounds__(256) attn_fwd_d64_stream_kernel(const LbAttnPa
             // mx is RELATIVE to the running maximum.  Deferred rescale: the maximum moves (and O, l are rescaled, and the scores
             // of this tile re-based) only when some query of the wave outgrew it by more than 2^ATT_DEFER; the first tile sets it
             // (every query sees at least key 0 there: Skv_valid > 0, causal k <= q).
-            if (t == 0 || __any(mx > ATT_DEFER)) {
+            if (t == 0 || __any(mx > defer)) {
                 const float m_abs = mx + m_use[qg];
                 const float m_new = t == 0 ? m_abs : fmaxf(m_use[qg], m_abs);
                 const float delta = m_new - m_use[qg];
-                const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
+                const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta * sc_frac);
                 m_use[qg] = m_new;
                 negm[qg] = (f32x4){-m_new, -m_new, -m_new, -m_new};
 #pragma unroll
@@ -526,7 +530,7 @@ __global__ void __launch_bounds__(256) attn_fwd_d64_stream_kernel(const LbAttnPa
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    pf[qg][kb >> 1][(kb & 1) * 4 + r] = (f16)__builtin_amdgcn_exp2f(sacc[qg][kb][r]);
+                    pf[qg][kb >> 1][(kb & 1) * 4 + r] = (f16)__builtin_amdgcn_exp2f(sacc[qg][kb][r] * sc_frac);
         }
         // ---- O^T += V^T . P^T ----  (V^T fragments of both k-steps are requested before the first MFMA)
         {
@@ -654,7 +658,8 @@ __global__ void __launch_bounds__(512, QG == 1 ? 4 : 2) attn_fwd_d64_pp_kernel(c
     };
 
     const int nt = (p.Skv + KT - 1) / KT;
-    const float sc = p.scale * 1.44269504088896340736f;
+    const float sc = p.scale * 1.44269504088896340736f;      // = sc_frac * sc_pow2, as in attn_fwd_d64_stream_kernel
+    const float sc_pow2 = __uint_as_float(__float_as_uint(sc) & 0xff800000u), sc_frac = sc / sc_pow2, defer = ATT_DEFER / sc_frac;
     f16x8 qraw[QG][2];      // (rows past Sq re-read the last row - never stored: no exec-masked load blocks, see attn_fwd_d64_kernel)
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
@@ -672,7 +677,7 @@ __global__ void __launch_bounds__(512, QG == 1 ? 4 : 2) attn_fwd_d64_pp_kernel(c
 #pragma unroll
         for (int s = 0; s < 2; ++s)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) qf[qg][s][e] = (f16)((float)qraw[qg][s][e] * sc);
+            for (int e = 0; e < 8; ++e) qf[qg][s][e] = (f16)((float)qraw[qg][s][e] * sc_pow2);
 
     int koff[2];
 #pragma unroll
@@ -755,11 +760,11 @@ __global__ void __launch_bounds__(512, QG == 1 ? 4 : 2) attn_fwd_d64_pp_kernel(c
                 const auto r32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
                 mx = fmaxf(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
             }
-            if (t == 0 || __any(mx > ATT_DEFER)) {
+            if (t == 0 || __any(mx > defer)) {
                 const float m_abs = mx + m_use[qg];
                 const float m_new = t == 0 ? m_abs : fmaxf(m_use[qg], m_abs);
                 const float delta = m_new - m_use[qg];
-                const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta);
+                const float alpha = t == 0 ? 1.f : __builtin_amdgcn_exp2f(-delta * sc_frac);
                 m_use[qg] = m_new;
                 negm[qg] = (f32x4){-m_new, -m_new, -m_new, -m_new};
 #pragma unroll
@@ -777,7 +782,7 @@ __global__ void __launch_bounds__(512, QG == 1 ? 4 : 2) attn_fwd_d64_pp_kernel(c
             for (int kb = 0; kb < NKB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    pf[qg][kb >> 1][(kb & 1) * 4 + r] = (f16)__builtin_amdgcn_exp2f(sacc[qg][kb][r]);
+                    pf[qg][kb >> 1][(kb & 1) * 4 + r] = (f16)__builtin_amdgcn_exp2f(sacc[qg][kb][r] * sc_frac);
         }
         if (!grpB) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");     // (end of an odd phase: tile t + 1)
         // ================= PV(t) + QK(t + 1): matrix phase =================

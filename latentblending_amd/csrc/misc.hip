@@ -65,13 +65,15 @@ __global__ void cast_f16_f32_kernel(const f16* __restrict__ x, float* __restrict
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = (float)x[i];
 }
 __global__ void cast_f32_f16_kernel(const float* __restrict__ x, f16* __restrict__ y, long n, float mul) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        y[i] = (f16)fminf(fmaxf(x[i] * mul, -65504.f), 65504.f);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float v = x[i] * mul;     // (fmaxf / fminf return the other operand for a NaN: it would come back as -65504)
+        y[i] = (f16)(__builtin_isnan(v) ? v : fminf(fmaxf(v, -65504.f), 65504.f));
+    }
 }
 extern "C" int lb_cast_f16_to_f32(const void* x, void* y, long n, void* stream) {
     LB_DISPATCH_STMT("lb_cast_f16_to_f32", hipLaunchKernelGGL(cast_f16_f32_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const f16*)x, (float*)y, n));
 }
-// y = fp16(saturate(x * mul)); mul = 0 is read as 1 (a power-of-two down-scale keeps the VAE's
+// y = fp16(saturate(x * mul)), NaN stays NaN; mul = 0 is read as 1 (a power-of-two down-scale keeps the VAE's
 // fp32 residual stream inside fp16 range for the next conv, whose epilogue multiplies back)
 extern "C" int lb_cast_f32_to_f16(const void* x, void* y, long n, float mul, void* stream) {
     const float m = mul == 0.f ? 1.f : mul;

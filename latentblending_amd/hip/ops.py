@@ -425,7 +425,7 @@ def cast_f16_to_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torc
 
 
 def cast_f32_to_f16(x: torch.Tensor, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp16(saturate(x * mul)): values beyond the fp16 range come back as +-65504."""
+    """fp16(saturate(x * mul)): values beyond the fp16 range (+-inf included) come back as +-65504, a NaN stays a NaN."""
     assert x.dtype == F32 and x.is_contiguous()
     if out is None:
         out = torch.empty(x.shape, dtype=F16, device=x.device)

@@ -1037,3 +1037,45 @@ def test_guard_helper_detects_every_kind_of_stray_or_missing_write(dtype):
         assert v.stride() == (ld, 1) and torch.equal(v, t)
         whole = torch.as_strided(v, (rows + 4, ld), (ld, 1))
         assert torch.isnan(whole[:rows, cols:]).all() and torch.isnan(whole[rows:]).all()
+
+
+# ------------------------------------------------------------------ the element-wise bound helper of the value-range tests
+def test_elementwise_bound_sees_what_check_close_cannot():
+    """tests/_parity.py: an error of twice the derived bound planted in ONE small element (|ref| < 1e-3) makes check_elementwise raise -
+    naming the element - while the suite's check_close (2^-8 * max|ref| + floor) still passes: the gap the value-range tests close.
+    An exact fp16 rounding of the reference passes both; a zero where the reference is a non-zero fp16 subnormal fails."""
+    from _parity import absdot, check_close, check_elementwise, contraction_bound, norm_bound, store_bound
+    g = torch.Generator().manual_seed(7)
+    A = torch.randn(40, 64, generator=g).half().double()
+    W = (torch.randn(24, 64, generator=g) * 64 ** -0.5).half().double()
+    ref = A @ W.t()
+    k = int(ref.abs().argmin())
+    i, j = k // 24, k % 24
+    ref[i, j] = 5e-4 if abs(float(ref[i, j])) >= 1e-3 else ref[i, j]
+    assert abs(float(ref[i, j])) < 1e-3
+    bound = contraction_bound(A, W, 64, ref)
+    assert torch.equal(bound, contraction_bound(A, W, 64, ref, absdot64=absdot(A, W)))
+    assert float(bound[i, j]) < 1e-4 and bool((bound > 0).all())
+    log = {}
+    exact = ref.half()
+    assert check_elementwise(log, "exact", exact, ref, store_bound(ref)) <= 1.0          # round-to-nearest alone is inside its own term
+    check_elementwise(log, "exact_full", exact, ref, bound)
+    check_close(log, "exact_cc", exact, ref.float())
+    planted = ref.clone()
+    planted[i, j] += 2 * bound[i, j]
+    check_close(log, "planted_cc", planted, ref.float())                                  # today's check cannot see it
+    with pytest.raises(AssertionError, match=rf"1 of 960 elements.*\({i}, {j}\)"):
+        check_elementwise(log, "planted", planted, ref, bound)
+    assert log["planted"]["bad"] == 1 and 1.9 < log["planted"]["worst_err_over_bound"] < 2.1
+    # a flushed subnormal: the reference is a non-zero fp16 subnormal, the output exactly zero
+    sub = torch.full((4, 4), 3 * 2.0 ** -24, dtype=torch.float64)
+    check_elementwise(log, "sub_exact", sub.half(), sub, store_bound(sub))
+    with pytest.raises(AssertionError):
+        check_elementwise(log, "sub_flushed", torch.zeros(4, 4, dtype=torch.float16), sub, store_bound(sub))
+    # non-finite outputs fail; the norm bound is relative for large outputs and 2^-10 max|gamma| for small ones
+    bad = exact.clone()
+    bad[0, 0] = float("inf")
+    with pytest.raises(AssertionError):
+        check_elementwise(log, "inf", bad, ref, bound)
+    nb = norm_bound(torch.tensor([0.0, 8.0], dtype=torch.float64), torch.tensor([0.5, -2.0]))
+    assert torch.equal(nb, torch.tensor([2.0 ** -9, 2.0 ** -7 + 2.0 ** -9], dtype=torch.float64))
