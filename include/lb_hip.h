@@ -280,9 +280,14 @@ int lb_resample_u8(const void* src, void* tmp, void* dst, int n, int Hin, int Wi
  *      compile, blending_engine.py:88-96): record the launchers above once, replay them from
  *      C++ or as one hipGraph ------------------------------------------------------------ */
 void* lb_program_create(void);
+/* destroying the program that is recording on the calling thread ends that recording */
 void lb_program_destroy(void* prog);
-int lb_program_begin_record(void* prog);   /* launchers called on this thread are recorded, not run */
+/* launchers called on this thread are recorded, not run: a launcher refuses while recording what it refuses when called directly
+ * (and then records nothing).  Beginning a new recording on an instantiated program drops its graph: lb_program_launch runs the
+ * ops eagerly until lb_program_instantiate is called again. */
+int lb_program_begin_record(void* prog);
 int lb_program_end_record(void* prog);
+int lb_program_recording(void);            /* 1 while the calling thread records (recording is per thread), else 0 */
 int lb_program_num_ops(void* prog);
 const char* lb_program_op_name(void* prog, int i);
 int lb_program_run(void* prog, void* stream);                        /* eager replay */

@@ -432,13 +432,14 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream) {
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
     constexpr int SMEM = (2 * HRP * 64 + 4 * BN * 64) * (int)sizeof(f16);
     static unsigned long long seen = 0;
-    LB_ONCE_PER_DEVICE(seen)                  // (first call on a device happens at record time, outside any capture)
+    // (a recording does not come here: the first call on a device happens at the first replay - inside the stream capture of
+    //  lb_program_instantiate when a program is instantiated before any eager run)
+    LB_ONCE_PER_DEVICE(seen)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
     long nblk, grid;
-    halo_grid(p, TW, KS, nblk, grid);
-    LB_REQUIRE(nblk < (1l << 30), "halo conv: too many tiles for one launch");
+    halo_grid(p, TW, KS, nblk, grid);          // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
     LbGemmParams pk = p;
 #ifdef LB_STUDY_BUILD
     pk.reserved_ = g_halo_study;
@@ -459,9 +460,22 @@ int lb_upconv_halo_eligible(const LbGemmParams& p) {
     return 0;
 }
 
-int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream) {
+// What a halo launch refuses, checked by every entry point (the two launchers here, the router in lb_gemm_f16) BEFORE it
+// dispatches: a recording refuses what a direct call refuses, at the call that caused it.  The launch functions trust their caller.
+static int halo_tiles_check(const LbGemmParams& p, int tw, int ks) {
+    long items, grid;
+    halo_grid(p, tw, ks, items, grid);
+    LB_REQUIRE(items < (1l << 30), "halo conv: too many tiles for one launch");
+    return 0;
+}
+
+int lb_upconv_halo_check(const LbGemmParams& p) {
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || (p.ch_stats != nullptr && p.ch_stats_rows == lb_conv_halo_stat_rows_total(p)),
                "halo upconv: LB_GEMM_CH_STATS needs ch_stats with ch_stats_rows = B * lb_gemm_ch_stat_rows()");
+    return halo_tiles_check(p, lb_upconv_halo_eligible(p), 2);
+}
+
+int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
     return lb_upconv_halo_eligible(p) == 32 ? launch_halo<128, 32, 2>(p, stream) : launch_halo<128, 16, 2>(p, stream);
@@ -476,6 +490,7 @@ extern "C" int lb_upconv2x_halo_f16(const LbGemmParams* pp, void* stream) {
     LB_REQUIRE(lb_upconv_halo_eligible(p) != 0,
                "lb_upconv2x_halo_f16: needs scatter = 2, KH = KW = 2, stride 1, Cin % 64 == 0, W % 16 == 0, zero page, no residual");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && p.ldc % 4 == 0, "lb_upconv2x_halo_f16: ldw / ldx multiples of 8, ldc multiple of 4");
+    if (const int rc = lb_upconv_halo_check(p)) return rc;
     LB_DISPATCH("lb_upconv2x_halo_f16", lb_upconv_halo_launch(p, s));
 }
 
@@ -496,11 +511,15 @@ long lb_conv3x3_halo_blocks(const LbGemmParams& p) {
     return tiles * ((p.N + 127) / 128);
 }
 
-int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
+int lb_conv3x3_halo_check(const LbGemmParams& p) {
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || (p.ch_stats != nullptr && !(p.flags & LB_GEMM_TRANS_OUT)),
                "halo conv: LB_GEMM_CH_STATS needs ch_stats and a row-major output");
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || p.ch_stats_rows == lb_conv_halo_stat_rows_total(p),
                "halo conv: ch_stats_rows must be B * lb_gemm_ch_stat_rows() (the row blocks this launch writes per channel)");
+    return halo_tiles_check(p, lb_conv3x3_halo_eligible(p), 3);
+}
+
+int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
     return lb_conv3x3_halo_eligible(p) == 32 ? launch_halo<128, 32>(p, stream) : launch_halo<128, 16>(p, stream);
@@ -514,6 +533,7 @@ extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
                "lb_conv3x3_halo_f16: needs a 3x3 / stride 1 / pad 1 conv, Cin % 64 == 0, W % 16 == 0, zero page");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && (p.ldc % 4 == 0 || (p.flags & LB_GEMM_TRANS_OUT)),
                "lb_conv3x3_halo_f16: ldw / ldx multiples of 8, ldc multiple of 4");
+    if (const int rc = lb_conv3x3_halo_check(p)) return rc;
     LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
 }
 

@@ -130,10 +130,19 @@ int lb_conv3x3_narrow_eligible(const LbGemmParams& p) {
     return 1;
 }
 
-int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream) {
+static long narrow_tiles(const LbGemmParams& p) {
+    return (long)(p.M / (p.Hin * p.Win)) * (p.Hin / NARROW_T) * (p.Win / NARROW_T);
+}
+
+// What a launch refuses, checked by every entry point BEFORE it dispatches: a recording refuses what a direct call refuses.
+int lb_conv3x3_narrow_check(const LbGemmParams& p) {
+    LB_REQUIRE(narrow_tiles(p) < (1l << 31), "conv3x3 narrow: too many tiles for one launch");
+    return 0;
+}
+
+int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream) {     // (trusts its caller: lb_conv3x3_narrow_check passed)
     if (p.alpha == 0.f) p.alpha = 1.f;
-    const long tiles = (long)(p.M / (p.Hin * p.Win)) * (p.Hin / NARROW_T) * (p.Win / NARROW_T);
-    LB_REQUIRE(tiles < (1l << 31), "conv3x3 narrow: too many tiles for one launch");
+    const long tiles = narrow_tiles(p);
     hipLaunchKernelGGL(conv3x3_narrow_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
     return lb_check_launch("lb_conv3x3_narrow_f16");
 }
@@ -144,5 +153,6 @@ extern "C" int lb_conv3x3_narrow_f16(const LbGemmParams* pp, void* stream) {
     LB_REQUIRE(lb_conv3x3_narrow_eligible(p) != 0,
                "lb_conv3x3_narrow_f16: needs a 3x3 / stride 1 / pad 1 conv, N <= 16, Cin % 64 == 0, H and W multiples of 16, bias-only epilogue");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && p.ldc % 4 == 0, "lb_conv3x3_narrow_f16: ldw / ldx multiples of 8, ldc multiple of 4");
+    if (const int rc = lb_conv3x3_narrow_check(p)) return rc;
     LB_DISPATCH("lb_conv3x3_narrow_f16", lb_conv3x3_narrow_launch(p, s));
 }

@@ -340,10 +340,13 @@ static constexpr int g_policy_off = 0;     // (the A/B switches of the tile poli
 // halo grid has at least LB_HALO_MIN_BLOCKS blocks (default), 2 = whenever eligible (tests / A-B studies).
 int lb_conv3x3_halo_eligible(const LbGemmParams& p);
 long lb_conv3x3_halo_blocks(const LbGemmParams& p);
+int lb_conv3x3_halo_check(const LbGemmParams& p);
 int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream);
 int lb_conv3x3_narrow_eligible(const LbGemmParams& p);
+int lb_conv3x3_narrow_check(const LbGemmParams& p);
 int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream);
 int lb_upconv_halo_eligible(const LbGemmParams& p);
+int lb_upconv_halo_check(const LbGemmParams& p);
 int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream);
 #define LB_HALO_MIN_BLOCKS 96
 static int g_halo = 1;
@@ -591,11 +594,17 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     if (p.scatter == 2) {       // all four sub-pixel parities in one launch: only the halo kernel implements it
         LB_REQUIRE(lb_upconv_halo_eligible(p) != 0, "lb_gemm_f16: scatter = 2 needs Cin % 64 == 0, W % 16 == 0, stacked [4][N][K] weights");
+        if (const int rc = lb_upconv_halo_check(p)) return rc;
         LB_DISPATCH("lb_upconv2x_halo_f16", lb_upconv_halo_launch(p, s));
     }
-    if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p))      // N <= 16: conv_out of the VAE / UNet (conv3_narrow.hip)
+    if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p)) {    // N <= 16: conv_out of the VAE / UNet (conv3_narrow.hip)
+        if (const int rc = lb_conv3x3_narrow_check(p)) return rc;
         LB_DISPATCH("lb_conv3x3_narrow_f16", lb_conv3x3_narrow_launch(p, s));
-    if (use_halo(p)) LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
+    }
+    if (use_halo(p)) {
+        if (const int rc = lb_conv3x3_halo_check(p)) return rc;
+        LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
+    }
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS), "lb_gemm_f16: LB_GEMM_CH_STATS is implemented by the halo-tile conv kernels only "
                                               "(check lb_gemm_plan == 6 / lb_conv_halo_plan before asking for it)");
     int tile = 0, splitk = 1;

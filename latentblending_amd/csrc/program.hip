@@ -30,7 +30,16 @@ struct LbProgram {
 
 static thread_local LbProgram* g_recording = nullptr;
 
+static void drop_graph(LbProgram* p) {
+    if (p->exec) { hipGraphExecDestroy(p->exec); p->exec = nullptr; }
+    if (p->graph) { hipGraphDestroy(p->graph); p->graph = nullptr; }
+}
+
 bool lb_recording() { return g_recording != nullptr; }
+
+// 1 while launchers called on this thread are recorded instead of run (host wrappers that allocate device buffers of
+// their own ask before they hand a pointer the caching allocator may reuse to a closure)
+extern "C" int lb_program_recording(void) { return g_recording != nullptr ? 1 : 0; }
 
 void lb_record(const char* name, std::function<int(hipStream_t)> fn) {
     g_recording->ops.push_back(LbOp{std::string(name), std::move(fn)});
@@ -41,8 +50,8 @@ extern "C" void* lb_program_create(void) { return new LbProgram(); }
 extern "C" void lb_program_destroy(void* prog) {
     LbProgram* p = (LbProgram*)prog;
     if (!p) return;
-    if (p->exec) hipGraphExecDestroy(p->exec);
-    if (p->graph) hipGraphDestroy(p->graph);
+    if (g_recording == p) g_recording = nullptr;       // destroying the program that records on this thread ends the recording
+    drop_graph(p);
     if (p->capture_stream) hipStreamDestroy(p->capture_stream);
     delete p;
 }
@@ -50,6 +59,7 @@ extern "C" void lb_program_destroy(void* prog) {
 extern "C" int lb_program_begin_record(void* prog) {
     LB_REQUIRE(prog != nullptr && g_recording == nullptr, "lb_program_begin_record: already recording");
     g_recording = (LbProgram*)prog;
+    drop_graph(g_recording);       // the ops are about to change: lb_program_launch runs them eagerly until the next instantiate
     return 0;
 }
 
@@ -89,8 +99,7 @@ extern "C" int lb_program_instantiate(void* prog) {
         e = hipStreamCreateWithFlags(&p->capture_stream, hipStreamNonBlocking);
         if (e != hipSuccess) { lb_set_error("lb_program_instantiate(stream)", e); return (int)e; }
     }
-    if (p->exec) { hipGraphExecDestroy(p->exec); p->exec = nullptr; }
-    if (p->graph) { hipGraphDestroy(p->graph); p->graph = nullptr; }
+    drop_graph(p);
     e = hipStreamBeginCapture(p->capture_stream, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) { lb_set_error("lb_program_instantiate(begin)", e); return (int)e; }
     int rc = lb_program_run(prog, p->capture_stream);

@@ -120,6 +120,7 @@ SIGNATURES = {
     "lb_program_destroy": (None, [_vp]),
     "lb_program_begin_record": (_i, [_vp]),
     "lb_program_end_record": (_i, [_vp]),
+    "lb_program_recording": (_i, []),
     "lb_program_num_ops": (_i, [_vp]),
     "lb_program_op_name": (C.c_char_p, [_vp, _i]),
     "lb_program_run": (_i, [_vp, _vp]),
@@ -138,7 +139,7 @@ STUDY_SIGNATURES = {
 
 _NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
              "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan", "lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
-             "lb_program_destroy", "lb_program_num_ops", "lb_program_op_name"}
+             "lb_program_destroy", "lb_program_recording", "lb_program_num_ops", "lb_program_op_name"}
 
 
 def _load():

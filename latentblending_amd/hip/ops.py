@@ -23,6 +23,21 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _own_buffer(wrapper: str, what: str) -> None:
+    """A wrapper about to allocate a device buffer it does not return calls this first: while the calling thread records a
+    program the closure would keep a pointer that the caching allocator reuses as soon as the wrapper returns."""
+    if api.lb_program_recording():
+        raise RuntimeError(f"{wrapper}: called while a program is recording without a caller-owned {what}; "
+                           f"pass one in (and keep it alive as long as the program) or call lib.api directly")
+
+
+def _operand(wrapper: str, given: torch.Tensor, used: torch.Tensor) -> torch.Tensor:
+    """``used`` is ``given`` made contiguous / converted: a temporary copy, if one had to be made, is such a buffer too."""
+    if used.data_ptr() != given.data_ptr():
+        _own_buffer(wrapper, "contiguous operand of the kernel's dtype (the wrapper had to copy this one)")
+    return used
+
+
 def _ptr_array(tensors: Sequence[torch.Tensor]):
     arr = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
     return C.cast(arr, lib.c_void_pp), arr
@@ -36,8 +51,8 @@ def slerp_pairs(p0: List[torch.Tensor], p1: List[torch.Tensor], fracts: List[flo
         p0 = [t.float() for t in p0]
         p1 = [t.float() for t in p1]
         dt = F32
-    a = [t.contiguous() for t in p0]
-    b = [t.to(dt).contiguous() for t in p1]
+    a = [_operand("slerp_pairs", t, t.contiguous()) for t in p0]
+    b = [_operand("slerp_pairs", t, t.to(dt).contiguous()) for t in p1]
     n = a[0].numel()
     assert all(t.numel() == n and t.is_cuda for t in a + b), "slerp_pairs: equal-sized device tensors"
     outs = [torch.empty(t.shape, dtype=F16 if dt == F16 else F32, device=t.device) for t in a]
@@ -77,12 +92,12 @@ def slerp_strided(p0: torch.Tensor, p1: torch.Tensor, fracts_dev: torch.Tensor, 
 
 
 def lerp(p0: torch.Tensor, p1: torch.Tensor, fract: float) -> torch.Tensor:
-    a, b = p0.contiguous(), p1.contiguous()
+    a, b = _operand("lerp", p0, p0.contiguous()), _operand("lerp", p1, p1.contiguous())
     if a.dtype == F16 and b.dtype == F16:
         out = torch.empty_like(a)
         api.lb_lerp_f16(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), float(fract), stream_ptr())
         return out
-    a, b = a.float(), b.float()
+    a, b = _operand("lerp", a, a.float()), _operand("lerp", b, b.float())
     out = torch.empty_like(a)
     api.lb_lerp_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), float(fract), stream_ptr())
     return out
@@ -108,7 +123,7 @@ def scale_model_input(x: torch.Tensor, params: torch.Tensor, dup_for_cfg: bool =
 def euler_step(x, eps, params, noise=None, cfg=False, ancestral=False) -> torch.Tensor:
     assert x.is_contiguous() and eps.is_contiguous(), "euler_step: the kernel takes its operands by pointer"
     if noise is not None and not noise.is_contiguous():
-        noise = noise.contiguous()
+        noise = _operand("euler_step", noise, noise.contiguous())
     out = torch.empty_like(x)
     api.lb_euler_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
                           x[0].numel(), x.shape[0], int(cfg), int(ancestral), stream_ptr())
@@ -165,8 +180,10 @@ def subpixel_upsample_weights(w: torch.Tensor, cin_pad: Optional[int] = None):
 
 def gemm(A: torch.Tensor, W: torch.Tensor, bias=None, residual=None, rowvec=None, rows_per_batch=0,
          flags: int = 0, alpha: float = 1.0, out: Optional[torch.Tensor] = None, splitk_ws: bool = True,
-         conv: Optional[dict] = None, M: Optional[int] = None, ln=None, ch_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+         conv: Optional[dict] = None, M: Optional[int] = None, ln=None, ch_stats: Optional[torch.Tensor] = None,
+         workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """C = epilogue(A . W^T).  A: [M, K] fp16 (or NHWC [B,H,W,C] with ``conv``), W: [N, K] fp16.
+    ``workspace``: caller-owned fp32 split-K slabs (>= lb_gemm_workspace_bytes(M, N) bytes) instead of a temporary one.
     ``conv``: dict(KH, KW, stride, pad, ups) for an implicit-GEMM convolution.
     ``ln`` = (colsum [N] fp32, eps): LayerNorm over A's columns folded into the GEMM (see ``fold_layernorm``)."""
     p = LbGemmParams()
@@ -220,7 +237,11 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias=None, residual=None, rowvec=None
         p.ch_stats, p.ch_stats_rows = ch_stats.data_ptr(), ch_stats.shape[1]      # [N][B * rows][2] fp32
     ws = None
     if splitk_ws and not (flags & lib.GEMM_GEGLU) and ln is None:
-        ws = torch.empty(api.lb_gemm_workspace_bytes(Mv, N) // 4, dtype=F32, device=dev)
+        ws = workspace
+        if ws is None:
+            _own_buffer("gemm", "split-K `workspace` (or splitk_ws=False)")
+            ws = torch.empty(api.lb_gemm_workspace_bytes(Mv, N) // 4, dtype=F32, device=dev)
+        assert ws.numel() * ws.element_size() >= api.lb_gemm_workspace_bytes(Mv, N), "gemm: split-K workspace too small"
         p.partial = ws.data_ptr()
     if conv is not None and conv.get("halo"):         # experimental halo-tile 3x3 kernel (csrc/conv3_halo.hip)
         api.lb_conv3x3_halo_f16(C.byref(p), stream_ptr())
@@ -241,17 +262,27 @@ def fold_layernorm(w: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.T
 # ------------------------------------------------------------------------------ norms ------
 def groupnorm_nhwc(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float,
                    silu: bool, ldx: Optional[int] = None, ldy: Optional[int] = None,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x: [B, H, W, C] (or [B, HW, C]) fp16 / fp32 -> fp16.  ``ldx`` / ``ldy``: pixel strides in elements (default C: dense);
-    ``out``: caller-owned fp16 output whose pixels are ``ldy`` apart."""
+    ``out``: caller-owned fp16 output whose pixels are ``ldy`` apart; ``workspace``: caller-owned float64 statistics buffer
+    (lb_groupnorm_workspace_bytes(B, groups) bytes) instead of a temporary one."""
     B, C = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C)
     y = torch.empty(x.shape, dtype=F16, device=x.device) if out is None else out
-    ws = torch.empty(api.lb_groupnorm_workspace_bytes(B, groups) // 8, dtype=F64, device=x.device)
+    ws = _groupnorm_workspace("groupnorm_nhwc", workspace, B, groups, x.device)
     api.lb_groupnorm_nhwc(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ws.data_ptr(),
                           B, HW, C, C if ldx is None else ldx, C if ldy is None else ldy, groups, eps, int(silu),
                           int(x.dtype == F32), stream_ptr())
     return y
+
+
+def _groupnorm_workspace(wrapper: str, workspace: Optional[torch.Tensor], B: int, groups: int, device) -> torch.Tensor:
+    nbytes = api.lb_groupnorm_workspace_bytes(B, groups)
+    if workspace is None:
+        _own_buffer(wrapper, "`workspace`")
+        return torch.empty(nbytes // 8, dtype=F64, device=device)
+    assert workspace.numel() * workspace.element_size() >= nbytes, f"{wrapper}: workspace too small"
+    return workspace
 
 
 def conv_halo_plan(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3):
@@ -280,14 +311,14 @@ def conv_ch_stat_rows(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3) 
 
 def groupnorm_from_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, silu: bool,
                          ch_stats: torch.Tensor, rows_per_sample: int, ldx: Optional[int] = None, ldy: Optional[int] = None,
-                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
     """GroupNorm of x [B, H, W, C] whose (sum, sum of squares) per (64-pixel row block, channel) the producing conv left in
     ``ch_stats`` ([C, B * rows_per_sample, 2] fp32, channel-major, LB_GEMM_CH_STATS).  ``ldx`` / ``ldy`` / ``out`` as in
-    ``groupnorm_nhwc``."""
+    ``groupnorm_nhwc``; ``workspace`` likewise."""
     B, C_ = x.shape[0], x.shape[-1]
     HW = x.numel() // (B * C_)
     y = torch.empty(x.shape, dtype=F16, device=x.device) if out is None else out
-    ws = torch.empty(api.lb_groupnorm_workspace_bytes(B, groups) // 8, dtype=F64, device=x.device)
+    ws = _groupnorm_workspace("groupnorm_from_stats", workspace, B, groups, x.device)
     api.lb_groupnorm_from_stats(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), ch_stats.data_ptr(), ws.data_ptr(),
                                 B, HW, C_, C_ if ldx is None else ldx, C_ if ldy is None else ldy, groups, eps, int(silu),
                                 int(x.dtype == F32), rows_per_sample, stream_ptr())
@@ -373,7 +404,8 @@ def copy_cols(src: torch.Tensor, dst: torch.Tensor, dst_off: int):
 def nchw_to_nhwc(x: torch.Tensor, ld: int, mul: float = 1.0) -> torch.Tensor:
     B, Cc, H, W = x.shape
     y = torch.empty(B, H, W, ld, dtype=F16, device=x.device)
-    api.lb_nchw_to_nhwc_f16(x.contiguous().data_ptr(), y.data_ptr(), B, Cc, H * W, ld, mul, stream_ptr())
+    x = _operand("nchw_to_nhwc", x, x.contiguous())
+    api.lb_nchw_to_nhwc_f16(x.data_ptr(), y.data_ptr(), B, Cc, H * W, ld, mul, stream_ptr())
     return y
 
 
@@ -399,14 +431,21 @@ def maxpool3s2(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def frames_lerp_u8(frames: torch.Tensor, left, weights, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def frames_lerp_u8(frames: torch.Tensor, left, weights, out: Optional[torch.Tensor] = None, tables=None) -> torch.Tensor:
     """frames: [n_key, H, W, 3] uint8 on the device; out[k] = uint8((1 - w[k]) * frames[left[k]] + w[k] * frames[left[k] + 1])
-    in float64 with a truncating cast (reference utils.py:97 as numpy >= 2 evaluates it on the movie's key frames)."""
+    in float64 with a truncating cast (reference utils.py:97 as numpy >= 2 evaluates it on the movie's key frames).
+    ``tables`` = (left int32 [n_out], weights float64 [n_out]) already on the device, caller-owned, instead of an upload of
+    ``left`` / ``weights`` (which then only give the count)."""
     assert frames.dtype == torch.uint8 and frames.is_contiguous()
     n_out = len(left)
     fb = frames[0].numel()
-    left_d = torch.tensor(list(left), dtype=torch.int32, device=frames.device)
-    w_d = torch.tensor(list(weights), dtype=F64, device=frames.device)
+    if tables is None:
+        _own_buffer("frames_lerp_u8", "`tables` (left, weights) on the device")
+        left_d = torch.tensor(list(left), dtype=torch.int32, device=frames.device)
+        w_d = torch.tensor(list(weights), dtype=F64, device=frames.device)
+    else:
+        left_d, w_d = tables
+        assert left_d.dtype == torch.int32 and w_d.dtype == F64 and left_d.numel() >= n_out and w_d.numel() >= n_out
     if out is None:
         out = torch.empty((n_out,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=frames.device)
     for k0 in range(0, n_out, 65535):
@@ -456,6 +495,7 @@ def lpips_tap(feats_a: Sequence[torch.Tensor], feats_b: Sequence[torch.Tensor], 
     hw, c = feats_a[0].shape[-2], feats_a[0].shape[-1]
     assert all(t.dtype == F16 and t.is_contiguous() and t.shape[-2:] == (hw, c) for t in list(feats_a) + list(feats_b))
     if workspace is None:
+        _own_buffer("lpips_tap", "`workspace`")
         workspace = torch.empty(16 * 128, dtype=F32, device=acc.device)
     pa, keep_a = _ptr_array(feats_a)
     pb, keep_b = _ptr_array(feats_b)
@@ -553,6 +593,7 @@ def jpeg_scan_from_coefficients(coef: torch.Tensor, h: int, w: int, subsampling:
     assert coef.dtype == torch.int16 and coef.is_cuda and coef.is_contiguous()
     assert coef.numel() == api.lb_jpeg_coefficient_count(n, h, w, code), "jpeg: coefficient tensor does not match (n, H, W, subsampling)"
     dev = coef.device
+    _own_buffer("jpeg_scan_from_coefficients", "workspace (use jpeg_entropy_into)")
     workspace = torch.empty(api.lb_jpeg_workspace_bytes(n, h, w, code), dtype=torch.uint8, device=dev)
     frame_bytes = torch.empty(n, dtype=torch.int32, device=dev)
     capacity = n * (h * w + 4096)                  # ~3x what quality 92 needs on noisy frames; the true sizes come back either way
@@ -639,6 +680,8 @@ def resample_u8(frames: torch.Tensor, size_hw, filter: str = "bicubic", out: Opt
     assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (n, hout, wout, 3) and out.device == dev
     tx, ty = _resample_tables(hin, win, hout, wout, filter, dev)
     chunk = min(n, 65535)
+    if tx is not None and ty is not None:
+        _own_buffer("resample_u8", "`tmp` (use resample_u8_into)")
     tmp = torch.empty((chunk, hin, wout, 3), dtype=torch.uint8, device=dev) if tx is not None and ty is not None else None
     for k0 in range(0, n, 65535):
         k1 = min(n, k0 + 65535)

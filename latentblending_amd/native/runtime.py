@@ -84,6 +84,7 @@ class Program:
     @contextlib.contextmanager
     def record(self):
         api.lb_program_begin_record(self.handle)
+        self.graph_ready = False           # (the library dropped the graph: launch() is eager until the next instantiate())
         try:
             yield self
         finally:
