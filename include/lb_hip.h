@@ -62,6 +62,14 @@ int lb_lerp_f32(const void* p0, const void* p1, void* out, long n, double fract,
 /* params_dev: float[batch][8] = {sigma_from, sigma_next, sigma_up, guidance, dt, -, -, -} */
 int lb_scale_model_input_f16(const void* x, void* out, const float* params_dev, long per_sample,
                              int batch, int dup_for_cfg, void* stream);
+/* `ancestral` is a MODE: 0 = Euler, 1 = Euler-ancestral (`noise` required), 2 = latent-consistency (LCM) step; anything else is
+ * refused.  Mode 2 (diffusers 0.25.0 LCMScheduler.step, epsilon prediction; fp16 tensor arithmetic rounded op by op, like DDIM):
+ *   params_dev: float[batch][8] = {0, c_skip, sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev),
+ *                                  1 / sqrt(abar_t), c_out}
+ *   x0 = (x - sqrt(1 - abar_t) eps) / sqrt(abar_t);  den = c_out x0 + c_skip x;  out = sqrt(abar_prev) den + sqrt(1 - abar_prev) noise.
+ *   A row with slot 5 == 0 is the LAST step of its schedule: out = den bit for bit and `noise` is not read for it.
+ *   `cfg`: bit 0 = CFG as in the other modes; bit 1 = the host's statement that EVERY row is such a last step - only then
+ *   may `noise` be null (a null `noise` without bit 1 is refused; the rows are never read back from the device). */
 int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
                       const float* params_dev, long per_sample, int batch, int cfg, int ancestral,
                       void* stream);

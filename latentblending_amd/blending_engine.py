@@ -384,7 +384,7 @@ class BlendingEngine:
     def _farm_shared_noise(self):
         """Ancestral noise as ONE stream on every rank (see ``_farm_begin``); returns the restore callable or None."""
         sched = getattr(self.dh.pipe, "scheduler", None)
-        if _is_native(self.dh.pipe) and getattr(sched, "ancestral", False) and sched.noise_source is None:
+        if _is_native(self.dh.pipe) and self._draws_noise(sched) and sched.noise_source is None:
             from .native.scheduler import SeededDeviceNoise
             seed = int(self.farm.broadcast_floats([float(np.random.randint(0, 2 ** 31 - 1))], src=0)[0])
             sched.noise_source = SeededDeviceNoise(seed, self.dh.pipe.device)
@@ -465,7 +465,7 @@ class BlendingEngine:
         self.dh.set_num_inference_steps(steps)
         pipe = self.dh.pipe
         farm = self.farm if self._farm_on() else None
-        ancestral = bool(getattr(getattr(pipe, "scheduler", None), "ancestral", False))
+        ancestral = self._draws_noise(getattr(pipe, "scheduler", None))      # (any sampler that draws per-step noise)
         restore_noise = self._farm_shared_noise() if farm else None
         try:
             mine = [k for k in range(n) if farm is None or farm.owner_of(k) == farm.rank]
@@ -487,13 +487,13 @@ class BlendingEngine:
                         for k, t in zip(part, got):
                             trajs[k] = t
                 elif ancestral:          # fewer key frames than ranks: a rank without one still advances a shared noise stream
-                    self._skip_noise_draws(n * steps)
+                    self._skip_noise_draws(n * self._run_noise_draws(0))
             else:
                 for k in range(n):                       # (generic pipes: one trajectory at a time, in chain order)
                     if k in mine:
                         trajs[k] = self.run_diffusion([embeddings[k]], latents_start=self.get_noise(int(seeds[k])), idx_start=0)
                     elif ancestral:
-                        self._skip_noise_draws(steps)
+                        self._skip_noise_draws(self._run_noise_draws(0))
             if farm:
                 shape = (1,) + self._latent_chw()
                 for k in range(n):
@@ -841,8 +841,8 @@ class BlendingEngine:
         chosen = list(range(len(specs))) if only is None else list(only)
         if _is_native(pipe):
             if not chosen:
-                if getattr(pipe.scheduler, "ancestral", False):
-                    self._skip_noise_draws(len(specs) * (self.num_inference_steps - idx_injection))
+                if self._draws_noise(pipe.scheduler):
+                    self._skip_noise_draws(len(specs) * self._run_noise_draws(idx_injection))
                 return []
             sel = [specs[k] for k in chosen]
             trajs = pipe.native_run_diffusion_batch(
@@ -856,7 +856,7 @@ class BlendingEngine:
         out = []
         for k, s in enumerate(specs):
             if k not in chosen:
-                self._skip_noise_draws(self.num_inference_steps - idx_injection)
+                self._skip_noise_draws(self._run_noise_draws(idx_injection))
                 continue
             self.guidance_scale = self.dh.guidance_scale = s["guidance"]
             traj = self.run_diffusion([s["cond"]], latents_start=s["mixed"][idx_injection - 1], idx_start=idx_injection,
@@ -889,13 +889,13 @@ class BlendingEngine:
         farm, steps = self.farm, self.num_inference_steps
         independent = self.branch1_crossfeed_power == 0.0
         shape = (1,) + self._latent_chw()
-        ancestral = bool(getattr(getattr(self.dh.pipe, "scheduler", None), "ancestral", False))
+        ancestral = self._draws_noise(getattr(self.dh.pipe, "scheduler", None))
         first = self.tree_latents[0] if keep1 else None
         if not keep1:
             if farm.rank == 0:
                 first = self.compute_latents1()
             elif ancestral:
-                self._skip_noise_draws(steps)
+                self._skip_noise_draws(self._run_noise_draws(0))
             first = self._on_pipe_device(farm.share_trajectory(first if farm.rank == 0 else None, 0, steps, shape))
             self.tree_latents[0] = first
         last = self.tree_latents[-1] if keep2 else None
@@ -904,15 +904,29 @@ class BlendingEngine:
             if farm.rank == owner2:
                 last = self.compute_latents2()
             elif ancestral:
-                self._skip_noise_draws(steps)
+                self._skip_noise_draws(self._run_noise_draws(0))
             last = self._on_pipe_device(farm.share_trajectory(last if farm.rank == owner2 else None, owner2, steps, shape))
         self.tree_latents[0], self.tree_latents[-1] = first, last
         return first, last
 
+    @staticmethod
+    def _draws_noise(sched) -> bool:
+        """Does this sampler consume per-step noise?  Euler-ancestral does; so does the latent-consistency sampler (``draws_noise``)."""
+        return bool(getattr(sched, "ancestral", False) or getattr(sched, "draws_noise", False))
+
+    def _run_noise_draws(self, idx_start: int) -> int:
+        """Latent-shaped draws ONE denoising run from ``idx_start`` consumes: one per step for an ancestral sampler, one per step
+        but the schedule's last for the latent-consistency sampler (the scheduler's own ``noise_draws`` says so)."""
+        sched, steps = getattr(self.dh.pipe, "scheduler", None), self.num_inference_steps
+        own = getattr(sched, "noise_draws", None)
+        if own is not None:
+            return int(own(steps, idx_start))
+        return max(0, steps - int(idx_start)) if getattr(sched, "ancestral", False) else 0
+
     def _skip_noise_draws(self, n):
         sched = getattr(self.dh.pipe, "scheduler", None)
         src = getattr(sched, "noise_source", None)
-        if src is not None and getattr(sched, "ancestral", False) and n > 0:
+        if src is not None and self._draws_noise(sched) and n > 0:
             shape = (1, self.dh.pipe.unet.config.in_channels, self.dh.height_latent, self.dh.width_latent)
             if hasattr(src, "many"):        # the ranks that DO draw make one generator call for these n latents (native pipe,
                 src.many(n, shape)          # scheduler.draw_noise_many): the same call keeps a shared device stream aligned

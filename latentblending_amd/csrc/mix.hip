@@ -1,5 +1,5 @@
 // Latent-mixing primitives for gfx950: whole-tensor slerp (float64 reductions), conditioning
-// lerp, scheduler input scaling, CFG combine + Euler / Euler-ancestral update.
+// lerp, scheduler input scaling, CFG combine + Euler / Euler-ancestral / DDIM / latent-consistency update.
 // All are HBM/L2-bound elementwise kernels: 16 B per lane, coalesced, wave-shuffle reductions.
 //
 // Reference behaviour (paths relative to /root/reference):
@@ -538,17 +538,6 @@ static void euler_launch(const void* x, const void* eps, const void* noise, void
 #undef LB_EULER
 }
 
-extern "C" int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
-                                 const float* params_dev, long per_sample, int batch, int cfg,
-                                 int ancestral, void* stream) {
-    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_euler_step_f16: sizes");
-    LB_REQUIRE(!ancestral || noise != nullptr, "lb_euler_step_f16: ancestral step needs noise");
-    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out) && (!ancestral || aligned16(noise));
-    LB_DISPATCH_STMT("lb_euler_step_f16",
-                     if (vec) euler_launch<true>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s);
-                     else euler_launch<false>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s));
-}
-
 // ------------------------------------------------------------------------------------------------
 // DDIM step (eta = 0, epsilon prediction; diffusers DDIMScheduler.step as SD / SDXL configure it: clip_sample = False,
 // set_alpha_to_one = False, leading spacing with steps_offset = 1).  Third party, reached from
@@ -628,3 +617,101 @@ extern "C" int lb_ddim_step_f16(const void* x, const void* eps, void* out, const
 #undef LB_DDIM
 }
 
+// ------------------------------------------------------------------------------------------------
+// Latent-consistency step (Luo et al. 2023, multistep consistency sampling; diffusers 0.25.0 LCMScheduler.step as LCM-SDXL
+// configures it: epsilon prediction, timestep_scaling 10, sigma_data 0.5, no clipping / thresholding).  Mode 2 of
+// lb_euler_step_f16 (a dedicated symbol follows when the replay registry is next opened).
+//   params row: {0 (sigma of lb_scale_model_input_f16: the identity, as for DDIM), c_skip, sqrt(abar_prev), guidance,
+//                sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t) [fp32], c_out}
+// Like DDIM, diffusers does not upcast: fp16 tensors, 0-dim fp32 / Python-float coefficients, so EVERY tensor operation
+// rounds to fp16 (CFG combine first, as in euler_one / ddim_one) -
+//   x0   = (sample - sqrt(1 - abar_t) * eps) / sqrt(abar_t)        [mul, sub, multiply by the reciprocal formed once: three]
+//   den  = c_out * x0 + c_skip * sample                            [mul, mul, add: three]
+//   prev = sqrt(abar_prev) * den + sqrt(1 - abar_prev) * noise     [mul, mul, add: three]
+// The LAST step of a schedule has no previous timestep: its row carries slot 5 == 0 and the result is `den` bit for bit
+// (-0 included: nothing is added to it); the noise is not read for such a row, nor when the pointer is null.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ f16 lcm_one(f16 xh, f16 eu, f16 et, f16 nz, float c_skip, float c_out, float inv_sa_t, float sa_p,
+                                       float sb_t, float sb_p, float g, bool cfg, bool last) {
+    f16 e = eu;
+    if (cfg) {
+        const f16 diff = (f16)((float)et - (float)eu);
+        const f16 sc = (f16)(g * (float)diff);
+        e = (f16)((float)eu + (float)sc);
+    }
+    // (the opaque register of ddim_one: no v_fma_mix fusion of "multiply, then round")
+    auto r16 = [](float v) {
+        asm volatile("" : "+v"(v));
+        return (f16)v;
+    };
+    const f16 t1 = r16(__fmul_rn(sb_t, (float)e));
+    const f16 t2 = r16(__fsub_rn((float)xh, (float)t1));
+    const f16 x0 = r16(__fmul_rn((float)t2, inv_sa_t));
+    const f16 d1 = r16(__fmul_rn(c_out, (float)x0));
+    const f16 d2 = r16(__fmul_rn(c_skip, (float)xh));
+    const f16 den = r16(__fadd_rn((float)d1, (float)d2));
+    if (last) return den;
+    const f16 a = r16(__fmul_rn(sa_p, (float)den));
+    const f16 b = r16(__fmul_rn(sb_p, (float)nz));
+    return r16(__fadd_rn((float)a, (float)b));
+}
+
+template <bool VEC, bool CFG>
+__global__ void __launch_bounds__(256) lcm_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps,
+                                                        const f16* __restrict__ noise, f16* __restrict__ out,
+                                                        const float* __restrict__ params, long per_sample, int batch) {
+    const long total = per_sample * batch;
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const float* row = params + (long)b * LB_STEP_STRIDE;
+        const float c_skip = row[1], sa_p = row[2], g = row[3], sb_t = row[4], sb_p = row[5], inv_sa_t = row[6], c_out = row[7];
+        const bool last = sb_p == 0.f || noise == nullptr;        // (uniform over the block: blockIdx.y is the sample)
+        const long base = (long)b * per_sample;
+        const long nvec = VEC ? per_sample >> 3 : 0;
+        const long stride = (long)gridDim.x * blockDim.x;
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+            const long o = base + i * 8;
+            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
+            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
+            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
+            const f16x8 nz = last ? zero8 : *reinterpret_cast<const f16x8*>(noise + o);
+            f16x8 r;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) r[j] = lcm_one(xv[j], eu[j], et[j], nz[j], c_skip, c_out, inv_sa_t, sa_p, sb_t, sb_p, g, CFG, last);
+            *reinterpret_cast<f16x8*>(out + o) = r;
+        }
+        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
+            const long o = base + i;
+            out[o] = lcm_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, last ? (f16)0.f : noise[o], c_skip, c_out, inv_sa_t, sa_p,
+                             sb_t, sb_p, g, CFG, last);
+        }
+    }
+}
+
+// `ancestral` is a MODE: 0 = Euler, 1 = Euler-ancestral (needs noise), 2 = latent-consistency step (params rows as above).
+// Mode 2 only: bit 1 of `cfg` is the host's statement that EVERY row is a last step (slot 5 == 0) - only then may `noise` be
+// null.  Bit 0 of `cfg` is the CFG flag in every mode.
+extern "C" int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
+                                 const float* params_dev, long per_sample, int batch, int cfg,
+                                 int ancestral, void* stream) {
+    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_euler_step_f16: sizes");
+    LB_REQUIRE(ancestral >= 0 && ancestral <= 2, "lb_euler_step_f16: mode (0 Euler, 1 Euler-ancestral, 2 LCM)");
+    LB_REQUIRE(ancestral != 1 || noise != nullptr, "lb_euler_step_f16: ancestral step needs noise");
+    if (ancestral == 2) {
+        LB_REQUIRE((cfg & ~3) == 0, "lb_euler_step_f16: cfg bits (LCM mode: bit 0 CFG, bit 1 every row is a last step)");
+        LB_REQUIRE((cfg & 2) || noise != nullptr, "lb_euler_step_f16: LCM step with a row that is not a last step needs noise");
+        const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out) && (noise == nullptr || aligned16(noise));
+        const int c = cfg & 1;
+        const dim3 grid = sample_grid(per_sample, batch), block(256);
+#define LB_LCM(V, C) hipLaunchKernelGGL((lcm_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (const f16*)noise, \
+                                        (f16*)out, params_dev, per_sample, batch)
+        LB_DISPATCH_STMT("lb_euler_step_f16",
+                         if (vec && c) LB_LCM(true, true); else if (vec) LB_LCM(true, false);
+                         else if (c) LB_LCM(false, true); else LB_LCM(false, false));
+#undef LB_LCM
+    }
+    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out) && (!ancestral || aligned16(noise));
+    LB_DISPATCH_STMT("lb_euler_step_f16",
+                     if (vec) euler_launch<true>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s);
+                     else euler_launch<false>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s));
+}

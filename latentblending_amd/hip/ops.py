@@ -109,7 +109,9 @@ def step_params(rows: Sequence[Sequence[float]], device) -> torch.Tensor:
     # (ONE host tensor from nested lists - a cfg-2 wavefront uploads 34 + 8 rows: the per-row tensor constructions of rounds 1-5 cost
     #  ~0.1 ms of host time in front of a transition's first launch)
     t = torch.tensor([[float(v) for v in r] + [0.0] * (8 - len(r)) for r in rows], dtype=F32).reshape(len(rows), 8)
-    return t.to(device)
+    dev = t.to(device)
+    dev._lb_host_rows = t           # host mirror (lcm_step decides from it whether a null noise pointer is legal; views lose it)
+    return dev
 
 
 def scale_model_input(x: torch.Tensor, params: torch.Tensor, dup_for_cfg: bool = False) -> torch.Tensor:
@@ -127,6 +129,38 @@ def euler_step(x, eps, params, noise=None, cfg=False, ancestral=False) -> torch.
     out = torch.empty_like(x)
     api.lb_euler_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
                           x[0].numel(), x.shape[0], int(cfg), int(ancestral), stream_ptr())
+    return out
+
+
+EULER_MODE_EULER, EULER_MODE_ANCESTRAL, EULER_MODE_LCM = 0, 1, 2      # ``ancestral`` argument of lb_euler_step_f16
+LCM_CFG_ALL_LAST = 2                                                  # bit 1 of its ``cfg`` argument (mode 2 only)
+
+
+def lcm_step(x, eps, params, noise=None, cfg=False, all_last: Optional[bool] = None) -> torch.Tensor:
+    """Latent-consistency step (mode 2 of ``lb_euler_step_f16``); ``params`` rows as NativeLCMScheduler.step_row builds them.
+    ``noise`` may be None only when EVERY row is a last step of its schedule (slot 5 == 0: the denoised latent is the result
+    and the noise is not read).  That is decided on the host, never by reading the rows back: from the host mirror
+    ``step_params`` leaves on the tensor it returns, or - for a view of such a tensor, which has none - from ``all_last``,
+    the caller's own statement about the rows it built.  A null ``noise`` that neither establishes as legal is refused
+    here, before anything is launched."""
+    assert x.is_contiguous() and eps.is_contiguous(), "lcm_step: the kernel takes its operands by pointer"
+    host = getattr(params, "_lb_host_rows", None)
+    known = None if host is None else bool((host.reshape(-1, 8)[:, 5] == 0).all())
+    if known is not None and all_last is not None and bool(all_last) and not known:
+        raise ValueError("lcm_step: all_last=True, but the host rows hold a step that is not the last of its schedule")
+    flag = known if known is not None else (bool(all_last) if all_last is not None else None)
+    if noise is None and flag is not True:
+        raise ValueError("lcm_step: noise=None needs every row to be a last step (slot 5 == 0)"
+                         + ("; these rows are not" if flag is False else
+                            "; that cannot be established on the host for this params tensor (pass all_last=)"))
+    if noise is not None and not noise.is_contiguous():
+        noise = _operand("lcm_step", noise, noise.contiguous())
+    if noise is not None:
+        assert noise.shape == x.shape and noise.dtype == F16, "lcm_step: noise must be an fp16 tensor of the latent's shape"
+    out = torch.empty_like(x)
+    api.lb_euler_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
+                          x[0].numel(), x.shape[0], int(bool(cfg)) | (LCM_CFG_ALL_LAST if noise is None else 0),
+                          EULER_MODE_LCM, stream_ptr())
     return out
 
 

@@ -35,7 +35,7 @@ from ..hip import ops
 from ..hip.lib import api
 from .frames import DeviceImage
 from .lpips import NativeLPIPS
-from .scheduler import NativeDDIMScheduler, NativeEulerScheduler
+from .scheduler import NativeDDIMScheduler, NativeEulerScheduler, NativeLCMScheduler, noise_draws_per_run
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
 from .weights import SyntheticProvider
@@ -58,10 +58,15 @@ class _UNetFacade:
     def __call__(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None,
                  cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=False):
         pipe = self._pipe
+        if self.config.time_cond_proj_dim is not None and timestep_cond is None:
+            raise ValueError("NativeSDXLPipe.unet: this UNet is guidance-embedded (time_cond_proj_dim = "
+                             f"{self.config.time_cond_proj_dim}); timestep_cond is required "
+                             "(pipe.get_guidance_scale_embedding(guidance_scale - 1, embedding_dim=time_cond_proj_dim))")
         B, _, L, _ = sample.shape
         prog = pipe.unet_program(B, L)
         prog.set_conditioning(encoder_hidden_states, added_cond_kwargs["text_embeds"],
-                              added_cond_kwargs["time_ids"])
+                              added_cond_kwargs["time_ids"],
+                              timestep_cond=None if timestep_cond is None else timestep_cond.to(sample.device, F16))
         t = torch.as_tensor(timestep, dtype=F32).reshape(-1).expand(B)
         return (prog.forward(sample.to(F16), t.to(sample.device)).clone(),)
 
@@ -107,17 +112,19 @@ class StableDiffusionXLPipeline:
                  scheduler: Optional[str] = None):
         """``scheduler``: None or "euler" = the reference pipes' choice (Euler-ancestral for Turbo, Euler for base); "ddim" = diffusers'
         DDIMScheduler (eta 0) behind the same native loops - also with ``turbo=True`` (the Turbo guidance / branching defaults
-        stay, only the sampler changes: deterministic, "leading" spacing).  Case-insensitive; anything else raises ``ValueError``
+        stay, only the sampler changes: deterministic, "leading" spacing); "lcm" = the latent-consistency sampler (diffusers'
+        LCMScheduler: few-step sampling of a distilled UNet or a merged LCM-LoRA, 1..50 steps, one noise draw per step but the
+        last), with ``turbo=True`` and ``False`` alike.  Case-insensitive; anything else raises ``ValueError``
         (a misspelt "DDIM " or a scheduler object used to fall through to Euler silently).
         ``allow_synthetic``: seeded synthetic stand-ins (UNet / VAE / LPIPS weights when no provider is given,
         prompt embeddings when no ``text_encoder_fn`` is given) are used silently when True (tests, bench: also
         ``LB_ALLOW_SYNTHETIC=1``); otherwise each stand-in announces itself ONCE with a ``UserWarning`` - frames
         rendered from them are noise-like and prompts have no semantic effect."""
         if scheduler is not None and not isinstance(scheduler, str):
-            raise ValueError(f"NativeSDXLPipe: scheduler must be None, 'euler' or 'ddim' (got an object of type {type(scheduler).__name__})")
+            raise ValueError(f"NativeSDXLPipe: scheduler must be None, 'euler', 'ddim' or 'lcm' (got an object of type {type(scheduler).__name__})")
         scheduler = None if scheduler is None else scheduler.strip().lower()
-        if scheduler not in (None, "euler", "ddim"):
-            raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler' or 'ddim')")
+        if scheduler not in (None, "euler", "ddim", "lcm"):
+            raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler', 'ddim' or 'lcm')")
         if not torch.cuda.is_available():
             raise RuntimeError("NativeSDXLPipe needs an MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device(device)
@@ -141,7 +148,10 @@ class StableDiffusionXLPipeline:
         self.vae_native = vae_native or NativeVAEDecoder(self.vae_cfg, vae_provider or SyntheticProvider(seed + 1), self.device)
         self.lpips_metric = NativeLPIPS(lpips_provider or SyntheticProvider(7), self.device)
         # (the reference's SDXL pipes carry Euler / Euler-ancestral schedulers; scheduler="ddim" = diffusers' DDIMScheduler, eta 0)
-        self.scheduler = NativeDDIMScheduler(device=self.device) if scheduler == "ddim" else NativeEulerScheduler(ancestral=turbo, device=self.device)
+        if scheduler == "lcm":          # (diffusers' LCMScheduler: few-step sampling of distilled UNets / merged LCM-LoRAs)
+            self.scheduler = NativeLCMScheduler(device=self.device)
+        else:
+            self.scheduler = NativeDDIMScheduler(device=self.device) if scheduler == "ddim" else NativeEulerScheduler(ancestral=turbo, device=self.device)
         self.unet = _UNetFacade(self)
         self.vae = _VAEFacade(self)
         self.image_processor = _ImageProcessor()
@@ -185,6 +195,37 @@ class StableDiffusionXLPipeline:
 
     def uses_cfg(self, guidance_scale: float) -> bool:
         return float(guidance_scale) > 1 and self.unet.config.time_cond_proj_dim is None
+
+    @staticmethod
+    def get_guidance_scale_embedding(w, embedding_dim: int = 512, dtype=torch.float32) -> torch.Tensor:
+        """The guidance-scale embedding a guidance-distilled UNet takes as ``timestep_cond`` (diffusers'
+        ``get_guidance_scale_embedding``; the reference's latentblending/diffusers_holder.py:303-309): ``w`` = guidance_scale - 1,
+        one value per row -> [len(w), embedding_dim] = [sin(1000 w f) | cos(1000 w f)], f_i = exp(-i ln(10000) / (half - 1)),
+        SIN first; one zero column pads an odd dimension.  fp32 on the host: it is tiny and per branch."""
+        w = torch.as_tensor(w, dtype=torch.float32).reshape(-1).cpu() * 1000.0
+        half = int(embedding_dim) // 2
+        if half < 2:
+            raise ValueError(f"get_guidance_scale_embedding: embedding_dim must be at least 4 (got {embedding_dim})")
+        freq = torch.exp(torch.arange(half, dtype=torch.float32) * -(torch.log(torch.tensor(10000.0)) / (half - 1)))
+        ang = w.to(dtype)[:, None] * freq.to(dtype)[None, :]
+        emb = torch.cat([torch.sin(ang), torch.cos(ang)], dim=1)
+        if int(embedding_dim) % 2 == 1:
+            emb = torch.nn.functional.pad(emb, (0, 1))
+        return emb
+
+    def _timestep_cond(self, guidance_scales: Sequence[float]) -> Optional[torch.Tensor]:
+        """[len(guidance_scales), time_cond_proj_dim] fp16 on the device - each sample's embedding from the guidance IT runs under
+        (mid-dampened guidance differs from branch to branch) - or None for a UNet that takes none."""
+        dim = self.unet_cfg.time_cond_proj_dim
+        if dim is None:
+            return None
+        w = [float(g) - 1.0 for g in guidance_scales]
+        return self.get_guidance_scale_embedding(w, embedding_dim=dim).to(self.device, F16)
+
+    def _step_kwargs(self, i: int, steps: int) -> dict:
+        # (the LCM step may run without noise on the schedule's last step only: the loop says which step this is - the kernel's
+        #  launcher never reads the device rows back)
+        return {"last": i == steps - 1} if self.scheduler.kind == "lcm" else {}
 
     def to(self, *_a, **_k):
         return self
@@ -350,7 +391,7 @@ class StableDiffusionXLPipeline:
         else:
             ctx, pooled = pos_ctx, pos_pool
         time_ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-        prog.set_conditioning(ctx, pooled, time_ids)
+        prog.set_conditioning(ctx, pooled, time_ids, timestep_cond=self._timestep_cond(guidance_scales))
 
         latents = torch.cat([s.to(self.device, F16).reshape(1, -1, L, L) for s in starts]).contiguous()
         trajs: List[List[Optional[torch.Tensor]]] = [[None] * idx_start for _ in range(G)]
@@ -362,10 +403,10 @@ class StableDiffusionXLPipeline:
         # ancestral noise is drawn sample-major (all steps of branch 0, then branch 1, ...): the same
         # order a sequential engine consumes a noise tape in, so batching does not change results
         noise_all = None
-        if sched.ancestral and num_inference_steps > idx_start:
+        nm = noise_draws_per_run(sched, num_inference_steps, idx_start)     # (ancestral: every step; LCM: every step but the last)
+        if nm > 0:
             shape1 = (1,) + tuple(latents.shape[1:])
             n_draw, keep = (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
-            nm = num_inference_steps - idx_start
             drawn = sched.draw_noise_many(n_draw * nm, shape1, self.device).view(n_draw, nm, *shape1[1:])
             noise_all = drawn[keep].transpose(0, 1).contiguous()                             # [steps, G, 4, L, L]
         for i in range(idx_start, num_inference_steps):
@@ -389,8 +430,8 @@ class StableDiffusionXLPipeline:
             prog.prog_step.launch(stream)
             self.stats["unet_forwards"] += 1
             self.stats["unet_samples"] += prog.B
-            noise = noise_all[i - idx_start] if noise_all is not None else None
-            latents = sched.device_step(latents, prog.eps, params, noise=noise, cfg=cfg)
+            noise = noise_all[i - idx_start] if noise_all is not None and i - idx_start < nm else None
+            latents = sched.device_step(latents, prog.eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, num_inference_steps))
             for g in range(G):
                 trajs[g].append(latents[g:g + 1])
         return trajs
@@ -453,7 +494,7 @@ class StableDiffusionXLPipeline:
             neg_pool = torch.cat([c[3] for c in conds]).to(self.device, F16)
             return torch.cat([neg_ctx, pos_ctx]), torch.cat([neg_pool, pos_pool])
 
-        def prepared(conds, side=None, after=None):
+        def prepared(conds, side=None, after=None, guid=None):
             # (the program - arena, workspaces, first-time graph instantiation - is always obtained on the MAIN stream: its
             # allocations then belong to the main stream's allocator pool; only the conditioning launches move to `side`)
             # `conds` may be a callable (evaluated on the stream the conditioning launches run on); `after` = an event of the main
@@ -465,7 +506,7 @@ class StableDiffusionXLPipeline:
                 conds = conds() if callable(conds) else conds
                 ctx, pooled = conditioning(conds)
                 ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-                prog.set_conditioning(ctx, pooled, ids)
+                prog.set_conditioning(ctx, pooled, ids, timestep_cond=self._timestep_cond(guid))
                 return prog, None
             if after is not None:
                 side.wait_event(after)
@@ -475,13 +516,13 @@ class StableDiffusionXLPipeline:
                 conds = conds() if callable(conds) else conds
                 ctx, pooled = conditioning(conds)
                 ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-                prog.set_conditioning(ctx, pooled, ids)     # (copies into program-owned buffers, then the conditioning program: all
+                prog.set_conditioning(ctx, pooled, ids, timestep_cond=self._timestep_cond(guid))     # (copies into program-owned buffers, then the conditioning program: all
                 return prog, side.record_event()            # on `side` - the temporaries above never meet another stream)
 
         # G == 0: a farm rank that owns no mid branch of the round (fewer gaps than ranks) still runs both anchors
         dead = [bool(elide_dead_steps) and G > 0 and i >= idx_injection and i + 1 < steps and
                 all(float(mid_coeffs[g][i + 1]) == 1.0 for g in range(G)) for i in range(steps)]
-        prog_a = prepared(list(anchor_conds))[0] if A and (idx_injection > 0 or G == 0 or any(dead)) else None
+        prog_a = prepared(list(anchor_conds), guid=all_g[:A])[0] if A and (idx_injection > 0 or G == 0 or any(dead)) else None
         # The big batch's conditioning program (every branch's context K | V projection: ~1.1 ms at 17 samples) does not depend
         # on any latent: when small anchor-only steps come first it runs on a SIDE stream beside them (they leave most of the
         # chip idle) and the main stream waits for it only before the first big step.  Different programs own different
@@ -496,9 +537,9 @@ class StableDiffusionXLPipeline:
                 before_first = torch.cuda.Event()
                 before_first.record()                   # everything the mids' conditionings read (the prompt embeddings) is older than this
             else:
-                prog_all, cond_ready = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds), side=self._side_stream)
+                prog_all, cond_ready = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds), side=self._side_stream, guid=all_g)
         else:
-            prog_all = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds))[0] if G else prog_a
+            prog_all = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds), guid=all_g)[0] if G else prog_a
         stream = torch.cuda.current_stream().cuda_stream
         rows_a = [sched.step_row(i, all_g[0]) for i in range(steps)]
         par_a = ops.step_params([r for r in rows_a for _ in range(A)], self.device).view(steps, A, 8) if A else None
@@ -506,13 +547,15 @@ class StableDiffusionXLPipeline:
                                    for s in range(A + G)], self.device).view(-1, A + G, 8) if G else None
         shape1 = (1,) + tuple(ref_start.shape[1:])
         noise_a = noise_m = None
-        if sched.ancestral:       # sample-major draws: anchor 1, anchor 2 (those denoised here), then every mid branch
+        # draws per run: an anchor's (from step 0) and a mid branch's (from idx_injection) - ancestral: one per step; LCM: one per
+        # step but the schedule's last, so both kinds of run have noise at exactly the steps < nd_a
+        nd_a, nm = noise_draws_per_run(sched, steps, 0), noise_draws_per_run(sched, steps, idx_injection)
+        if nd_a > 0:              # sample-major draws: anchor 1, anchor 2 (those denoised here), then every mid branch
             n_draw, keep = (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
-            nm = steps - idx_injection
-            flat = sched.draw_noise_many(A * steps + n_draw * nm, shape1, self.device)      # ONE launch on the device RNG
+            flat = sched.draw_noise_many(A * nd_a + n_draw * nm, shape1, self.device)      # ONE launch on the device RNG
             # (contiguous per step: the step kernels take noise[i] by pointer)
-            noise_a = flat[:A * steps].view(A, steps, *shape1[1:]).transpose(0, 1).contiguous() if A else None          # [steps, A, 4, L, L]
-            noise_m = flat[A * steps:].view(n_draw, nm, *shape1[1:])[keep].transpose(0, 1).contiguous() if G else None   # [nm, G, 4, L, L]
+            noise_a = flat[:A * nd_a].view(A, nd_a, *shape1[1:]).transpose(0, 1).contiguous() if A else None          # [nd_a, A, 4, L, L]
+            noise_m = flat[A * nd_a:].view(n_draw, nm, *shape1[1:])[keep].transpose(0, 1).contiguous() if G and nm else None   # [nm, G, 4, L, L]
         lat_shape = (int(ref_start.shape[-3]), L, L)
         lat_a = torch.cat([s.to(self.device, F16).reshape(1, -1, L, L) for s in anchor_starts]).contiguous() if A else \
             torch.empty((0,) + lat_shape, dtype=F16, device=self.device)
@@ -541,7 +584,7 @@ class StableDiffusionXLPipeline:
                                 traj_m[g].append(None)
                         continue
                     prog, lat, params, n = prog_a, lat_a, par_a[i], A
-                    noise = noise_a[i] if noise_a is not None else None
+                    noise = noise_a[i] if noise_a is not None and i < nd_a else None
                 else:
                     prev1, prev2 = traj_a[0][i - 1].contiguous(), traj_a[1][i - 1].contiguous()
                     mix_prev = ops.slerp_strided(prev1, prev2, fr_dev, n_lat, broadcast0=True, broadcast1=True)   # parental mix of step i-1
@@ -559,7 +602,7 @@ class StableDiffusionXLPipeline:
                         torch.cuda.current_stream().wait_event(cond_ready)
                         cond_ready = None
                     noise = None
-                    if noise_m is not None:
+                    if noise_m is not None and i < nd_a:
                         noise = torch.cat([noise_a[i], noise_m[i - idx_injection]]) if A else noise_m[i - idx_injection]
                 api.lb_scale_model_input_f16(lat.data_ptr(), prog.x_in.data_ptr(), params.data_ptr(), per_sample, n,
                                              int(cfg), stream)
@@ -567,10 +610,10 @@ class StableDiffusionXLPipeline:
                 prog.prog_step.launch(stream)
                 self.stats["unet_forwards"] += 1
                 self.stats["unet_samples"] += prog.B
-                out = sched.device_step(lat, prog.eps, params, noise=noise, cfg=cfg)
+                out = sched.device_step(lat, prog.eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, steps))
                 if deferred:            # the first small step is launched: now the host work the big batch needs (runs beside it)
                     deferred = False
-                    prog_all, cond_ready = prepared(lambda: list(anchor_conds) + list(mid_conds()), side=self._side_stream, after=before_first)
+                    prog_all, cond_ready = prepared(lambda: list(anchor_conds) + list(mid_conds()), side=self._side_stream, after=before_first, guid=all_g)
                 lat_a = out[:A]
                 for j, k in enumerate(live):
                     traj_a[k].append(out[j:j + 1])

@@ -1,7 +1,9 @@
 """Host side of the Euler / Euler-ancestral schedulers (diffusers 0.25 semantics for SDXL base
 and SDXL-Turbo).  Only the sigma / timestep tables and per-step scalar
 coefficients live here (float64 numpy); the tensor work — ``x / sqrt(sigma^2+1)``, CFG combine
-and the update — runs in ``lb_scale_model_input_f16`` / ``lb_euler_step_f16``.
+and the update — runs in ``lb_scale_model_input_f16`` / ``lb_euler_step_f16``.  ``NativeDDIMScheduler`` and
+``NativeLCMScheduler`` (few-step sampling: diffusers' ``LCMScheduler``) keep the same interface over an fp32 abar table;
+their tensor work is ``lb_ddim_step_f16`` and mode 2 of ``lb_euler_step_f16``.
 
 Reference call sites: /root/reference/latentblending/diffusers_holder.py:42,53,247 (set_timesteps),
 :301 (order), :330 (scale_model_input), :356 (step).  Known answers: tests/golden/scheduler.json.
@@ -207,5 +209,111 @@ class NativeDDIMScheduler:
         i = self._locate(timestep)
         params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
         out = ops.ddim_step(sample.contiguous(), model_output.contiguous(), params)
+        self._step_index += 1
+        return (out,)
+
+
+LCM_ORIGINAL_STEPS = 50          # diffusers 0.25.0 LCMScheduler: original_inference_steps
+LCM_TIMESTEP_SCALING = 10.0      # timestep_scaling
+LCM_SIGMA_DATA = 0.5
+
+
+def lcm_boundary_scalings(t: int) -> Tuple[float, float]:
+    """(c_skip, c_out) of the consistency parameterisation at timestep ``t``, in Python floats as diffusers'
+    ``get_scalings_for_boundary_condition_discrete`` forms them: s = 10 t, c_skip = 0.25 / (s^2 + 0.25), c_out = s / sqrt(s^2 + 0.25)."""
+    s = t * LCM_TIMESTEP_SCALING
+    sd2 = LCM_SIGMA_DATA ** 2
+    return sd2 / (s ** 2 + sd2), s / (s ** 2 + sd2) ** 0.5
+
+
+def noise_draws_per_run(sched, steps: int, idx_start: int) -> int:
+    """Latent-shaped noise draws one denoising run from ``idx_start`` consumes under ``sched``: a scheduler that knows says so
+    itself (``noise_draws``: LCM draws at every step but the schedule's last); an ancestral one draws once per step; others none."""
+    own = getattr(sched, "noise_draws", None)
+    if own is not None:
+        return int(own(steps, idx_start))
+    return max(0, int(steps) - int(idx_start)) if getattr(sched, "ancestral", False) else 0
+
+
+class NativeLCMScheduler:
+    """Latent-consistency multistep sampler (Luo et al. 2023, "Latent Consistency Models", algorithm 3) as diffusers 0.25.0's
+    ``LCMScheduler`` configures it for SDXL: scaled-linear betas, original_inference_steps = 50, timestep_scaling = 10,
+    sigma_data = 0.5, epsilon prediction, no thresholding / clipping.  Restated from the published algorithm and that class's
+    documented behaviour - not checked against diffusers itself.  Host side = the fp32 abar table (as the DDIM class builds it),
+    the timestep selection and the per-step coefficients; the tensor work is mode 2 of ``lb_euler_step_f16``.  Same interface as
+    :class:`NativeDDIMScheduler`; ``scale_model_input`` is the identity and ``init_noise_sigma`` is 1.  Every step but the LAST
+    of the schedule re-noises the denoised latent with one fresh fp16 draw (``noise_draws``)."""
+    order = 1
+    kind = "lcm"
+    ancestral = False            # (not the Euler-ancestral update; whether noise is drawn is ``draws_noise`` / ``noise_draws``)
+    draws_noise = True
+    init_noise_sigma = 1.0
+
+    def __init__(self, device="cuda"):
+        self.device = device
+        betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, NUM_TRAIN_TIMESTEPS, dtype=torch.float32) ** 2
+        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)            # fp32, as diffusers holds it
+        self.noise_source = None
+        self._step_index = None
+        self.set_timesteps(4)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n = int(num_inference_steps)
+        if n < 1 or n > LCM_ORIGINAL_STEPS:
+            raise ValueError(f"NativeLCMScheduler: num_inference_steps must be in 1..{LCM_ORIGINAL_STEPS} (got {n})")
+        origin = np.arange(1, LCM_ORIGINAL_STEPS + 1) * (NUM_TRAIN_TIMESTEPS // LCM_ORIGINAL_STEPS) - 1
+        skip = LCM_ORIGINAL_STEPS // n
+        ts = origin[::-1][::skip][:n].copy().astype(np.int64)
+        self.timesteps_np = ts.astype(np.float32)
+        self.timesteps = torch.from_numpy(self.timesteps_np)
+        self.num_inference_steps = n
+        self._step_index = None
+
+    def index_of(self, t) -> int:
+        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
+
+    def noise_draws(self, steps: int, idx_start: int) -> int:
+        return max(0, int(steps) - int(idx_start) - 1)
+
+    def is_last(self, i: int) -> bool:
+        return i == self.num_inference_steps - 1
+
+    def step_row(self, i: int, guidance: float = 0.0):
+        """(0, c_skip, sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t), c_out): the boundary
+        scalings in Python floats, the roots and the reciprocal in 0-dim fp32 tensor arithmetic (as ``NativeDDIMScheduler.step_row``
+        forms its own).  The last step of the schedule has no previous timestep: its slots 2 and 5 are 0, which is how the kernel
+        knows to return the denoised latent itself and to leave the noise unread."""
+        t = int(self.timesteps_np[i])
+        a_t = self.alphas_cumprod[t]
+        inv = torch.ones((), dtype=torch.float32) / (a_t ** 0.5).to(torch.float32)
+        c_skip, c_out = lcm_boundary_scalings(t)
+        if self.is_last(i):
+            sa_p = sb_p = 0.0
+        else:
+            a_p = self.alphas_cumprod[int(self.timesteps_np[i + 1])]
+            sa_p, sb_p = float(a_p ** 0.5), float((1 - a_p) ** 0.5)
+        return (0.0, c_skip, sa_p, guidance, float((1 - a_t) ** 0.5), sb_p, float(inv), c_out)
+
+    def _locate(self, t) -> int:
+        if self._step_index is None:
+            self._step_index = self.index_of(float(t))
+        return self._step_index
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    draw_noise = NativeEulerScheduler.draw_noise
+    draw_noise_many = NativeEulerScheduler.draw_noise_many
+
+    def device_step(self, latents, eps, params, noise=None, cfg=False, last: Optional[bool] = None):
+        """``last``: the loop's statement that this is the schedule's last step for every sample of the batch (``params`` is
+        usually a view of one upload of all steps' rows, which carries no host mirror) - only then may ``noise`` be None."""
+        return ops.lcm_step(latents, eps, params, noise=noise, cfg=cfg, all_last=last)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
+        i = self._locate(timestep)
+        params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
+        noise = None if self.is_last(i) else self.draw_noise(sample.shape, sample.device)
+        out = ops.lcm_step(sample.contiguous(), model_output.contiguous(), params, noise=noise)
         self._step_index += 1
         return (out,)

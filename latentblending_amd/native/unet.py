@@ -211,6 +211,12 @@ class NativeUNet:
         temb_acc = {"w": [], "b": [], "n": 0}
         ctx_acc = {"k": [], "v": [], "n": 0}
         self._conv(pv, "conv_in", cfg.in_channels, ch[0], 3)
+        if cfg.time_cond_proj_dim is not None:
+            # guidance-distilled UNets (LCM-SDXL and its kin): the guidance-scale embedding is projected onto the timestep
+            # sinusoid in front of linear_1 (diffusers TimestepEmbedding.cond_proj: Linear(time_cond_proj_dim, C0, bias=False))
+            if cfg.time_cond_proj_dim <= 0 or cfg.time_cond_proj_dim % 8:
+                raise ValueError(f"UNetConfig.time_cond_proj_dim must be a positive multiple of 8 (got {cfg.time_cond_proj_dim})")
+            self._linear(pv, "time_embedding.cond_proj", cfg.time_cond_proj_dim, ch[0], bias=False)
         self._linear(pv, "time_embedding.linear_1", ch[0], T)
         self._linear(pv, "time_embedding.linear_2", T, T)
         self._linear(pv, "add_embedding.linear_1", cfg.add_in_dim, T)
@@ -273,6 +279,8 @@ class UNetProgram:
         self.ctx = torch.zeros(B, CTX_PAD, cfg.cross_dim, dtype=F16, device=dev)     # rows 77..79 stay zero
         self.text_embeds = torch.zeros(B, cfg.pooled_dim, dtype=F16, device=dev)
         self.eps = torch.zeros(B, cfg.out_channels, L, L, dtype=F16, device=dev)
+        # guidance-scale embedding of guidance-distilled UNets, one row per sample (None for every other config)
+        self.timestep_cond = None if cfg.time_cond_proj_dim is None else torch.zeros(B, cfg.time_cond_proj_dim, dtype=F16, device=dev)
         # ---- conditioning-program outputs (persistent) ----
         self.aug = torch.zeros(B, T, dtype=F16, device=dev)
         self.ctx_kv = torch.zeros(B * CTX_PAD, 2 * net.n_ctx, dtype=F16, device=dev)   # [K of all blocks | V of all blocks]
@@ -427,6 +435,11 @@ class UNetProgram:
         # time embedding: silu(temb + aug) feeds every resnet's projection -> one fused GEMM
         tsin = ar.alloc((B, ch[0]))
         api.lb_sinusoid_f16(self.tvals.data_ptr(), B, 1, 1, ch[0], tsin.data_ptr(), ch[0], 0, _stream())
+        if self.timestep_cond is not None:      # tsum = timestep_cond . Wc^T + tsin (diffusers: sample + cond_proj(condition))
+            tsum = ar.alloc((B, ch[0]))
+            em.gemm(self.timestep_cond, w["time_embedding.cond_proj.weight"], tsum, M=B, residual=tsin)
+            ar.release(tsin)
+            tsin = tsum
         t1 = ar.alloc((B, T))
         em.gemm(tsin, w["time_embedding.linear_1.weight"], t1, M=B, bias=w["time_embedding.linear_1.bias"],
                 flags=lib.GEMM_SILU)
@@ -503,8 +516,23 @@ class UNetProgram:
         ar.release(o)
 
     # ---- execution ------------------------------------------------------------------------
-    def set_conditioning(self, ctx: torch.Tensor, text_embeds: torch.Tensor, time_ids: torch.Tensor):
-        """ctx [B,77,X] fp16, text_embeds [B,P] fp16, time_ids [B,6] (any float dtype)."""
+    def set_conditioning(self, ctx: torch.Tensor, text_embeds: torch.Tensor, time_ids: torch.Tensor,
+                         timestep_cond: Optional[torch.Tensor] = None):
+        """ctx [B,77,X] fp16, text_embeds [B,P] fp16, time_ids [B,6] (any float dtype); ``timestep_cond`` [B, time_cond_proj_dim]
+        (or one row for all samples): the guidance-scale embedding - required when the config has that dimension, refused when
+        it has not (the step program reads it; the conditioning program does not depend on it)."""
+        if self.timestep_cond is None:
+            if timestep_cond is not None:
+                raise ValueError("UNetProgram.set_conditioning: timestep_cond given, but the UNet config has no time_cond_proj_dim")
+        else:
+            if timestep_cond is None:
+                raise ValueError("UNetProgram.set_conditioning: this UNet is guidance-embedded (time_cond_proj_dim = "
+                                 f"{self.net.cfg.time_cond_proj_dim}): timestep_cond is required")
+            tc = timestep_cond.reshape(-1, timestep_cond.shape[-1])
+            if tc.shape[-1] != self.timestep_cond.shape[1] or tc.shape[0] not in (1, self.B):
+                raise ValueError(f"UNetProgram.set_conditioning: timestep_cond of shape {tuple(timestep_cond.shape)}, "
+                                 f"expected [{self.B} or 1, {self.timestep_cond.shape[1]}]")
+            self.timestep_cond.copy_(tc.expand(self.B, -1))
         self.ctx[:, :CTX_TOKENS].copy_(ctx)
         self.text_embeds.copy_(text_embeds)
         self.time_ids.copy_(time_ids.to(F32))

@@ -2,7 +2,8 @@
 
 The model builders walk their architecture and ask a provider for every parameter by its HF
 diffusers state-dict name (``down_blocks.1.attentions.0.transformer_blocks.0.attn1.to_q.weight``,
-``decoder.up_blocks.2.resnets.0.conv1.weight`` ...), so the same walk serves
+``decoder.up_blocks.2.resnets.0.conv1.weight`` ...; a guidance-distilled UNet config also asks for
+``time_embedding.cond_proj.weight``), so the same walk serves
 
 * ``DictProvider``      — a state dict: a real checkpoint's tensors (``from_safetensors``) or the
   seeded weights a test shares with the CPU oracle;
