@@ -99,6 +99,11 @@ enum {
                               * the STORED values to ch_stats[channel][row block] (float2, channel-major) - the GroupNorm statistics of this conv's
                               * output without a second pass over it (lb_groupnorm_from_stats).  Row block = (tile [, parity])
                               * * 4 + wave row; rows per sample: lb_gemm_ch_stat_rows) */
+    LB_GEMM_HALO_RAGGED = 1024, /* opt-in, 3x3 halo-tile conv only (lb_conv3x3_halo_f16, the router in lb_gemm_f16, lb_conv_halo_plan,
+                              * lb_gemm_ch_stat_rows): the image need not divide into 32 x 8 or 16 x 16 tiles.  Tiles are counted with
+                              * ceiling division, the tile shape is the one that covers the image with fewer tile pixels (ties: 32 x 8),
+                              * pixels of an overhanging tile outside the image are neither stored nor counted into LB_GEMM_CH_STATS.
+                              * A shape that divides runs exactly what it runs without the flag; every other launcher ignores the bit. */
     LB_GEMM_LN_A = 64        /* A is consumed through a LayerNorm over its K columns (K = the normalised width):
                                 C = LN(A) . Wt computed as rstd_m * (A . W'^T - mean_m * colsum) + bias with
                                 W' = W * gamma (folded by the caller), ln_colsum[n] = sum_k W'[n][k],
@@ -150,7 +155,7 @@ void lb_gemm_pp_set_group(int gm);                /* tuning: tile order of the p
 void lb_gemm_set_depth(int depth);               /* testing: 1 = one K-tile in flight, 0 = default ring */
 int lb_gemm_plan(const LbGemmParams* p, int* tile, int* splitk, long* blocks); /* the tile (1..5) / split-K / grid lb_gemm_f16 would use; launches nothing */
 /* 3x3 / stride 1 / pad 1 conv from an LDS-resident halo tile; same parameter block as lb_gemm_f16 (conv = 1,
- * KH = KW = 3, Cin % 64 == 0, Win % 16 == 0, zero_page set).  lb_gemm_f16 routes eligible convs here by itself
+ * KH = KW = 3, Cin % 64 == 0, Win % 16 == 0 - or any Hin x Win with LB_GEMM_HALO_RAGGED -, zero_page set).  lb_gemm_f16 routes eligible convs here by itself
  * (lb_gemm_plan reports tile code 6); lb_gemm_set_halo: 0 = never, 1 = when the halo grid fills the chip
  * (default), 2 = whenever eligible. */
 int lb_conv3x3_halo_f16(const LbGemmParams* params, void* stream);

@@ -77,8 +77,14 @@ template <int KS, int NR, int TAP> constexpr int halo_full_rounds_in_tap() {   /
 // form on every conv shape of the programs (profiles/r04_halo_pp_ab.txt; git history has the code): the step body below
 // already spreads its requests and its second fragment read between the MFMA groups, and the two waves of a SIMD drift apart
 // on their own.  What a tile pays beyond its MFMA + LDS time is the epilogue and the once-per-chunk activation read.
-template <int BN, int TW, int KS = 3>
+//
+// RAG (LB_GEMM_HALO_RAGGED, 3x3 form only): the image need not divide into tiles.  Tiles are counted with ceiling division; a tile that
+// overhangs the right / bottom edge stages zeros for the pixels outside the image (the loader's mask below does that for every form) and
+// its epilogue stores - and counts into the channel statistics - only the pixels inside it.  The request streams and their vmcnt counts
+// are those of the whole-tile form: masked requests are still issued.  RAG = false is the shipped code, instruction for instruction.
+template <int BN, int TW, int KS = 3, bool RAG = false>
 __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p) {
+    static_assert(!RAG || KS == 3, "ragged tiles exist for the 3x3 form only");
     constexpr int TH = 256 / TW;
     constexpr int NTAP = KS * KS;
     constexpr int HWP = TW + KS - 1;                    // halo width in pixels
@@ -113,7 +119,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
     // store drain (measured ~14 us, against 11 us of MFMA work for an 18-step Cin = 128 tile) once per tile.
     // With gridDim.x == number of items the same code is the one-item-per-block form.
     const int n_blocks = (p.N + BN - 1) / BN;
-    const int tiles_x = p.Win / TW, tiles_y = p.Hin / TH;
+    const int tiles_x = RAG ? (p.Win + TW - 1) / TW : p.Win / TW, tiles_y = RAG ? (p.Hin + TH - 1) / TH : p.Hin / TH;
     const int n_items = (p.M / (p.Hin * p.Win)) * tiles_x * tiles_y * (KS == 2 ? 4 : 1) * n_blocks;
     const int G = gridDim.x;
     int bid = blockIdx.x;
@@ -339,8 +345,28 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         // across the MFMA loop - which it then spills around this epilogue)
         int col0 = n0 + wave_n * (BN / 2) + 4 * g;
         asm volatile("" : "+v"(col0));
-        if (!(study & 1)) {
-            // geometry of the one-round-trip epilogue (lb_gemm.h): the tile's rows all exist and lie inside ONE image; output
+        bool overhang = false;                          // (block-uniform) RAG: this tile has pixels outside the image
+        if constexpr (RAG) overhang = cur.y0 + TH > p.Hin || cur.x0 + TW > p.Win;
+        if (RAG && overhang && !(study & 1)) {
+            // The geometry of the one-round-trip epilogue below does not hold: the address of a pixel outside the image is the next
+            // image row's, the next sample's or past the end of the buffer.  Per-row epilogue with the pixel's validity as its row mask
+            // (a row >= M loads its operands from row M - 1 and stores nothing; ROWMASK keeps it out of the statistics as well).
+            int tid_o = tid;
+            asm volatile("" : "+v"(tid_o));
+            auto row_of = [&](int i) {
+                const int ml = (tid_o >> 7) * 64 + i * 16 + (tid_o & 15), ly = ml / TW, lx = ml - ly * TW;
+                return cur.y0 + ly < p.Hin && cur.x0 + lx < p.Win ? mbase + mloc[i] : p.M;
+            };
+            if (p.flags & LB_GEMM_CH_STATS) {
+                const long stat_rows = (long)(n_items / n_blocks) * 4;
+                float2* chst = reinterpret_cast<float2*>(p.ch_stats) + ((long)(item / n_blocks) * 4 + wave_m);
+                lb_gemm_tile_epilogue_rows_ln<TM, TN, false, false, true, true>(q, acc, row_of, col0, 0, (const LbLnRows<TM>*)nullptr, chst, stat_rows);
+            } else {
+                lb_gemm_tile_epilogue_rows<TM, TN, false>(q, acc, row_of, col0, 0);
+            }
+        } else if (!(study & 1)) {
+            // geometry of the one-round-trip epilogue (lb_gemm.h): the tile's rows all exist and lie inside ONE image (a RAG launch
+            // comes here with its whole tiles only); output
             // rows relative to the tile's first output pixel (for KS == 2 on the 2x grid, at this block's parity) are
             // recomputed from the lane's local pixel index - compile-time shifts, nothing held across the MFMA loop
             int tid_o = tid;                            // (opaque: nothing derived from it is hoisted out of the tile loop)
@@ -401,9 +427,11 @@ static int halo_num_cus() {
 
 // work items of a launch and the grid that walks them: persistent = the largest multiple of the weight-slab period
 // (channel blocks, x4 parities for the 2x2 form) that fits the CUs, so that a block keeps one (channel block, parity)
+// (ceiling division: the same counts as ever for shapes that divide into tiles - the only ones the 2x2 form and the unflagged 3x3
+//  form accept -, the ragged tile counts under LB_GEMM_HALO_RAGGED)
 static void halo_grid(const LbGemmParams& p, int tw, int ks, long& items, long& grid) {
     const int th = 256 / tw;
-    const long tiles = (long)(p.M / (p.Hin * p.Win)) * (p.Hin / th) * (p.Win / tw) * (ks == 2 ? 4 : 1);
+    const long tiles = (long)(p.M / (p.Hin * p.Win)) * ((p.Hin + th - 1) / th) * ((p.Win + tw - 1) / tw) * (ks == 2 ? 4 : 1);
     const int n_blocks = (p.N + 127) / 128;
     items = tiles * n_blocks;
     const int period = n_blocks * (ks == 2 ? 4 : 1);
@@ -426,7 +454,7 @@ long lb_conv_halo_stat_rows_total(const LbGemmParams& p) {
     return items / ((p.N + 127) / 128) * 4;
 }
 
-template <int BN, int TW, int KS = 3>
+template <int BN, int TW, int KS = 3, bool RAG = false>
 static int launch_halo(const LbGemmParams& p, hipStream_t stream) {
     constexpr int TH = 256 / TW;
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
@@ -435,7 +463,7 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream) {
     // (a recording does not come here: the first call on a device happens at the first replay - inside the stream capture of
     //  lb_program_instantiate when a program is instantiated before any eager run)
     LB_ONCE_PER_DEVICE(seen)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
     long nblk, grid;
@@ -444,7 +472,7 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream) {
 #ifdef LB_STUDY_BUILD
     pk.reserved_ = g_halo_study;
 #endif
-    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
     return lb_check_launch(KS == 2 ? "lb_upconv2x_halo_f16" : "lb_conv3x3_halo_f16");
 }
 
@@ -503,11 +531,18 @@ int lb_conv3x3_halo_eligible(const LbGemmParams& p) {
     if ((long)p.N * p.ldw * 2 >= (1l << 32)) return 0;         // (32-bit byte offsets into the weight matrix: LB_HALO_LEAN_ADDR)
     if (p.Win % 32 == 0 && p.Hin % 8 == 0) return 32;
     if (p.Win % 16 == 0 && p.Hin % 16 == 0) return 16;
-    return 0;
+    if (!(p.flags & LB_GEMM_HALO_RAGGED)) return 0;
+    // ragged tiles (opt-in): the tile shape that covers the image with fewer tile pixels; ties go to 32 x 8
+    const long t32 = (long)((p.Win + 31) / 32) * ((p.Hin + 7) / 8), t16 = (long)((p.Win + 15) / 16) * ((p.Hin + 15) / 16);
+    return t16 < t32 ? 16 : 32;
 }
+// (of an eligible problem) the image does not divide into tiles of the width lb_conv3x3_halo_eligible chose: the RAG instantiation
+static bool halo3_ragged(const LbGemmParams& p, int tw) { return p.Win % tw != 0 || p.Hin % (256 / tw) != 0; }
 
 long lb_conv3x3_halo_blocks(const LbGemmParams& p) {
-    const long tiles = (long)p.M / 256;                 // 256 output pixels per block
+    long tiles = (long)p.M / 256;                       // 256 output pixels per block
+    if (const int tw = (p.flags & LB_GEMM_HALO_RAGGED) ? lb_conv3x3_halo_eligible(p) : 0)       // (ragged: blocks, not pixels / 256)
+        tiles = (long)(p.M / (p.Hin * p.Win)) * ((p.Hin + 256 / tw - 1) / (256 / tw)) * ((p.Win + tw - 1) / tw);
     return tiles * ((p.N + 127) / 128);
 }
 
@@ -522,7 +557,9 @@ int lb_conv3x3_halo_check(const LbGemmParams& p) {
 int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
-    return lb_conv3x3_halo_eligible(p) == 32 ? launch_halo<128, 32>(p, stream) : launch_halo<128, 16>(p, stream);
+    const int tw = lb_conv3x3_halo_eligible(p);
+    if (halo3_ragged(p, tw)) return tw == 32 ? launch_halo<128, 32, 3, true>(p, stream) : launch_halo<128, 16, 3, true>(p, stream);
+    return tw == 32 ? launch_halo<128, 32>(p, stream) : launch_halo<128, 16>(p, stream);
 }
 
 extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
@@ -530,7 +567,7 @@ extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_conv3x3_halo_f16: empty problem");
     LB_REQUIRE(lb_conv3x3_halo_eligible(p) != 0,
-               "lb_conv3x3_halo_f16: needs a 3x3 / stride 1 / pad 1 conv, Cin % 64 == 0, W % 16 == 0, zero page");
+               "lb_conv3x3_halo_f16: needs a 3x3 / stride 1 / pad 1 conv, Cin % 64 == 0, W % 16 == 0 (or LB_GEMM_HALO_RAGGED), zero page");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && (p.ldc % 4 == 0 || (p.flags & LB_GEMM_TRANS_OUT)),
                "lb_conv3x3_halo_f16: ldw / ldx multiples of 8, ldc multiple of 4");
     if (const int rc = lb_conv3x3_halo_check(p)) return rc;

@@ -119,7 +119,8 @@ __device__ __forceinline__ void lb_row16_reduce32(const float (&v)[32], float (&
 // values this epilogue STORES (after the fp16 rounding when the output is fp16) go to chst[n * chst_ld] (float2: the statistics
 // buffer is CHANNEL-major, [N][row blocks], so that the fold kernel reads a group's channels as contiguous runs): each lane sums its
 // TM rows, the 16 lanes that share a column quad (l16 = 0..15) fold them with a DPP butterfly (fixed order), two values per lane.
-template <int TM, int TN, bool GEGLU, bool LNA, bool CHST = false, typename RowFn>
+// ROWMASK (ragged halo tiles): rows >= M are left out of the sums as well (they store nothing in every form).
+template <int TM, int TN, bool GEGLU, bool LNA, bool CHST = false, bool ROWMASK = false, typename RowFn>
 __device__ __forceinline__ void lb_gemm_tile_epilogue_rows_ln(const LbGemmParams& p, const f32x4 (&acc)[TM][TN],
                                                            RowFn row_of, int col0, int gcol0, const LbLnRows<TM>* ln,
                                                            float2* chst = nullptr, long chst_ld = 1) {
@@ -294,7 +295,8 @@ __device__ __forceinline__ void lb_gemm_tile_epilogue_rows_ln(const LbGemmParams
             if (CHST) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float h = (p.flags & LB_GEMM_OUT_F32) ? o[r] : (float)(f16)o[r];   // the value a GroupNorm pass would read back
+                    float h = (p.flags & LB_GEMM_OUT_F32) ? o[r] : (float)(f16)o[r];   // the value a GroupNorm pass would read back
+                    if (ROWMASK) h = m_ok ? h : 0.f;
                     cs_s[j][r] += h;
                     cs_q[j][r] += h * h;
                 }

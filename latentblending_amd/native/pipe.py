@@ -34,6 +34,7 @@ from PIL import Image
 from ..hip import ops
 from ..hip.lib import api
 from .frames import DeviceImage
+from .geometry import program_key
 from .lpips import NativeLPIPS
 from .scheduler import NativeDDIMScheduler, NativeEulerScheduler, NativeLCMScheduler, noise_draws_per_run
 from .unet import NativeUNet, UNetConfig, UNetProgram
@@ -62,8 +63,8 @@ class _UNetFacade:
             raise ValueError("NativeSDXLPipe.unet: this UNet is guidance-embedded (time_cond_proj_dim = "
                              f"{self.config.time_cond_proj_dim}); timestep_cond is required "
                              "(pipe.get_guidance_scale_embedding(guidance_scale - 1, embedding_dim=time_cond_proj_dim))")
-        B, _, L, _ = sample.shape
-        prog = pipe.unet_program(B, L)
+        B, _, H, W = sample.shape
+        prog = pipe.unet_program(B, (H, W))
         prog.set_conditioning(encoder_hidden_states, added_cond_kwargs["text_embeds"],
                               added_cond_kwargs["time_ids"],
                               timestep_cond=None if timestep_cond is None else timestep_cond.to(sample.device, F16))
@@ -81,7 +82,7 @@ class _VAEFacade:
 
     def decode(self, z, return_dict=False):
         """z = latents / scaling_factor -> float image [B,3,H,W] (diffusers convention)."""
-        prog = self._pipe.vae_program(z.shape[0], z.shape[-1])
+        prog = self._pipe.vae_program(z.shape[0], (z.shape[-2], z.shape[-1]))
         prog.decode((z.float() * self._pipe.vae_cfg.scaling_factor).to(F16))
         return (prog.image_f32[..., :3].permute(0, 3, 1, 2).clone(),)
 
@@ -166,10 +167,14 @@ class StableDiffusionXLPipeline:
         self._denoising_end = None
         self._interrupt = False
         self._num_timesteps = 0
-        # recorded launch programs, keyed by (batch, latent side); each owns its activation arena (+ hipGraph), so the
+        # recorded launch programs, keyed by geometry.program_key: (batch, latent side) or (batch, latent height, latent width); each owns its activation arena (+ hipGraph), so the
         # caches are LRU-bounded: speculative rounds of varying width must not pile up SDXL-sized arenas
-        self._unet_programs: "OrderedDict[Tuple[int, int], UNetProgram]" = OrderedDict()
-        self._vae_programs: "OrderedDict[Tuple[int, int], VAEProgram]" = OrderedDict()
+        self._unet_programs: "OrderedDict[Tuple[int, ...], UNetProgram]" = OrderedDict()
+        self._vae_programs: "OrderedDict[Tuple[int, ...], VAEProgram]" = OrderedDict()
+        # non-square programs send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo kernel
+        # (geometry.use_ragged_halo); False = the implicit GEMM there (A/B runs, tests).  Read when a program is BUILT: the
+        # setter drops the cached non-square programs.
+        self._ragged_halo = True
         self.max_cached_programs = 8
         self._embed_cache: OrderedDict = OrderedDict()           # text -> (prompt_embeds, pooled); cleared when the encoder changes
         self._use_graphs = False
@@ -310,21 +315,38 @@ class StableDiffusionXLPipeline:
         cache[key] = build()
         return cache[key]
 
-    def unet_program(self, B: int, L: int) -> UNetProgram:
+    @property
+    def ragged_halo(self) -> bool:
+        return self._ragged_halo
+
+    @ragged_halo.setter
+    def ragged_halo(self, flag: bool):
+        flag = bool(flag)
+        if flag != self._ragged_halo:
+            self._ragged_halo = flag
+            for cache in (self._unet_programs, self._vae_programs):
+                stale = [k for k in cache if len(k) == 3]           # (square programs, keyed (B, L), never carry the flag)
+                if stale:
+                    torch.cuda.synchronize(self.device)
+                for k in stale:
+                    del cache[k]
+
+    def unet_program(self, B: int, L) -> UNetProgram:
+        """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named)."""
         def build():
-            prog = self.unet_native.build(B, L)
+            prog = self.unet_native.build(B, L, ragged_halo=self._ragged_halo)
             if self._use_graphs:
                 prog.enable_graphs()
             return prog
-        return self._cached(self._unet_programs, (B, L), build)
+        return self._cached(self._unet_programs, program_key(B, L), build)
 
-    def vae_program(self, B: int, L: int) -> VAEProgram:
+    def vae_program(self, B: int, L) -> VAEProgram:
         def build():
-            prog = self.vae_native.build(B, L)
+            prog = self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
             if self._use_graphs:
                 prog.prog.instantiate()
             return prog
-        return self._cached(self._vae_programs, (B, L), build)
+        return self._cached(self._vae_programs, program_key(B, L), build)
 
     def enable_graphs(self, flag: bool = True):
         self._use_graphs = bool(flag)
@@ -378,9 +400,9 @@ class StableDiffusionXLPipeline:
             return out
         self._guidance_scale = float(guidance_scales[-1])
         cfg = wants[0]
-        L = starts[0].shape[-1]
+        LH, LW = int(starts[0].shape[-2]), int(starts[0].shape[-1])
         per_sample = starts[0][0].numel()
-        prog = self.unet_program(G * (2 if cfg else 1), L)
+        prog = self.unet_program(G * (2 if cfg else 1), (LH, LW))
 
         pos_ctx = torch.cat([c[0] for c in conds]).to(self.device, F16)
         pos_pool = torch.cat([c[2] for c in conds]).to(self.device, F16)
@@ -393,7 +415,7 @@ class StableDiffusionXLPipeline:
         time_ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
         prog.set_conditioning(ctx, pooled, time_ids, timestep_cond=self._timestep_cond(guidance_scales))
 
-        latents = torch.cat([s.to(self.device, F16).reshape(1, -1, L, L) for s in starts]).contiguous()
+        latents = torch.cat([s.to(self.device, F16).reshape(1, -1, LH, LW) for s in starts]).contiguous()
         trajs: List[List[Optional[torch.Tensor]]] = [[None] * idx_start for _ in range(G)]
         stream = torch.cuda.current_stream().cuda_stream
         # every step's scalar coefficients in ONE upload: [steps][G][8]
@@ -482,7 +504,7 @@ class StableDiffusionXLPipeline:
         anchor_starts = [anchor_starts[k] for k in live]
         assert all(self.uses_cfg(g) == cfg for g in all_g), "wavefront batches must be uniformly CFG or non-CFG"
         mul = 2 if cfg else 1
-        L = ref_start.shape[-1]
+        LH, LW = int(ref_start.shape[-2]), int(ref_start.shape[-1])
         per_sample = ref_start[0].numel()
 
         def conditioning(conds):
@@ -501,7 +523,7 @@ class StableDiffusionXLPipeline:
             # stream the side stream waits for INSTEAD of everything queued on the main stream so far (the deferred form: the first
             # small UNet step is already queued - waiting for it would also park the host in the side stream's host-to-device copies)
             n_conds = A + G if callable(conds) else len(conds)
-            prog = self.unet_program(n_conds * mul, L)
+            prog = self.unet_program(n_conds * mul, (LH, LW))
             if side is None:
                 conds = conds() if callable(conds) else conds
                 ctx, pooled = conditioning(conds)
@@ -556,11 +578,11 @@ class StableDiffusionXLPipeline:
             # (contiguous per step: the step kernels take noise[i] by pointer)
             noise_a = flat[:A * nd_a].view(A, nd_a, *shape1[1:]).transpose(0, 1).contiguous() if A else None          # [nd_a, A, 4, L, L]
             noise_m = flat[A * nd_a:].view(n_draw, nm, *shape1[1:])[keep].transpose(0, 1).contiguous() if G and nm else None   # [nm, G, 4, L, L]
-        lat_shape = (int(ref_start.shape[-3]), L, L)
-        lat_a = torch.cat([s.to(self.device, F16).reshape(1, -1, L, L) for s in anchor_starts]).contiguous() if A else \
+        lat_shape = (int(ref_start.shape[-3]), LH, LW)
+        lat_a = torch.cat([s.to(self.device, F16).reshape(1, -1, LH, LW) for s in anchor_starts]).contiguous() if A else \
             torch.empty((0,) + lat_shape, dtype=F16, device=self.device)
         lat_m = None
-        traj_a = [[] if known[k] is None else [t.to(self.device, F16).reshape(1, -1, L, L) for t in known[k]] for k in (0, 1)]
+        traj_a = [[] if known[k] is None else [t.to(self.device, F16).reshape(1, -1, LH, LW) for t in known[k]] for k in (0, 1)]
         traj_m: List[List[Optional[torch.Tensor]]] = [[None] * idx_injection for _ in range(G)]
         # mixing fractions / crossfeed coefficients live on the device: every step's parental mix (ONE pair of anchor
         # latents at G fractions) and crossfeed (G pairs) is one strided-slerp launch, no host pointer tables
@@ -632,7 +654,7 @@ class StableDiffusionXLPipeline:
     @torch.no_grad()
     def native_latent2image_batch(self, latents: Sequence[torch.Tensor], output_type="pil"):
         z = torch.cat([t.to(self.device, F16).reshape(1, -1, t.shape[-2], t.shape[-1]) for t in latents])
-        prog = self.vae_program(z.shape[0], z.shape[-1])
+        prog = self.vae_program(z.shape[0], (z.shape[-2], z.shape[-1]))
         frames = prog.decode(z).clone()
         self.stats["vae_decodes"] += z.shape[0]
         if output_type == "np":     # the reference's postprocess(..., "np"): (x / 2 + 0.5).clamp(0, 1) as float32 HWC, unquantised

@@ -20,6 +20,7 @@ import torch
 
 from ..hip import lib
 from ..hip.lib import api, LbGemmParams, LbAttnParams
+from .geometry import use_ragged_halo
 
 F16, F32 = torch.float16, torch.float32
 
@@ -143,6 +144,25 @@ class Emitter:
         self.norm_log: List[dict] = []      # GroupNorm / LayerNorm launches: algorithmic HBM bytes
         self._retired: List[torch.Tensor] = []
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=self.device)
+        # set by the builder of a NON-SQUARE program (and its pipe's ``ragged_halo`` switch): 3x3 convs whose level does not divide
+        # into halo tiles ask for the ragged-tile form (LB_GEMM_HALO_RAGGED) where ``geometry.use_ragged_halo`` says so.  False
+        # (every square program): no plan call, no flag - the recorded ops are those of ever.
+        self.ragged_halo = False
+
+    def _ragged_flag(self, p: LbGemmParams) -> int:
+        """LB_GEMM_HALO_RAGGED or 0 for the 3x3 / stride 1 conv ``p`` describes (the library's own plan, with and without the bit).
+        Convs of at most 16 output channels are left alone: the narrow-N kernel's domain, 128-column halo blocks would idle."""
+        if not self.ragged_halo or not p.conv or p.KH != 3 or p.KW != 3 or p.stride != 1 or p.scatter or p.ups or p.N <= 16:
+            return 0
+        kind, tw = C.c_int(), C.c_int()
+        flags = p.flags
+        p.flags = flags & ~lib.GEMM_HALO_RAGGED
+        api.lb_conv_halo_plan(C.byref(p), C.byref(kind), None, None, None)
+        plain = kind.value
+        p.flags = flags | lib.GEMM_HALO_RAGGED
+        api.lb_conv_halo_plan(C.byref(p), C.byref(kind), C.byref(tw), None, None)
+        p.flags = flags
+        return lib.GEMM_HALO_RAGGED if use_ragged_halo(True, plain, kind.value, p.Hin, p.Win, tw.value) else 0
 
     # -- workspaces -------------------------------------------------------------------------
     def _gemm_ws(self, M: int, N: int) -> Optional[torch.Tensor]:
@@ -205,6 +225,8 @@ class Emitter:
             p.ch_stats, p.ch_stats_rows = ch_stats.data_ptr(), ch_stats.shape[1]    # [N][B * rows][2]: checked by the launcher
         if splitk and not (flags & lib.GEMM_GEGLU) and ln is None:
             p.partial = _p(self._gemm_ws(M, N))
+        if self.ragged_halo:
+            p.flags |= self._ragged_flag(p)
         api.lb_gemm_f16(C.byref(p), _stream())
         mult = 4.0 if p.scatter == 2 else 1.0          # (four parities: four times the rows, weights and outputs)
         self.gemm_log.append({"M": M, "N": N, "K": K, "flops": mult * 2.0 * M * N * K, "conv": conv is not None,
@@ -233,6 +255,8 @@ class Emitter:
         p.zero_page = self.zero_page.data_ptr()
         if ks == 2 and not self.upconv_one_launch(B, H, W, cin, cout):
             return 0
+        if self.ragged_halo:                  # (the same decision ``gemm`` makes for the launch itself)
+            p.flags |= self._ragged_flag(p)
         return int(api.lb_gemm_ch_stat_rows(C.byref(p)))      # the library's own routing + tile constants (0: not a halo launch)
 
     @staticmethod

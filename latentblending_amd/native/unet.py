@@ -26,6 +26,7 @@ import torch
 
 from ..hip import lib
 from ..hip.lib import api
+from .geometry import check_unet_latent_size, latent_hw
 from .runtime import Arena, Emitter, Program, F16, F32, _stream
 
 CTX_TOKENS = 77
@@ -255,30 +256,38 @@ class NativeUNet:
         return sum(t.numel() * t.element_size() for t in self.w.values())
 
     # ------------------------------------------------------------------ program -----------
-    def build(self, B: int, L: int) -> "UNetProgram":
-        return UNetProgram(self, B, L)
+    def build(self, B: int, L, ragged_halo: bool = True) -> "UNetProgram":
+        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``)."""
+        return UNetProgram(self, B, L, ragged_halo=ragged_halo)
 
 
 class UNetProgram:
-    """One recorded forward for a fixed (batch, latent side).  Inputs are device buffers the
-    caller fills (torch copies on the launch stream); ``run`` replays the launches."""
+    """One recorded forward for a fixed (batch, latent size).  Inputs are device buffers the
+    caller fills (torch copies on the launch stream); ``run`` replays the launches.
+    ``L``: latent side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for square programs (else None).  ``ragged_halo``: a
+    non-square program may send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo
+    kernel (``geometry.use_ragged_halo``); a square program records what it always recorded."""
 
-    def __init__(self, net: NativeUNet, B: int, L: int):
+    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True):
         cfg = net.cfg
-        self.net, self.B, self.L = net, B, L
+        H, W = latent_hw(L)
+        check_unet_latent_size(H, W, len(cfg.block_channels))
+        self.net, self.B, self.H, self.W = net, B, H, W
+        self.L = H if H == W else None
         # LayerNorm handling of THIS program ("auto": fold into the consumers only where the program is launch-bound)
-        self.ln_mode = net.fuse_layernorm if net.fuse_layernorm != "auto" else (B * max(L // 4, 1) ** 2 <= 1024)
+        self.ln_mode = net.fuse_layernorm if net.fuse_layernorm != "auto" else (B * max(H // 4, 1) * max(W // 4, 1) <= 1024)
         dev = net.device
         self.arena = Arena(dev)
         self.em = Emitter(self.arena)
+        self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
         T = cfg.time_embed_dim
         # ---- inputs / outputs (persistent) ----
-        self.x_in = torch.zeros(B, cfg.in_channels, L, L, dtype=F16, device=dev)
+        self.x_in = torch.zeros(B, cfg.in_channels, H, W, dtype=F16, device=dev)
         self.tvals = torch.zeros(B, 1, dtype=F32, device=dev)
         self.time_ids = torch.zeros(B, 6, dtype=F32, device=dev)
         self.ctx = torch.zeros(B, CTX_PAD, cfg.cross_dim, dtype=F16, device=dev)     # rows 77..79 stay zero
         self.text_embeds = torch.zeros(B, cfg.pooled_dim, dtype=F16, device=dev)
-        self.eps = torch.zeros(B, cfg.out_channels, L, L, dtype=F16, device=dev)
+        self.eps = torch.zeros(B, cfg.out_channels, H, W, dtype=F16, device=dev)
         # guidance-scale embedding of guidance-distilled UNets, one row per sample (None for every other config)
         self.timestep_cond = None if cfg.time_cond_proj_dim is None else torch.zeros(B, cfg.time_cond_proj_dim, dtype=F16, device=dev)
         # ---- conditioning-program outputs (persistent) ----
@@ -430,7 +439,7 @@ class UNetProgram:
 
     # ---- step program: depends on the latent and the timestep
     def _emit_step(self):
-        net, cfg, em, w, ar, B, L = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B, self.L
+        net, cfg, em, w, ar, B = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B
         ch, T = cfg.block_channels, cfg.time_embed_dim
         # time embedding: silu(temb + aug) feeds every resnet's projection -> one fused GEMM
         tsin = ar.alloc((B, ch[0]))
@@ -453,35 +462,35 @@ class UNetProgram:
         ar.release(emb)
         # input: NCHW latent -> NHWC (channels padded to 8)
         cin_p = _pad(cfg.in_channels, 8)
-        x8 = ar.alloc((B, L, L, cin_p))
-        api.lb_nchw_to_nhwc_f16(self.x_in.data_ptr(), x8.data_ptr(), B, cfg.in_channels, L * L, cin_p, 1.0, _stream())
-        h, _, _ = self._conv(x8, "conv_in", B, L, L, cfg.in_channels, ch[0])
+        x8 = ar.alloc((B, self.H, self.W, cin_p))
+        api.lb_nchw_to_nhwc_f16(self.x_in.data_ptr(), x8.data_ptr(), B, cfg.in_channels, self.H * self.W, cin_p, 1.0, _stream())
+        h, _, _ = self._conv(x8, "conv_in", B, self.H, self.W, cfg.in_channels, ch[0])
         ar.release(x8)
         skips = [(h, ch[0])]
-        side, prev = L, ch[0]
+        sh, sw, prev = self.H, self.W, ch[0]                    # the current level's map is sh x sw
         for bi, c in enumerate(ch):
             for li in range(cfg.layers_per_block):
-                nxt = self._resnet(h, f"down_blocks.{bi}.resnets.{li}", B, side, side, prev, c)
+                nxt = self._resnet(h, f"down_blocks.{bi}.resnets.{li}", B, sh, sw, prev, c)
                 if not any(h is s for s, _ in skips):
                     ar.release(h)
                 h = nxt
                 if cfg.transformer_depth[bi]:
-                    nxt = self._transformer(h, f"down_blocks.{bi}.attentions.{li}", B, side, side, c,
+                    nxt = self._transformer(h, f"down_blocks.{bi}.attentions.{li}", B, sh, sw, c,
                                             cfg.transformer_depth[bi])
                     ar.release(h)
                     h = nxt
                 skips.append((h, c))
                 prev = c
             if bi < len(ch) - 1:
-                h, side, _ = self._conv(h, f"down_blocks.{bi}.downsamplers.0.conv", B, side, side, c, c, stride=2)
+                h, sh, sw = self._conv(h, f"down_blocks.{bi}.downsamplers.0.conv", B, sh, sw, c, c, stride=2)
                 skips.append((h, c))
         c = ch[-1]
-        nxt = self._resnet(h, "mid_block.resnets.0", B, side, side, c, c)     # h is a skip: not released
+        nxt = self._resnet(h, "mid_block.resnets.0", B, sh, sw, c, c)     # h is a skip: not released
         h = nxt
-        nxt = self._transformer(h, "mid_block.attentions.0", B, side, side, c, cfg.transformer_depth[-1])
+        nxt = self._transformer(h, "mid_block.attentions.0", B, sh, sw, c, cfg.transformer_depth[-1])
         ar.release(h)
         h = nxt
-        nxt = self._resnet(h, "mid_block.resnets.1", B, side, side, c, c)
+        nxt = self._resnet(h, "mid_block.resnets.1", B, sh, sw, c, c)
         ar.release(h)
         h = nxt
         depths = list(reversed(cfg.transformer_depth))
@@ -489,29 +498,29 @@ class UNetProgram:
             for li, (hid, sc) in enumerate(cins):
                 skip, sch = skips.pop()
                 assert sch == sc
-                M = B * side * side
-                cat = ar.alloc((B, side, side, hid + sc))
+                M = B * sh * sw
+                cat = ar.alloc((B, sh, sw, hid + sc))
                 em.copy_cols(h, cat, rows=M, cols=hid, ld_src=hid, ld_dst=hid + sc, dst_off=0)
                 em.copy_cols(skip, cat, rows=M, cols=sc, ld_src=sc, ld_dst=hid + sc, dst_off=hid)
                 ar.release(h)
                 ar.release(skip)
-                h = self._resnet(cat, f"up_blocks.{ui}.resnets.{li}", B, side, side, hid + sc, c)
+                h = self._resnet(cat, f"up_blocks.{ui}.resnets.{li}", B, sh, sw, hid + sc, c)
                 ar.release(cat)
                 if depths[ui]:
-                    nxt = self._transformer(h, f"up_blocks.{ui}.attentions.{li}", B, side, side, c, depths[ui])
+                    nxt = self._transformer(h, f"up_blocks.{ui}.attentions.{li}", B, sh, sw, c, depths[ui])
                     ar.release(h)
                     h = nxt
             if ui < len(ch) - 1:
-                nxt, side, _ = self._upconv(h, f"up_blocks.{ui}.upsamplers.0.conv", B, side, side, c)
+                nxt, sh, sw = self._upconv(h, f"up_blocks.{ui}.upsamplers.0.conv", B, sh, sw, c)
                 ar.release(h)
                 h = nxt
-        n = ar.alloc((B, side, side, ch[0]))
-        em.groupnorm(h, n, w["conv_norm_out.weight"], w["conv_norm_out.bias"], B=B, HW=side * side, C_=ch[0],
+        n = ar.alloc((B, sh, sw, ch[0]))
+        em.groupnorm(h, n, w["conv_norm_out.weight"], w["conv_norm_out.bias"], B=B, HW=sh * sw, C_=ch[0],
                      eps=1e-5, silu=True, groups=cfg.norm_groups)
         ar.release(h)
-        o, _, _ = self._conv(n, "conv_out", B, side, side, ch[0], cfg.out_channels)
+        o, _, _ = self._conv(n, "conv_out", B, sh, sw, ch[0], cfg.out_channels)
         ar.release(n)
-        api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.eps.data_ptr(), B, cfg.out_channels, L * L,
+        api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.eps.data_ptr(), B, cfg.out_channels, self.H * self.W,
                                 _pad(cfg.out_channels, 4), _stream())
         ar.release(o)
 
@@ -539,7 +548,7 @@ class UNetProgram:
         self.prog_cond.launch()
 
     def forward(self, x_in: torch.Tensor, tvals: torch.Tensor) -> torch.Tensor:
-        """x_in [B,4,L,L] fp16 (already scaled), tvals [B] -> eps [B,4,L,L] fp16 (program-owned buffer)."""
+        """x_in [B,4,H,W] fp16 (already scaled), tvals [B] -> eps [B,4,H,W] fp16 (program-owned buffer)."""
         self.x_in.copy_(x_in)
         self.tvals.copy_(tvals.reshape(-1, 1).to(F32))
         self.prog_step.launch()

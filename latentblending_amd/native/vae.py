@@ -27,6 +27,7 @@ import torch
 
 from ..hip import lib
 from ..hip.lib import api
+from .geometry import latent_hw
 from .runtime import Arena, Emitter, Program, F16, F32, _stream
 from .unet import _pad
 
@@ -130,25 +131,32 @@ class NativeVAEDecoder:
         for key in [k for k in self.w if k.endswith(".bias")]:          # biases in stream units (x 2^-4, exact)
             self.w[key + "_s"] = self.w[key] * STREAM_SCALE
 
-    def build(self, B: int, L: int) -> "VAEProgram":
-        return VAEProgram(self, B, L)
+    def build(self, B: int, L, ragged_halo: bool = True) -> "VAEProgram":
+        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``)."""
+        return VAEProgram(self, B, L, ragged_halo=ragged_halo)
 
 
 class VAEProgram:
-    def __init__(self, net: NativeVAEDecoder, B: int, L: int):
+    """One recorded decode for a fixed (batch, latent size): ``L`` = a side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for
+    square programs (else None).  ``ragged_halo`` as in ``UNetProgram``."""
+
+    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True):
         cfg = net.cfg
-        self.net, self.B, self.L = net, B, L
+        H, W = latent_hw(L)
+        self.net, self.B, self.H, self.W = net, B, H, W
+        self.L = H if H == W else None
         self.scaled = bool(cfg.stream_fp16_scaled)
         self.fuse_gn_stats = bool(getattr(cfg, "fuse_gn_stats", True))
         self.fused_mid_attention = bool(getattr(cfg, "fused_mid_attention", True))
         dev = net.device
         self.arena = Arena(dev)
         self.em = Emitter(self.arena)
-        S = L * cfg.scale_factor
-        self.z_in = torch.zeros(B, cfg.latent_channels, L, L, dtype=F16, device=dev)
-        self.frames = torch.zeros(B, S, S, 3, dtype=torch.uint8, device=dev)
-        self.image_f32 = torch.zeros(B, S, S, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
-        self._pq = torch.zeros(B, L, L, _pad(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
+        self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
+        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
+        self.image_f32 = torch.zeros(B, SH, SW, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
+        self._pq = torch.zeros(B, H, W, _pad(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
         self.prog = Program("vae-decode")
         with self.prog.record():
             self._emit()
@@ -264,64 +272,64 @@ class VAEProgram:
         return h
 
     def _emit(self):
-        net, cfg, em, w, ar, B, L = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B, self.L
+        net, cfg, em, w, ar, B, LH, LW = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B, self.H, self.W
         sc = self.scaled
         rev = list(reversed(cfg.block_channels))
         top, lc = rev[0], cfg.latent_channels
         lc_p = _pad(lc, 8)
-        z8 = ar.alloc((B, L, L, lc_p))
-        api.lb_nchw_to_nhwc_f16(self.z_in.data_ptr(), z8.data_ptr(), B, lc, L * L, lc_p, 1.0 / cfg.scaling_factor,
+        z8 = ar.alloc((B, LH, LW, lc_p))
+        api.lb_nchw_to_nhwc_f16(self.z_in.data_ptr(), z8.data_ptr(), B, lc, LH * LW, lc_p, 1.0 / cfg.scaling_factor,
                                 _stream())
         # post_quant_conv (1x1) writes the first `lc` channels of a zero-padded buffer
-        em.gemm(z8, w["post_quant_conv.weight"], self._pq, M=B * L * L, bias=w["post_quant_conv.bias"], ldc=lc_p)
+        em.gemm(z8, w["post_quant_conv.weight"], self._pq, M=B * LH * LW, bias=w["post_quant_conv.bias"], ldc=lc_p)
         ar.release(z8)
-        h = self._stream_conv(self._pq, "decoder.conv_in", B, L, L, lc, top)
-        nxt = self._resnet(h, "decoder.mid_block.resnets.0", B, L, L, top, top); ar.release(h); h = nxt
-        h = self._mid_attention(h, B, L, L, top)
-        nxt = self._resnet(h, "decoder.mid_block.resnets.1", B, L, L, top, top); ar.release(h); h = nxt
-        side, prev = L, top
+        h = self._stream_conv(self._pq, "decoder.conv_in", B, LH, LW, lc, top)
+        nxt = self._resnet(h, "decoder.mid_block.resnets.0", B, LH, LW, top, top); ar.release(h); h = nxt
+        h = self._mid_attention(h, B, LH, LW, top)
+        nxt = self._resnet(h, "decoder.mid_block.resnets.1", B, LH, LW, top, top); ar.release(h); h = nxt
+        sh, sw, prev = LH, LW, top                              # the current level's map is sh x sw
         for ui, c in enumerate(rev):
             for li in range(cfg.layers_per_block + 1):
-                nxt = self._resnet(h, f"decoder.up_blocks.{ui}.resnets.{li}", B, side, side, prev, c)
+                nxt = self._resnet(h, f"decoder.up_blocks.{ui}.resnets.{li}", B, sh, sw, prev, c)
                 ar.release(h); h = nxt
                 prev = c
             if ui < len(rev) - 1:
-                h16, owned = self._stream_as_operand(h, B, side, side, c)
+                h16, owned = self._stream_as_operand(h, B, sh, sw, c)
                 name = f"decoder.up_blocks.{ui}.upsamplers.0.conv"
-                up = ar.alloc((B, 2 * side, 2 * side, c), F16 if sc else F32)
-                one = em.upconv_one_launch(B, side, side, c, c)
+                up = ar.alloc((B, 2 * sh, 2 * sw, c), F16 if sc else F32)
+                one = em.upconv_one_launch(B, sh, sw, c, c)
                 if one:                     # all four sub-pixel convs in ONE launch of the halo kernel
-                    em.gemm(h16, w[f"{name}.weight.sub4"][0], up, M=B * side * side,
+                    em.gemm(h16, w[f"{name}.weight.sub4"][0], up, M=B * sh * sw,
                             bias=w[name + (".bias_s" if sc else ".bias")], ldc=c,
                             flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE,
-                            ch_stats=self._stats_for(up, B, side, side, c, c, ks=2),
-                            conv=dict(Hin=side, Win=side, Cin=c, Hout=side, Wout=side, KH=2, KW=2, stride=1, pad=0,
+                            ch_stats=self._stats_for(up, B, sh, sw, c, c, ks=2),
+                            conv=dict(Hin=sh, Win=sw, Cin=c, Hout=sh, Wout=sw, KH=2, KW=2, stride=1, pad=0,
                                       ups=0, ldx=c, parity="all"))
                 for py in (() if one else (0, 1)):           # else: four 2x2 convs on the low-res grid
                     for px in (0, 1):
-                        em.gemm(h16, w[f"{name}.weight.sub{py}{px}"], up, M=B * side * side,
+                        em.gemm(h16, w[f"{name}.weight.sub{py}{px}"], up, M=B * sh * sw,
                                 bias=w[name + (".bias_s" if sc else ".bias")], ldc=c,
                                 flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE,
-                                conv=dict(Hin=side, Win=side, Cin=c, Hout=side, Wout=side, KH=2, KW=2, stride=1, pad=0,
+                                conv=dict(Hin=sh, Win=sw, Cin=c, Hout=sh, Wout=sw, KH=2, KW=2, stride=1, pad=0,
                                           ups=0, ldx=c, parity=(py, px)))
                 if owned:
                     ar.release(h16)
                 ar.release(h)
                 h = up
-                side *= 2
-        n = ar.alloc((B, side, side, rev[-1]))
-        self._gn(h, n, "decoder.conv_norm_out", B, side * side, rev[-1], True)
+                sh, sw = 2 * sh, 2 * sw
+        n = ar.alloc((B, sh, sw, rev[-1]))
+        self._gn(h, n, "decoder.conv_norm_out", B, sh * sw, rev[-1], True)
         ar.release(h)
         cin_p = _pad(rev[-1], 8)
-        em.gemm(n, w["decoder.conv_out.weight"], self.image_f32, M=B * side * side, bias=w["decoder.conv_out.bias"],
+        em.gemm(n, w["decoder.conv_out.weight"], self.image_f32, M=B * sh * sw, bias=w["decoder.conv_out.bias"],
                 flags=lib.GEMM_OUT_F32,
-                conv=dict(Hin=side, Win=side, Cin=cin_p, Hout=side, Wout=side, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p))
+                conv=dict(Hin=sh, Win=sw, Cin=cin_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p))
         ar.release(n)
-        api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * side * side,
+        api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw,
                               _pad(cfg.out_channels, 4), 1, _stream())
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """z [B,4,L,L] fp16 final latents (NOT yet divided by the scaling factor) -> uint8 [B,8L,8L,3]."""
+        """z [B,4,H,W] fp16 final latents (NOT yet divided by the scaling factor) -> uint8 [B,8H,8W,3]."""
         self.z_in.copy_(z)
         self.prog.launch()
         return self.frames
