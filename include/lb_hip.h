@@ -78,7 +78,17 @@ int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* o
  * guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t), -} - slot 0 = 0 makes lb_scale_model_input_f16 the identity, as
  * DDIM's scale_model_input is; slot 6 is the fp32 reciprocal the kernel MULTIPLIES by where diffusers divides a device tensor by a
  * 0-dim host tensor (the tensor library's true-division kernel multiplies by 1 / b for a host scalar b).  fp16 tensor arithmetic
- * rounded op by op like diffusers' (no fp32 upcast in DDIM).  eps as above. */
+ * rounded op by op like diffusers' (no fp32 upcast in DDIM).  eps as above.
+ *   `cfg` is a bit field: bit 0 = CFG; bit 1 = the DPM-Solver++ 2M step (Lu et al. 2022, algorithm 2; DDIM is that solver at
+ *   order 1); any other bit is refused ("cfg bits").  Before bit 1 existed every non-zero value meant CFG - that reading of 2
+ *   and 3 is gone; nothing ever passed them.  With bit 1 clear the launch is the DDIM step above, unchanged.
+ *   With bit 1 set `x` and `out` are two-plane buffers [2][batch][per_sample] (fp16): plane 0 of `x` the latent, plane 1 the
+ *   previous step's x0 prediction m1; plane 0 of `out` the next latent, plane 1 this step's x0 prediction m0.  The kernel keeps
+ *   no state: feed `out` of step i as `x` of step i + 1.  `x` and `out` must NOT overlap (not checked).  params_dev rows are
+ *   {0, sigma_s, ratio, guidance, c0, c1, 1 / alpha_s, 1 / r0}; every tensor operation rounds to fp16 (CFG combine first) -
+ *     m0 = (x - sigma_s eps) (1 / alpha_s);  y = ratio x - c0 m0;  if c1 != 0: y = y - c1 ((1 / r0) (m0 - m1))
+ *   A row with c1 == 0 is a first-order row: plane 1 of `x` is not read for it (it may hold anything).  A schedule's last row
+ *   (ratio 0, c0 -1, c1 0) returns m0 bit for bit in both planes. */
 int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
                      int cfg, void* stream);
 

@@ -605,11 +605,113 @@ __global__ void __launch_bounds__(256) ddim_step_kernel(const f16* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// DPM-Solver++ 2M step (Lu et al. 2022, "DPM-Solver++", algorithm 2: multistep, order 2, data prediction; the midpoint form
+// diffusers' DPMSolverMultistepScheduler takes with algorithm_type "dpmsolver++", epsilon prediction, final sigma zero).
+// Bit 1 of lb_ddim_step_f16's `cfg` (DDIM is this solver at order 1; a dedicated symbol follows when the replay registry is
+// next opened).  `x` and `out` are TWO-PLANE buffers [2][batch][per_sample]: plane 0 of `x` the latent, plane 1 the previous
+// step's x0 prediction m1; plane 0 of `out` the next latent, plane 1 this step's x0 prediction m0.  The kernel keeps no state:
+// the caller feeds `out` of step i as `x` of step i + 1 (so `x` and `out` must not overlap - not checked).
+//   params row: {0 (sigma of lb_scale_model_input_f16: the identity), sigma_s, ratio, guidance, c0, c1, 1 / alpha_s, 1 / r0}
+//   with sigma_s = sigma alpha (the variance-preserving noise level), ratio = sigma_next / sigma_s, c0 = alpha_next expm1(-h),
+//   c1 = c0 / 2, r0 = h_prev / h.  fp16 tensors, fp32 row scalars, every tensor operation rounds to fp16 (CFG combine first) -
+//   m0 = (x - sigma_s * eps) * (1 / alpha_s)                         [mul, sub, mul: three]
+//   y  = ratio * x - c0 * m0                                         [mul, mul, sub: three]
+//   c1 != 0:  D1 = (1 / r0) * (m0 - m1);  y = y - c1 * D1            [sub, mul, mul, sub: four]
+// A row with c1 == 0 is a FIRST-ORDER row (the first step of a run, the last of a schedule): plane 1 of `x` is not read for it.
+// The last row of a schedule carries ratio 0 and c0 -1: 0 * x = 0 and 0 - (-m0) is exact, so it returns m0 bit for bit.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void dpmpp2m_one(f16 xh, f16 eu, f16 et, f16 m1, float sig, float ratio, float g, float c0, float c1,
+                                            float inv_alpha, float inv_r0, bool cfg, bool second, f16& y_out, f16& m0_out) {
+    // (the opaque register of ddim_one: no v_fma_mix fusion of "multiply, then round")
+    auto r16 = [](float v) {
+        asm volatile("" : "+v"(v));
+        return (f16)v;
+    };
+    f16 e = eu;
+    if (cfg) {
+        // fenced as well, unlike ddim_one's: the mids run under mid-dampened guidance, an arbitrary fp32 value whose product with
+        // an fp16 difference is not exact in fp32 - a fused multiply-and-round would round it once, a tensor library rounds twice
+        const f16 diff = r16(__fsub_rn((float)et, (float)eu));
+        const f16 sc = r16(__fmul_rn(g, (float)diff));
+        e = r16(__fadd_rn((float)eu, (float)sc));
+    }
+    const f16 t1 = r16(__fmul_rn(sig, (float)e));
+    const f16 t2 = r16(__fsub_rn((float)xh, (float)t1));
+    const f16 m0 = r16(__fmul_rn((float)t2, inv_alpha));
+    const f16 a = r16(__fmul_rn(ratio, (float)xh));
+    const f16 b = r16(__fmul_rn(c0, (float)m0));
+    f16 y = r16(__fsub_rn((float)a, (float)b));
+    if (second) {
+        const f16 dm = r16(__fsub_rn((float)m0, (float)m1));
+        const f16 d1 = r16(__fmul_rn(inv_r0, (float)dm));
+        const f16 c = r16(__fmul_rn(c1, (float)d1));
+        y = r16(__fsub_rn((float)y, (float)c));
+    }
+    y_out = y;
+    m0_out = m0;
+}
+
+template <bool VEC, bool CFG>
+__global__ void __launch_bounds__(256) dpmpp2m_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps, f16* __restrict__ out,
+                                                            const float* __restrict__ params, long per_sample, int batch) {
+    const long total = per_sample * batch;          // (also the plane stride of x and out)
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const float* row = params + (long)b * LB_STEP_STRIDE;
+        const float sig = row[1], ratio = row[2], g = row[3], c0 = row[4], c1 = row[5], inv_alpha = row[6], inv_r0 = row[7];
+        const bool second = c1 != 0.f;                // (uniform over the block: blockIdx.y is the sample)
+        const long base = (long)b * per_sample;
+        const long nvec = VEC ? per_sample >> 3 : 0;
+        const long stride = (long)gridDim.x * blockDim.x;
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+            const long o = base + i * 8;
+            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
+            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
+            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
+            const f16x8 mv = second ? *reinterpret_cast<const f16x8*>(x + total + o) : zero8;
+            f16x8 y, m;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                f16 yj, mj;
+                dpmpp2m_one(xv[j], eu[j], et[j], mv[j], sig, ratio, g, c0, c1, inv_alpha, inv_r0, CFG, second, yj, mj);
+                y[j] = yj;
+                m[j] = mj;
+            }
+            *reinterpret_cast<f16x8*>(out + o) = y;
+            *reinterpret_cast<f16x8*>(out + total + o) = m;
+        }
+        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
+            const long o = base + i;
+            f16 y, m;
+            dpmpp2m_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, second ? x[o + total] : (f16)0.f, sig, ratio, g, c0, c1,
+                        inv_alpha, inv_r0, CFG, second, y, m);
+            out[o] = y;
+            out[o + total] = m;
+        }
+    }
+}
+
+// `cfg`: bit 0 = classifier-free guidance (eps holds 2 * batch samples); bit 1 = the DPM-Solver++ 2M step above on two-plane
+// `x` / `out`.  With bit 1 clear this is the DDIM launch it always was.  Any other bit is refused (before bit 1 existed every
+// non-zero value meant CFG; nothing passed anything but 0 or 1).
 extern "C" int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
                                 int cfg, void* stream) {
     LB_REQUIRE(per_sample > 0 && batch > 0, "lb_ddim_step_f16: sizes");
-    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
+    LB_REQUIRE((cfg & ~3) == 0, "lb_ddim_step_f16: cfg bits (bit 0 CFG, bit 1 DPM-Solver++ 2M step on two-plane buffers)");
     const dim3 grid = sample_grid(per_sample, batch), block(256);
+    if (cfg & 2) {
+        // (the second plane starts per_sample * batch elements in: the vector form needs that offset to keep 16-byte alignment,
+        //  which per_sample % 8 == 0 gives)
+        const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
+        const int c = cfg & 1;
+#define LB_DPMPP(V, C) hipLaunchKernelGGL((dpmpp2m_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (f16*)out, params_dev, per_sample, batch)
+        LB_DISPATCH_STMT("lb_ddim_step_f16",
+                         if (vec && c) LB_DPMPP(true, true); else if (vec) LB_DPMPP(true, false);
+                         else if (c) LB_DPMPP(false, true); else LB_DPMPP(false, false));
+#undef LB_DPMPP
+    }
+    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
 #define LB_DDIM(V, C) hipLaunchKernelGGL((ddim_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (f16*)out, params_dev, per_sample, batch)
     LB_DISPATCH_STMT("lb_ddim_step_f16",
                      if (vec && cfg) LB_DDIM(true, true); else if (vec) LB_DDIM(true, false);

@@ -172,6 +172,34 @@ def ddim_step(x, eps, params, cfg=False) -> torch.Tensor:
     return out
 
 
+DDIM_CFG_DPMPP_2M = 2                                                 # bit 1 of the ``cfg`` argument of lb_ddim_step_f16
+
+
+def dpmpp2m_step(state, eps, params, cfg=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """DPM-Solver++ 2M step (bit 1 of ``cfg`` of ``lb_ddim_step_f16``); ``params`` rows as NativeDPMSolverPP2MScheduler.step_row
+    builds them.  ``state`` is ``[2, B, ...]`` fp16: plane 0 the latents, plane 1 the previous step's x0 prediction (not read for
+    a first-order row).  Returns the new state - next latents and this step's x0 prediction - in ``out``, which must not share
+    memory with ``state``; while a program records, the caller owns ``out``."""
+    if state.dim() < 3 or state.shape[0] != 2:
+        raise ValueError(f"dpmpp2m_step: state must have two planes, [2, B, ...] (got shape {tuple(state.shape)})")
+    assert state.dtype == F16 and eps.dtype == F16 and state.is_contiguous() and eps.is_contiguous(), \
+        "dpmpp2m_step: the kernel takes contiguous fp16 operands by pointer"
+    B = state.shape[1]
+    if eps.shape[0] != B * (2 if cfg else 1) or eps[0].numel() != state[0, 0].numel():
+        raise ValueError(f"dpmpp2m_step: eps of shape {tuple(eps.shape)} does not go with a state of shape {tuple(state.shape)} (cfg={bool(cfg)})")
+    if out is None:
+        _own_buffer("dpmpp2m_step", "out")
+        out = torch.empty_like(state)
+    if out.shape != state.shape or out.dtype != F16 or not out.is_contiguous():
+        raise ValueError(f"dpmpp2m_step: out must be a contiguous fp16 tensor of the state's shape, two planes (got {tuple(out.shape)})")
+    nbytes = state.numel() * state.element_size()
+    if out.data_ptr() < state.data_ptr() + nbytes and state.data_ptr() < out.data_ptr() + nbytes:
+        raise ValueError("dpmpp2m_step: out aliases state (the step reads plane 1 of state while it writes plane 1 of out)")
+    api.lb_ddim_step_f16(state.data_ptr(), eps.data_ptr(), out.data_ptr(), params.data_ptr(), state[0, 0].numel(), B,
+                         int(bool(cfg)) | DDIM_CFG_DPMPP_2M, stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------ GEMM / conv
 def pack_linear_weight(w: torch.Tensor) -> torch.Tensor:
     """[N, K] -> fp16 [N, K] contiguous (K padded to a multiple of 8 with zeros)."""

@@ -36,7 +36,8 @@ from ..hip.lib import api
 from .frames import DeviceImage
 from .geometry import program_key
 from .lpips import NativeLPIPS
-from .scheduler import NativeDDIMScheduler, NativeEulerScheduler, NativeLCMScheduler, noise_draws_per_run
+from .scheduler import (NativeDDIMScheduler, NativeDPMSolverPP2MScheduler, NativeEulerScheduler, NativeLCMScheduler,
+                        noise_draws_per_run)
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
 from .weights import SyntheticProvider
@@ -115,17 +116,20 @@ class StableDiffusionXLPipeline:
         DDIMScheduler (eta 0) behind the same native loops - also with ``turbo=True`` (the Turbo guidance / branching defaults
         stay, only the sampler changes: deterministic, "leading" spacing); "lcm" = the latent-consistency sampler (diffusers'
         LCMScheduler: few-step sampling of a distilled UNet or a merged LCM-LoRA, 1..50 steps, one noise draw per step but the
-        last), with ``turbo=True`` and ``False`` alike.  Case-insensitive; anything else raises ``ValueError``
+        last), with ``turbo=True`` and ``False`` alike; "dpmpp_2m" / "dpmpp_2m_karras" = DPM-Solver++ 2M (second-order multistep,
+        diffusers' DPMSolverMultistepScheduler with its dpmsolver++ / midpoint defaults) on uniform / Karras sigmas (commonly run at about
+        20 steps; at most 44 on Karras sigmas).  Case-insensitive; anything else raises ``ValueError``
         (a misspelt "DDIM " or a scheduler object used to fall through to Euler silently).
         ``allow_synthetic``: seeded synthetic stand-ins (UNet / VAE / LPIPS weights when no provider is given,
         prompt embeddings when no ``text_encoder_fn`` is given) are used silently when True (tests, bench: also
         ``LB_ALLOW_SYNTHETIC=1``); otherwise each stand-in announces itself ONCE with a ``UserWarning`` - frames
         rendered from them are noise-like and prompts have no semantic effect."""
         if scheduler is not None and not isinstance(scheduler, str):
-            raise ValueError(f"NativeSDXLPipe: scheduler must be None, 'euler', 'ddim' or 'lcm' (got an object of type {type(scheduler).__name__})")
+            raise ValueError(f"NativeSDXLPipe: scheduler must be None, 'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras' "
+                             f"(got an object of type {type(scheduler).__name__})")
         scheduler = None if scheduler is None else scheduler.strip().lower()
-        if scheduler not in (None, "euler", "ddim", "lcm"):
-            raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler', 'ddim' or 'lcm')")
+        if scheduler not in (None, "euler", "ddim", "lcm", "dpmpp_2m", "dpmpp_2m_karras"):
+            raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras')")
         if not torch.cuda.is_available():
             raise RuntimeError("NativeSDXLPipe needs an MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device(device)
@@ -151,6 +155,8 @@ class StableDiffusionXLPipeline:
         # (the reference's SDXL pipes carry Euler / Euler-ancestral schedulers; scheduler="ddim" = diffusers' DDIMScheduler, eta 0)
         if scheduler == "lcm":          # (diffusers' LCMScheduler: few-step sampling of distilled UNets / merged LCM-LoRAs)
             self.scheduler = NativeLCMScheduler(device=self.device)
+        elif scheduler in ("dpmpp_2m", "dpmpp_2m_karras"):
+            self.scheduler = NativeDPMSolverPP2MScheduler(use_karras_sigmas=scheduler.endswith("karras"), device=self.device)
         else:
             self.scheduler = NativeDDIMScheduler(device=self.device) if scheduler == "ddim" else NativeEulerScheduler(ancestral=turbo, device=self.device)
         self.unet = _UNetFacade(self)
@@ -231,6 +237,42 @@ class StableDiffusionXLPipeline:
         # (the LCM step may run without noise on the schedule's last step only: the loop says which step this is - the kernel's
         #  launcher never reads the device rows back)
         return {"last": i == steps - 1} if self.scheduler.kind == "lcm" else {}
+
+    def _step_row(self, i: int, guidance: float, first: bool):
+        """The scheduler's row of step ``i``; a multistep sampler is also told whether this is the FIRST step the sample executes (it
+        has no history then: the reference's loop calls ``set_timesteps`` at the start of every run, which empties it)."""
+        sched = self.scheduler
+        return sched.step_row(i, guidance, first=first) if getattr(sched, "multistep", False) else sched.step_row(i, guidance)
+
+    def _device_step(self, lat, hists, eps, params, noise, cfg: bool, i: int, steps: int, carry=None, mixed: bool = True):
+        """One batched scheduler step -> (latents, history, carry).  A single-step sampler has neither history nor carry (None).
+        A multistep one gets a two-plane state: plane 0 the latents - AFTER any crossfeed / parental mix, which touch the latents
+        only - and plane 1 the samples' previous x0 predictions.  ``carry`` is the state the previous call returned for the SAME
+        batch: the kernel's contract is that ``out`` of step i is ``x`` of step i + 1, so it goes straight back in (after one copy
+        of the latents into its plane 0 when they were ``mixed`` since) and nothing is allocated or gathered.  Without a carry
+        (first step; a wavefront batch that just changed its size) the state is assembled from ``lat`` and ``hists`` =
+        [(tensor or None, rows), ...] in batch order; a part without history (its rows are first-order rows) leaves its share of
+        plane 1 unwritten - the kernel does not read it.  The latents returned are a COPY of plane 0: the loops keep them in
+        trajectories, which must neither pin the x0-prediction plane nor see the carry's plane 0 overwritten by a later mix."""
+        sched = self.scheduler
+        if not getattr(sched, "multistep", False):
+            return sched.device_step(lat, eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, steps)), None, None
+        if carry is not None:
+            assert carry.shape[1:] == lat.shape
+            state = carry
+            if mixed:
+                state[0].copy_(lat)
+        else:
+            state = torch.empty((2,) + tuple(lat.shape), dtype=F16, device=lat.device)
+            state[0].copy_(lat)
+            at = 0
+            for h, rows in hists:
+                if h is not None and rows:
+                    state[1, at:at + rows].copy_(h)
+                at += rows
+            assert at == lat.shape[0]
+        out = sched.device_step(state, eps, params, cfg=cfg)
+        return out[0].clone(), out[1], out
 
     def to(self, *_a, **_k):
         return self
@@ -419,7 +461,7 @@ class StableDiffusionXLPipeline:
         trajs: List[List[Optional[torch.Tensor]]] = [[None] * idx_start for _ in range(G)]
         stream = torch.cuda.current_stream().cuda_stream
         # every step's scalar coefficients in ONE upload: [steps][G][8]
-        rows = [sched.step_row(i, float(guidance_scales[g])) for i in range(idx_start, num_inference_steps)
+        rows = [self._step_row(i, float(guidance_scales[g]), first=i == idx_start) for i in range(idx_start, num_inference_steps)
                 for g in range(G)]
         params_all = ops.step_params(rows, self.device).view(-1, G, 8) if rows else None
         # ancestral noise is drawn sample-major (all steps of branch 0, then branch 1, ...): the same
@@ -431,7 +473,9 @@ class StableDiffusionXLPipeline:
             n_draw, keep = (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
             drawn = sched.draw_noise_many(n_draw * nm, shape1, self.device).view(n_draw, nm, *shape1[1:])
             noise_all = drawn[keep].transpose(0, 1).contiguous()                             # [steps, G, 4, L, L]
+        hist = carry = None         # (a multistep sampler's previous x0 predictions / two-plane state; every run starts without)
         for i in range(idx_start, num_inference_steps):
+            mix = []
             if i > 0:
                 mix = [g for g in range(G) if coeffs_list[g][i] > 0]
                 if mix:
@@ -453,7 +497,8 @@ class StableDiffusionXLPipeline:
             self.stats["unet_forwards"] += 1
             self.stats["unet_samples"] += prog.B
             noise = noise_all[i - idx_start] if noise_all is not None and i - idx_start < nm else None
-            latents = sched.device_step(latents, prog.eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, num_inference_steps))
+            latents, hist, carry = self._device_step(latents, [(hist, G)], prog.eps, params, noise, cfg, i, num_inference_steps,
+                                                     carry=carry, mixed=bool(mix))
             for g in range(G):
                 trajs[g].append(latents[g:g + 1])
         return trajs
@@ -482,7 +527,11 @@ class StableDiffusionXLPipeline:
         are still consumed in the same order); the reference itself performs the dead forward, so the default is off.
         ``known_anchors[k]`` = a finished trajectory of anchor k (a recycled key frame, blending_engine.py:333-342 of the
         reference: ``recycle_img1`` after ``swap_forward``): that anchor is not denoised again - the small batches carry only
-        the other anchor, the mids mix from the stored latents - and is returned as given."""
+        the other anchor, the mids mix from the stored latents - and is returned as given.
+        Under a MULTISTEP sampler every sample carries its previous x0 prediction from step to step: when the batch grows at
+        ``idx_injection`` the anchors keep theirs and the mids enter without (first-order rows - the order is a property of the
+        row, so one launch serves the mixed batch).  A skipped step would leave no x0 prediction behind for the step after it, so
+        ``elide_dead_steps`` is ignored under such a sampler (with one warning per pipe)."""
         known = [None if t is None else list(t) for t in known_anchors]
         live = [k for k in (0, 1) if known[k] is None]          # anchors denoised here
         # ``mid_conds`` may be a CALLABLE returning the list (round 6): the mids' conditionings (two lerp launches each) are then built -
@@ -542,6 +591,12 @@ class StableDiffusionXLPipeline:
                 return prog, side.record_event()            # on `side` - the temporaries above never meet another stream)
 
         # G == 0: a farm rank that owns no mid branch of the round (fewer gaps than ranks) still runs both anchors
+        if elide_dead_steps and getattr(sched, "multistep", False):
+            if "elide-multistep" not in self._warned:
+                self._warned.add("elide-multistep")
+                warnings.warn(f"elide_dead_steps is ignored under the multistep sampler {sched.kind!r}: a skipped step leaves no x0 "
+                              f"prediction behind for the next step's second-order update", UserWarning, stacklevel=2)
+            elide_dead_steps = False
         dead = [bool(elide_dead_steps) and G > 0 and i >= idx_injection and i + 1 < steps and
                 all(float(mid_coeffs[g][i + 1]) == 1.0 for g in range(G)) for i in range(steps)]
         prog_a = prepared(list(anchor_conds), guid=all_g[:A])[0] if A and (idx_injection > 0 or G == 0 or any(dead)) else None
@@ -563,9 +618,9 @@ class StableDiffusionXLPipeline:
         else:
             prog_all = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds), guid=all_g)[0] if G else prog_a
         stream = torch.cuda.current_stream().cuda_stream
-        rows_a = [sched.step_row(i, all_g[0]) for i in range(steps)]
+        rows_a = [self._step_row(i, all_g[0], first=i == 0) for i in range(steps)]
         par_a = ops.step_params([r for r in rows_a for _ in range(A)], self.device).view(steps, A, 8) if A else None
-        par_all = ops.step_params([sched.step_row(i, all_g[s]) for i in range(idx_injection, steps)
+        par_all = ops.step_params([self._step_row(i, all_g[s], first=i == (0 if s < A else idx_injection)) for i in range(idx_injection, steps)
                                    for s in range(A + G)], self.device).view(-1, A + G, 8) if G else None
         shape1 = (1,) + tuple(ref_start.shape[1:])
         noise_a = noise_m = None
@@ -582,6 +637,7 @@ class StableDiffusionXLPipeline:
         lat_a = torch.cat([s.to(self.device, F16).reshape(1, -1, LH, LW) for s in anchor_starts]).contiguous() if A else \
             torch.empty((0,) + lat_shape, dtype=F16, device=self.device)
         lat_m = None
+        hist_a = hist_m = None      # (a multistep sampler's previous x0 predictions: the anchors' [A, ...] and the mids' [G, ...])
         traj_a = [[] if known[k] is None else [t.to(self.device, F16).reshape(1, -1, LH, LW) for t in known[k]] for k in (0, 1)]
         traj_m: List[List[Optional[torch.Tensor]]] = [[None] * idx_injection for _ in range(G)]
         # mixing fractions / crossfeed coefficients live on the device: every step's parental mix (ONE pair of anchor
@@ -606,6 +662,7 @@ class StableDiffusionXLPipeline:
                                 traj_m[g].append(None)
                         continue
                     prog, lat, params, n = prog_a, lat_a, par_a[i], A
+                    hists = [(hist_a, A)]
                     noise = noise_a[i] if noise_a is not None and i < nd_a else None
                 else:
                     prev1, prev2 = traj_a[0][i - 1].contiguous(), traj_a[1][i - 1].contiguous()
@@ -620,6 +677,7 @@ class StableDiffusionXLPipeline:
                         lat_m = ops.slerp_strided(lat_m.contiguous().view(G, n_lat), mix_prev, coef_dev[i], n_lat).view(G, *lat_shape)
                         self.stats["slerps"] += nfeed
                     prog, lat, params, n = prog_all, (torch.cat([lat_a, lat_m]) if A else lat_m.contiguous()), par_all[i - idx_injection], A + G
+                    hists = [(hist_a, A), (hist_m, G)]
                     if cond_ready is not None:
                         torch.cuda.current_stream().wait_event(cond_ready)
                         cond_ready = None
@@ -632,11 +690,13 @@ class StableDiffusionXLPipeline:
                 prog.prog_step.launch(stream)
                 self.stats["unet_forwards"] += 1
                 self.stats["unet_samples"] += prog.B
-                out = sched.device_step(lat, prog.eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, steps))
+                out, hist, _ = self._device_step(lat, hists, prog.eps, params, noise, cfg, i, steps)      # (the batch changes size: no carry)
                 if deferred:            # the first small step is launched: now the host work the big batch needs (runs beside it)
                     deferred = False
                     prog_all, cond_ready = prepared(lambda: list(anchor_conds) + list(mid_conds()), side=self._side_stream, after=before_first, guid=all_g)
                 lat_a = out[:A]
+                if hist is not None:
+                    hist_a, hist_m = hist[:A], (hist[A:] if n > A else hist_m)
                 for j, k in enumerate(live):
                     traj_a[k].append(out[j:j + 1])
                 if i >= idx_injection and G and dead[i]:

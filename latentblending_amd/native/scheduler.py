@@ -317,3 +317,145 @@ class NativeLCMScheduler:
         out = ops.lcm_step(sample.contiguous(), model_output.contiguous(), params, noise=noise)
         self._step_index += 1
         return (out,)
+
+
+KARRAS_RHO = 7.0
+
+
+def dpmpp_schedule(n: int, karras: bool, table: Optional[np.ndarray] = None):
+    """(sigmas [n + 1] with sigma_n = 0 appended, integer timesteps [n]) of an ``n``-step schedule, float64.  Karras: the ramp of
+    Karras et al. 2022, eq. 5 (rho = 7) from table[999] down to table[0], timesteps by linear interpolation in log sigma, rounded.
+    Otherwise the sigmas at Euler's "leading" timesteps with steps_offset 1.  Nothing is refused here: whether the timesteps can be
+    shown to a UNet (strictly decreasing) is ``set_timesteps``' business - the sigmas alone define the solver."""
+    table = _sigma_table() if table is None else table
+    if karras:
+        s_max, s_min = table[-1], table[0]
+        ramp = np.linspace(0.0, 1.0, n)
+        sig = (s_max ** (1 / KARRAS_RHO) + ramp * (s_min ** (1 / KARRAS_RHO) - s_max ** (1 / KARRAS_RHO))) ** KARRAS_RHO
+        sig[0] = s_max                      # (the ramp's ends are the table's ends exactly, not to a rounding of the 7th power)
+        if n > 1:
+            sig[-1] = s_min
+        ts = np.round(np.interp(np.log(sig), np.log(table), np.arange(NUM_TRAIN_TIMESTEPS, dtype=np.float64)))
+    else:
+        ts = (np.arange(0, n) * (NUM_TRAIN_TIMESTEPS // n)).round()[::-1].copy().astype(np.float64) + 1      # leading, steps_offset = 1
+        sig = np.interp(ts, np.arange(0, NUM_TRAIN_TIMESTEPS), table)
+    return np.concatenate([sig, [0.0]]), ts
+
+
+def dpmpp_2m_row(sigmas: np.ndarray, i: int, guidance: float = 0.0, first: bool = False):
+    """(0, sigma'_i, ratio, guidance, c0, c1, 1 / alpha_i, 1 / r0) of step ``i`` over ``sigmas`` (float64, 0 appended), in float64 -
+    rounded once to fp32 on upload.  Variance-preserving form of the table: alpha = 1 / sqrt(sigma^2 + 1), sigma' = sigma alpha,
+    lambda = log(alpha / sigma') = -log(sigma); with h = lambda_{i+1} - lambda_i: ratio = sigma'_{i+1} / sigma'_i,
+    c0 = alpha_{i+1} expm1(-h), c1 = c0 / 2, r0 = (lambda_i - lambda_{i-1}) / h.  A FIRST-ORDER row has c1 = 0 (which is how the
+    kernel knows to leave the previous x0 prediction unread): ``first``, step 0, and the step onto sigma = 0, whose row is
+    ratio 0, c0 -1 - the x0 prediction itself."""
+    sig_i, sig_n = float(sigmas[i]), float(sigmas[i + 1])
+    a_i, a_n = 1.0 / (sig_i ** 2 + 1.0) ** 0.5, 1.0 / (sig_n ** 2 + 1.0) ** 0.5
+    s_i, s_n = sig_i * a_i, sig_n * a_n
+    if sig_n == 0.0:
+        return (0.0, s_i, 0.0, guidance, -1.0, 0.0, 1.0 / a_i, 0.0)
+    h = float(np.log(sig_i) - np.log(sig_n))
+    c0 = a_n * float(np.expm1(-h))
+    if first or i == 0:
+        return (0.0, s_i, s_n / s_i, guidance, c0, 0.0, 1.0 / a_i, 0.0)
+    r0 = float(np.log(sigmas[i - 1]) - np.log(sig_i)) / h
+    return (0.0, s_i, s_n / s_i, guidance, c0, 0.5 * c0, 1.0 / a_i, 1.0 / r0)
+
+
+class NativeDPMSolverPP2MScheduler:
+    """DPM-Solver++ 2M (Lu et al. 2022, "DPM-Solver++", algorithm 2: second-order multistep, data prediction) in the form diffusers'
+    ``DPMSolverMultistepScheduler`` takes with algorithm_type "dpmsolver++", solver_type "midpoint", final_sigmas_type "zero" and
+    epsilon prediction, over uniform ("leading", steps_offset 1) or Karras (Karras et al. 2022, eq. 5, rho = 7) sigmas - what user
+    interfaces call "DPM++ 2M" / "DPM++ 2M Karras".  Restated from the paper and that class's documented behaviour - not checked
+    against diffusers itself.  Host side = the float64 sigma table (``_sigma_table``, as for Euler), the schedule and the per-step
+    coefficients, each rounded ONCE to fp32 on upload; the tensor work is bit 1 of ``cfg`` of ``lb_ddim_step_f16``.  Same interface
+    as :class:`NativeDDIMScheduler`, except that the sampler has a history: ``device_step`` takes and returns a two-plane state
+    (latents, previous x0 prediction), and ``step_row`` takes ``first`` - the first step a sample executes has no history and is
+    first order, like the schedule's last step (whose target sigma is 0).  The reference's restartable loop calls
+    ``set_timesteps`` at the start of every run, which empties a multistep scheduler's history: a branch entering at
+    ``idx_start > 0`` starts first order too."""
+    order = 1                    # model evaluations per step (as diffusers reports it; the engine's loops read this)
+    solver_order = 2
+    kind = "dpmpp_2m"
+    multistep = True
+    ancestral = False
+    init_noise_sigma = 1.0
+
+    def __init__(self, use_karras_sigmas: bool = False, device="cuda"):
+        self.use_karras_sigmas = bool(use_karras_sigmas)
+        self.device = device
+        self._table = _sigma_table()
+        self.noise_source = None
+        self._step_index = None
+        self._m1 = None
+        self.set_timesteps(20)
+
+    # ---- tables -----------------------------------------------------------------------------
+    def _schedule(self, n: int):
+        return dpmpp_schedule(n, self.use_karras_sigmas, self._table)
+
+    @staticmethod
+    def _valid(ts) -> bool:
+        # (strictly decreasing, inside the training range: Euler's "leading" formula puts the first of 1000 steps at t = 1000)
+        return bool(np.all(np.diff(ts) < 0)) and 0 <= ts[-1] and ts[0] <= NUM_TRAIN_TIMESTEPS - 1
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n = int(num_inference_steps)
+        if n < 1:
+            raise ValueError(f"NativeDPMSolverPP2MScheduler: num_inference_steps must be at least 1 (got {n})")
+        sig, ts = self._schedule(n)
+        if not self._valid(ts):
+            best = next(m for m in range(min(n, NUM_TRAIN_TIMESTEPS) - 1, 0, -1) if self._valid(self._schedule(m)[1]))
+            raise ValueError(f"NativeDPMSolverPP2MScheduler: the timesteps of a {n}-step schedule are not strictly decreasing "
+                             f"inside 0..{NUM_TRAIN_TIMESTEPS - 1} (the UNet would see one timestep twice, or one it was never trained on); the largest valid step count here is {best}")
+        self.sigmas_np = sig                                                # float64 [n + 1]; sigma_n = 0
+        self.timesteps_np = ts.astype(np.float32)
+        self.timesteps = torch.from_numpy(self.timesteps_np)
+        self.sigmas = torch.from_numpy(self.sigmas_np.astype(np.float32))
+        self.num_inference_steps = n
+        self._step_index = None
+        self._m1 = None
+
+    def index_of(self, t) -> int:
+        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
+
+    def noise_draws(self, steps: int, idx_start: int) -> int:
+        return 0
+
+    def is_last(self, i: int) -> bool:
+        return i == self.num_inference_steps - 1
+
+    def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
+        """The row of step ``i`` (``dpmpp_2m_row`` over this schedule's sigmas).  ``first`` = the sample has no history at this
+        step - the first step it executes: a first-order row."""
+        return dpmpp_2m_row(self.sigmas_np, i, guidance, first)
+
+    # ---- diffusers-style tensor API (generic holder loop / foreign callers) ------------------
+    def _locate(self, t) -> int:
+        if self._step_index is None:
+            self._step_index = self.index_of(float(t))
+        return self._step_index
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
+    def draw_noise(self, shape, device) -> torch.Tensor:        # (never used: the solver is deterministic)
+        return torch.zeros(shape, device=device, dtype=torch.float16)
+
+    def device_step(self, state, eps, params, noise=None, cfg=False, out=None):
+        """The batched step of the native loops: ``state`` [2, B, ...] (latents, previous x0 prediction) -> the next state."""
+        return ops.dpmpp2m_step(state, eps, params, cfg=cfg, out=out)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
+        """One step with the history kept HERE (``_m1``, the previous call's x0 prediction; ``set_timesteps`` drops it)."""
+        i = self._locate(timestep)
+        first = self._m1 is None
+        params = ops.step_params([self.step_row(i, first=first)] * sample.shape[0], sample.device)
+        state = torch.empty((2,) + tuple(sample.shape), dtype=torch.float16, device=sample.device)
+        state[0].copy_(sample)
+        if not first:
+            state[1].copy_(self._m1)
+        out = ops.dpmpp2m_step(state, model_output.contiguous(), params)
+        self._m1 = out[1]
+        self._step_index += 1
+        return (out[0],)
