@@ -114,6 +114,14 @@ enum {
                               * ceiling division, the tile shape is the one that covers the image with fewer tile pixels (ties: 32 x 8),
                               * pixels of an overhanging tile outside the image are neither stored nor counted into LB_GEMM_CH_STATS.
                               * A shape that divides runs exactly what it runs without the flag; every other launcher ignores the bit. */
+    LB_GEMM_C64 = 2048,      /* opt-in routing bit of lb_gemm_f16 (lb_gemm_plan: tile code 12; recorded as "conv3x3_c64"): the 64 -> 64 channel
+                              * 3x3 conv with the layer's whole weight matrix resident in LDS (conv3_c64.hip).  Needs conv = 1, KH = KW = 3,
+                              * stride 1, pad 1, scatter 0, Cin = N = 64, K = 576, ldx / ldw multiples of 8, ldc a multiple of 4, zero_page,
+                              * ups 0 or 1 with Hout = Hin << ups and Wout = Win << ups (any size >= 1 x 1: ragged edge tiles are masked), fp16
+                              * in and out; bias, fp16 residual, alpha and LB_GEMM_RELU are allowed, every other flag, rowvec and partial are
+                              * refused.  A flagged problem runs there or fails with a message naming the violated condition - it never takes
+                              * another route; lb_gemm_ch_stat_rows is 0 and lb_conv_halo_plan's kind is 0 for it.  The direct entry points
+                              * (lb_conv3x3_halo_f16, lb_conv3x3_narrow_f16, lb_upconv2x_halo_f16) ignore the bit. */
     LB_GEMM_LN_A = 64        /* A is consumed through a LayerNorm over its K columns (K = the normalised width):
                                 C = LN(A) . Wt computed as rstd_m * (A . W'^T - mean_m * colsum) + bias with
                                 W' = W * gamma (folded by the caller), ln_colsum[n] = sum_k W'[n][k],

@@ -513,6 +513,7 @@ int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream) {
 extern int g_lb_wide_store, g_lb_lean_epilogue;
 extern "C" int lb_upconv2x_halo_f16(const LbGemmParams* pp, void* stream) {
     LbGemmParams p = *pp;
+    p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_upconv2x_halo_f16: empty problem");
     LB_REQUIRE(lb_upconv_halo_eligible(p) != 0,
@@ -564,6 +565,7 @@ int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
 
 extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
     LbGemmParams p = *pp;
+    p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_conv3x3_halo_f16: empty problem");
     LB_REQUIRE(lb_conv3x3_halo_eligible(p) != 0,
@@ -579,7 +581,8 @@ extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
 extern "C" void lb_conv_halo_plan(const LbGemmParams* pp, int* kind, int* tile_w, long* items, long* grid) {
     LbGemmParams p = *pp;
     int k = 0, tw = 0;
-    if ((tw = lb_upconv_halo_eligible(p)) != 0) k = 2;
+    if (p.flags & LB_GEMM_C64) tw = 0;              // (lb_gemm_f16 takes a flagged problem to conv3_c64.hip: not a halo launch)
+    else if ((tw = lb_upconv_halo_eligible(p)) != 0) k = 2;
     else if ((tw = lb_conv3x3_halo_eligible(p)) != 0) k = 3;
     long it = 0, gr = 0;
     if (k) halo_grid(p, tw, k, it, gr);

@@ -149,6 +149,7 @@ int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream) {     // (trust
 
 extern "C" int lb_conv3x3_narrow_f16(const LbGemmParams* pp, void* stream) {
     LbGemmParams p = *pp;
+    p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_conv3x3_narrow_f16: empty problem");
     LB_REQUIRE(lb_conv3x3_narrow_eligible(p) != 0,
                "lb_conv3x3_narrow_f16: needs a 3x3 / stride 1 / pad 1 conv, N <= 16, Cin % 64 == 0, H and W multiples of 16, bias-only epilogue");

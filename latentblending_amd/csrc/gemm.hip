@@ -348,6 +348,10 @@ int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream);
 int lb_upconv_halo_eligible(const LbGemmParams& p);
 int lb_upconv_halo_check(const LbGemmParams& p);
 int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream);
+// LB_GEMM_C64 (conv3_c64.hip): opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights; tile code 12.  Flagged problems go there or are refused.
+int lb_conv3_c64_check(const LbGemmParams& p);
+int lb_conv3_c64_launch(LbGemmParams p, hipStream_t stream);
+void lb_conv3_c64_grid(const LbGemmParams& p, long& items, long& grid);
 #define LB_HALO_MIN_BLOCKS 96
 static int g_halo = 1;
 extern "C" void lb_gemm_set_halo(int mode) { g_halo = mode; }
@@ -545,7 +549,13 @@ extern "C" int lb_gemm_plan(const LbGemmParams* pp, int* tile, int* splitk, long
     LB_REQUIRE(pp != nullptr && pp->M > 0 && pp->N > 0 && pp->K > 0, "lb_gemm_plan: empty problem");
     int t = 0, sk = 1;
     long nb = 0;
-    if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(*pp)) { t = 8; nb = (long)pp->M / 256; }   // tile code 8 = narrow-N conv kernel
+    if (pp->flags & LB_GEMM_C64) {                  // tile code 12 = 64-channel conv with resident weights; blocks = its persistent grid
+        if (const int rc = lb_conv3_c64_check(*pp)) return rc;
+        long items = 0;
+        t = 12;
+        lb_conv3_c64_grid(*pp, items, nb);
+    }
+    else if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(*pp)) { t = 8; nb = (long)pp->M / 256; }   // tile code 8 = narrow-N conv kernel
     else if (use_halo(*pp)) { t = 6; nb = lb_conv3x3_halo_blocks(*pp); }     // tile code 6 = halo-tile conv kernel
     else gemm_plan(*pp, t, sk, nb);
     if (tile) *tile = t;
@@ -558,6 +568,7 @@ extern "C" int lb_gemm_plan(const LbGemmParams* pp, int* tile, int* splitk, long
 long lb_conv_halo_stat_rows_total(const LbGemmParams& p);
 extern "C" int lb_gemm_ch_stat_rows(const LbGemmParams* pp) {
     if (pp == nullptr || !pp->conv || pp->M <= 0 || pp->Hout <= 0 || pp->Wout <= 0) return 0;
+    if (pp->flags & LB_GEMM_C64) return 0;          // (not a halo-tile launch: no statistics)
     const LbGemmParams& p = *pp;
     bool halo;
     if (p.scatter == 2) halo = lb_upconv_halo_eligible(p) != 0;
@@ -592,6 +603,10 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     }
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
+    if (p.flags & LB_GEMM_C64) {                    // opt-in: this kernel or a refusal, never another route
+        if (const int rc = lb_conv3_c64_check(p)) return rc;
+        LB_DISPATCH("conv3x3_c64", lb_conv3_c64_launch(p, s));
+    }
     if (p.scatter == 2) {       // all four sub-pixel parities in one launch: only the halo kernel implements it
         LB_REQUIRE(lb_upconv_halo_eligible(p) != 0, "lb_gemm_f16: scatter = 2 needs Cin % 64 == 0, W % 16 == 0, stacked [4][N][K] weights");
         if (const int rc = lb_upconv_halo_check(p)) return rc;

@@ -73,14 +73,17 @@ class BlendingVariableHolder:
         self.idx_img_movie_selected = _index_of(data)
 
     # ---- previews (gradio_ui.py:141-161): nmb_preview_images renders of ONE prompt under random seeds ----
-    def compute_imgs(self, prompt, negative_prompt):
+    def compute_imgs(self, prompt, negative_prompt, decoder: Optional[str] = None):
+        """``decoder``: "full" / "tiny" = the native pipe's ``decoder`` for these previews (None: as the pipe stands); the previous
+        value is restored afterwards."""
         from PIL import Image
+        from .replay import _decoder_as
         self.prompt = prompt
         self.negative_prompt = negative_prompt
         self.list_seeds = []
         self.list_images_preview = []
         self.idx_img_preview_selected = None
-        with self.session.bound() as be:
+        with self.session.bound() as be, _decoder_as(be, decoder):
             be.set_prompt1(prompt)
             be.set_prompt2(prompt)
             be.set_negative_prompt(negative_prompt)

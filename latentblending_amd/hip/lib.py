@@ -48,6 +48,7 @@ class LbAttnParams(C.Structure):
 GEMM_OUT_F32, GEMM_RES_F32, GEMM_GEGLU, GEMM_TRANS_OUT, GEMM_SILU, GEMM_RELU, GEMM_LN_A = 1, 2, 4, 8, 16, 32, 64
 GEMM_QUICK_GELU, GEMM_GELU, GEMM_CH_STATS = 128, 256, 512
 GEMM_HALO_RAGGED = 1024      # opt-in ragged tiles of the 3x3 halo conv (include/lb_hip.h)
+GEMM_C64 = 2048              # opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights: that kernel or a refusal (include/lb_hip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 

@@ -39,6 +39,7 @@ from .lpips import NativeLPIPS
 from .scheduler import (NativeDDIMScheduler, NativeDPMSolverPP2MScheduler, NativeEulerScheduler, NativeLCMScheduler,
                         noise_draws_per_run)
 from .unet import NativeUNet, UNetConfig, UNetProgram
+from .tiny_vae import NativeTinyVAEDecoder, TinyVAEConfig, TinyVAEProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
 from .weights import SyntheticProvider
 
@@ -76,15 +77,18 @@ class _UNetFacade:
 class _VAEFacade:
     def __init__(self, pipe):
         self._pipe = pipe
-        c = pipe.vae_cfg
         self.dtype = F16
-        self.config = SimpleNamespace(force_upcast=False, scaling_factor=c.scaling_factor)
         self.post_quant_conv = SimpleNamespace(parameters=lambda: iter([torch.zeros(1, dtype=F16)]))
+
+    @property
+    def config(self):
+        """Of the pipe's ACTIVE decoder: the tiny decoder takes the latents as they are (scaling_factor 1.0)."""
+        return SimpleNamespace(force_upcast=False, scaling_factor=self._pipe.active_vae_cfg.scaling_factor)
 
     def decode(self, z, return_dict=False):
         """z = latents / scaling_factor -> float image [B,3,H,W] (diffusers convention)."""
         prog = self._pipe.vae_program(z.shape[0], (z.shape[-2], z.shape[-1]))
-        prog.decode((z.float() * self._pipe.vae_cfg.scaling_factor).to(F16))
+        prog.decode((z.float() * self._pipe.active_vae_cfg.scaling_factor).to(F16))
         return (prog.image_f32[..., :3].permute(0, 3, 1, 2).clone(),)
 
     def to(self, *a, **k):
@@ -111,8 +115,14 @@ class StableDiffusionXLPipeline:
                  lpips_provider=None, device="cuda", seed: int = 0, name_or_path: Optional[str] = None,
                  text_encoder_fn=None, unet_native: Optional[NativeUNet] = None,
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
-                 scheduler: Optional[str] = None):
-        """``scheduler``: None or "euler" = the reference pipes' choice (Euler-ancestral for Turbo, Euler for base); "ddim" = diffusers'
+                 scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
+                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None):
+        """``decoder``: "full" (default) = the SDXL ``AutoencoderKL`` decoder; "tiny" = the TAESDXL tiny decoder (``native/tiny_vae.py``:
+        a speed / preview option - a distilled approximation, its LPIPS tree is computed on its own frames).  Case-insensitive,
+        anything else raises ``ValueError``; ``pipe.decoder`` switches it afterwards (preview tiny, render full).  The tiny network
+        is built on first use from ``tiny_vae_native`` / ``tiny_vae_provider`` (``native.from_safetensors(<dir>/taesdxl)``), else
+        from the seeded synthetic stand-in (announced like the others).
+        ``scheduler``: None or "euler" = the reference pipes' choice (Euler-ancestral for Turbo, Euler for base); "ddim" = diffusers'
         DDIMScheduler (eta 0) behind the same native loops - also with ``turbo=True`` (the Turbo guidance / branching defaults
         stay, only the sampler changes: deterministic, "leading" spacing); "lcm" = the latent-consistency sampler (diffusers'
         LCMScheduler: few-step sampling of a distilled UNet or a merged LCM-LoRA, 1..50 steps, one noise draw per step but the
@@ -130,6 +140,7 @@ class StableDiffusionXLPipeline:
         scheduler = None if scheduler is None else scheduler.strip().lower()
         if scheduler not in (None, "euler", "ddim", "lcm", "dpmpp_2m", "dpmpp_2m_karras"):
             raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras')")
+        self._decoder = self._check_decoder(decoder)
         if not torch.cuda.is_available():
             raise RuntimeError("NativeSDXLPipe needs an MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device(device)
@@ -152,6 +163,8 @@ class StableDiffusionXLPipeline:
         self.unet_native = unet_native or NativeUNet(self.unet_cfg, unet_provider or SyntheticProvider(seed), self.device)
         self.vae_native = vae_native or NativeVAEDecoder(self.vae_cfg, vae_provider or SyntheticProvider(seed + 1), self.device)
         self.lpips_metric = NativeLPIPS(lpips_provider or SyntheticProvider(7), self.device)
+        self.tiny_vae_native, self._tiny_vae_provider, self._tiny_seed = tiny_vae_native, tiny_vae_provider, seed + 2
+        self.tiny_vae_cfg = tiny_vae_native.cfg if tiny_vae_native is not None else TinyVAEConfig()
         # (the reference's SDXL pipes carry Euler / Euler-ancestral schedulers; scheduler="ddim" = diffusers' DDIMScheduler, eta 0)
         if scheduler == "lcm":          # (diffusers' LCMScheduler: few-step sampling of distilled UNets / merged LCM-LoRAs)
             self.scheduler = NativeLCMScheduler(device=self.device)
@@ -177,6 +190,11 @@ class StableDiffusionXLPipeline:
         # caches are LRU-bounded: speculative rounds of varying width must not pile up SDXL-sized arenas
         self._unet_programs: "OrderedDict[Tuple[int, ...], UNetProgram]" = OrderedDict()
         self._vae_programs: "OrderedDict[Tuple[int, ...], VAEProgram]" = OrderedDict()
+        self._tiny_vae_programs: "OrderedDict[Tuple[int, ...], TinyVAEProgram]" = OrderedDict()     # (decoder="tiny": same bound)
+        # the tiny decoder's 64 -> 64 convs ask for the LDS-resident-weights kernel (LB_GEMM_C64) where tiny_vae.use_c64 says so;
+        # False = the library's own routing everywhere (A/B runs, tests).  Read when a program is BUILT: the setter drops the
+        # cached tiny programs.
+        self._tiny_conv_c64 = True
         # non-square programs send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo kernel
         # (geometry.use_ragged_halo); False = the implicit GEMM there (A/B runs, tests).  Read when a program is BUILT: the
         # setter drops the cached non-square programs.
@@ -373,6 +391,45 @@ class StableDiffusionXLPipeline:
                 for k in stale:
                     del cache[k]
 
+    @staticmethod
+    def _check_decoder(name) -> str:
+        if not isinstance(name, str) or name.strip().lower() not in ("full", "tiny"):
+            raise ValueError(f"NativeSDXLPipe: decoder must be 'full' or 'tiny' (got {name!r})")
+        return name.strip().lower()
+
+    @property
+    def decoder(self) -> str:
+        return self._decoder
+
+    @decoder.setter
+    def decoder(self, name: str):
+        self._decoder = self._check_decoder(name)
+
+    @property
+    def active_vae_cfg(self):
+        return self.tiny_vae_cfg if self._decoder == "tiny" else self.vae_cfg
+
+    @property
+    def tiny_conv_c64(self) -> bool:
+        return self._tiny_conv_c64
+
+    @tiny_conv_c64.setter
+    def tiny_conv_c64(self, flag: bool):
+        flag = bool(flag)
+        if flag != self._tiny_conv_c64:
+            self._tiny_conv_c64 = flag
+            if self._tiny_vae_programs:
+                torch.cuda.synchronize(self.device)
+            self._tiny_vae_programs.clear()
+
+    def _tiny_net(self) -> NativeTinyVAEDecoder:
+        if self.tiny_vae_native is None:
+            if self._tiny_vae_provider is None:
+                self._synthetic_notice("tiny VAE (TAESDXL) weights", "pass tiny_vae_provider=native.from_safetensors(<dir>/taesdxl)")
+            self.tiny_vae_native = NativeTinyVAEDecoder(self.tiny_vae_cfg, self._tiny_vae_provider or SyntheticProvider(self._tiny_seed),
+                                                        self.device)
+        return self.tiny_vae_native
+
     def unet_program(self, B: int, L) -> UNetProgram:
         """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named)."""
         def build():
@@ -382,7 +439,16 @@ class StableDiffusionXLPipeline:
             return prog
         return self._cached(self._unet_programs, program_key(B, L), build)
 
-    def vae_program(self, B: int, L) -> VAEProgram:
+    def vae_program(self, B: int, L):
+        """The ACTIVE decoder's program (``pipe.decoder``): a ``VAEProgram`` or a ``TinyVAEProgram`` - the same surface."""
+        if self._decoder == "tiny":
+            def build_tiny():
+                prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64)
+                if self._use_graphs:
+                    prog.prog.instantiate()
+                return prog
+            return self._cached(self._tiny_vae_programs, program_key(B, L), build_tiny)
+
         def build():
             prog = self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
             if self._use_graphs:
@@ -395,7 +461,7 @@ class StableDiffusionXLPipeline:
         if flag:
             for p in self._unet_programs.values():
                 p.enable_graphs()
-            for p in self._vae_programs.values():
+            for p in list(self._vae_programs.values()) + list(self._tiny_vae_programs.values()):
                 p.prog.instantiate()
 
     def synchronize(self):

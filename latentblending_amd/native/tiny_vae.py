@@ -1,0 +1,241 @@
+"""Native TAESDXL tiny decoder (diffusers ``AutoencoderTiny`` decoder as published for ``madebyollin/taesdxl``; the reference
+loads it at latentblending/blending_engine.py:797-806 and diffusers_holder.py:373-379) for gfx950: the
+preview / real-time alternative to the full ``AutoencoderKL`` decode of ``native/vae.py``.
+
+Architecture (restated from the published one; ``diffusers`` is not available here, so the decoder is NOT pinned against a
+diffusers run - the tests hold it to a float64 restatement of this description, ``tests/_taesd_ref.py``):
+
+    x = tanh(z / 3) * 3                                      z: latents in SCALED units (scaling_factor 1.0: nothing is divided out)
+    decoder.layers.0        conv 4 -> 64, bias, ReLU
+    per stage i (num_blocks (3, 3, 3, 1)):
+        block               relu(conv(relu(conv(relu(conv(x))))) + x), three biased 64 -> 64 convs at decoder.layers.N.conv.{0,2,4}
+        every stage but the last:  nearest-2x upsample, then conv 64 -> 64 WITHOUT bias
+        the last stage:            conv 64 -> 3 with bias
+    image = 2 x - 1  in [-1, 1]
+    layer indices: 0, [2-4], 6, [7-9], 11, [12-14], 16, [17], 18; the checkpoint's ``encoder.*`` keys are ignored.
+
+No normalisation, no attention: the program is ``lb_nchw_to_nhwc_f16``, about thirty 3x3 convs and ``lb_postprocess_u8``.  The
+64 -> 64 convs (block convs; the three upsample convs with ``ups = 1``: the gather reads the low-resolution map) go through
+``lb_gemm_f16`` with ``LB_GEMM_C64`` - the kernel with LDS-resident weights, csrc/conv3_c64.hip - where ``use_c64`` says so, and
+through the library's own routing (halo-tile kernel / implicit GEMM) otherwise: ``c64=False`` records the same launches without the
+bit, which is the A/B and the fallback.  The last conv takes the narrow-N route with ``OUT_F32``; ``2 x - 1`` is folded into its
+weights and bias at load time (``W * 2``, ``b * 2 - 1``).
+
+The tanh clamp has no launcher of its own (the library's C ABI is closed: every exported launcher must have a replay case in the
+program tests, and this pull request adds no symbol): it is one torch elementwise over ``B * 4 * H * W`` values, applied where
+``decode()`` stages the latents.
+
+Quality: TAESDXL is a distilled approximation of the SDXL VAE - a speed / preview option.  With the seeded synthetic stand-in
+weights nothing can be said about it; an LPIPS tree built under ``decoder="tiny"`` is computed on the tiny decoder's own frames.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, Tuple
+
+import torch
+
+from ..hip import lib
+from ..hip.lib import api
+from .geometry import latent_hw
+from .runtime import Arena, Emitter, Program, F16, F32, _stream
+from .unet import _pad
+from .weights import SyntheticProvider
+
+# LB_GEMM_C64 is set on a 64 -> 64 conv only where the flagged launch measured faster than the library's own route for the same
+# problem by more than the run-to-run spread (tools/tiny_vae_bench.py -> profiles/tiny_vae.txt, one MI355X, both launches
+# interleaved in one process, bias + ReLU; unflagged time / flagged time):
+#    B  output map  ups   tiles  speedup        B  output map  ups   tiles  speedup
+#   17    64 x 64     0     272    1.61         2    64 x 64     0      32    1.00   <- a tie: 32 blocks on 256 CUs either way
+#   17   128 x 128    0    1088    1.74         2   128 x 128    0     128    1.48
+#   17   256 x 256    0    4352    1.77         2   256 x 256    0     512    1.58
+#   17   512 x 512    0   17408    1.80         2   512 x 512    0    2048    1.79
+#   17   128 x 128    1    1088    1.58         2   128 x 128    1     128    1.08
+#   17   256 x 256    1    4352    1.92         2   256 x 256    1     512    1.62
+#   17   512 x 512    1   17408    1.91         2   512 x 512    1    2048    1.87
+# Every shape of at least 128 output tiles (16 x 16 pixels) wins, the one below (32 tiles) does not; nothing in between was
+# measured, so the bit stays off there: the constant is the smallest tile count that was measured to win.
+C64_MIN_TILES = 128
+
+
+def use_c64(B: int, Hout: int, Wout: int, min_tiles: int = None) -> bool:
+    """The emitter's rule for one 64 -> 64 conv whose OUTPUT map is ``Hout x Wout`` at batch ``B`` (``min_tiles``: default
+    ``C64_MIN_TILES``, read at call time)."""
+    return B * -(-Hout // 16) * -(-Wout // 16) >= (C64_MIN_TILES if min_tiles is None else min_tiles)
+
+
+@dataclass
+class TinyVAEConfig:
+    latent_channels: int = 4
+    out_channels: int = 3
+    block_channels: Tuple[int, ...] = (64, 64, 64, 64)
+    num_blocks: Tuple[int, ...] = (3, 3, 3, 1)
+    latent_magnitude: float = 3.0
+    scaling_factor: float = 1.0          # the latents arrive in scaled units
+    force_upcast: bool = False
+
+    def __post_init__(self):
+        if any(int(c) != 64 for c in self.block_channels):
+            raise ValueError(f"TinyVAEConfig: every block width must be 64 (TAESDXL), got {tuple(self.block_channels)}")
+        if len(self.block_channels) != len(self.num_blocks) or not self.num_blocks:
+            raise ValueError("TinyVAEConfig: block_channels and num_blocks must have the same, non-zero length")
+
+    @property
+    def scale_factor(self) -> int:
+        return 2 ** (len(self.block_channels) - 1)
+
+
+def layer_plan(cfg: TinyVAEConfig):
+    """The decoder's parameterised layers in order: ("in" | "block" | "up" | "out", index into ``decoder.layers``)."""
+    plan, idx = [("in", 0)], 2                          # (layers.1 is the ReLU behind conv_in)
+    for i, n in enumerate(cfg.num_blocks):
+        for _ in range(n):
+            plan.append(("block", idx))
+            idx += 1
+        if i < len(cfg.num_blocks) - 1:
+            plan.append(("up", idx + 1))                # (layers.idx is the Upsample)
+            idx += 2
+        else:
+            plan.append(("out", idx))
+            idx += 1
+    return plan
+
+
+def state_dict_keys(cfg: TinyVAEConfig = None):
+    """The ``decoder.*`` keys of ``taesdxl``'s ``diffusion_pytorch_model.safetensors`` this decoder reads, in layer order."""
+    keys = []
+    for kind, n in layer_plan(cfg or TinyVAEConfig()):
+        p = f"decoder.layers.{n}"
+        if kind == "block":
+            for k in (0, 2, 4):
+                keys += [f"{p}.conv.{k}.weight", f"{p}.conv.{k}.bias"]
+        elif kind == "up":
+            keys.append(p + ".weight")
+        else:
+            keys += [p + ".weight", p + ".bias"]
+    return keys
+
+
+class NativeTinyVAEDecoder:
+    def __init__(self, cfg: TinyVAEConfig, provider, device="cuda"):
+        self.cfg, self.device = cfg, torch.device(device)
+        self.w: Dict[str, torch.Tensor] = {}
+        self._load(provider)
+
+    def _dev(self, t, dtype):
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _conv(self, pv, name, cin, cout, bias=True, gain=1.0, bias_shift=0.0, fold=False):
+        """Packed as ``NativeVAEDecoder._conv`` does: [cout_p][3][3][cin_p] fp16 ((ky, kx, cin) order), fp32 bias.  ``fold``: the
+        decoder's final ``2 x - 1`` goes into the last conv (``W * 2``: exact in fp16; ``b * 2 - 1``)."""
+        w = pv.weight(name + ".weight", (cout, cin, 3, 3), cin * 9, gain)
+        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
+        packed = torch.zeros(cout_p, 3, 3, cin_p, dtype=torch.float32)
+        packed[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
+        b = torch.zeros(cout_p, dtype=torch.float32)
+        if bias:
+            b[:cout] = pv.bias(name + ".bias", cout) + bias_shift
+        if fold:
+            packed, b = packed * 2.0, b * 2.0
+            b[:cout] -= 1.0
+        self.w[name + ".weight"] = self._dev(packed.reshape(cout_p, 9 * cin_p), F16)
+        self.w[name + ".bias"] = self._dev(b, F32) if (bias or fold) else None
+
+    def _load(self, pv):
+        cfg = self.cfg
+        # the synthetic stand-in: the last conv at gain 0.5 with 0.5 added to its biases, so that frames centre on mid-grey
+        # instead of saturating at black; a real checkpoint (DictProvider) is taken as it is
+        synthetic = isinstance(pv, SyntheticProvider)
+        for kind, n in layer_plan(cfg):
+            p = f"decoder.layers.{n}"
+            if kind == "in":
+                self._conv(pv, p, cfg.latent_channels, 64)
+            elif kind == "block":
+                for k in (0, 2, 4):
+                    self._conv(pv, f"{p}.conv.{k}", 64, 64)
+            elif kind == "up":
+                self._conv(pv, p, 64, 64, bias=False)
+            else:
+                self._conv(pv, p, 64, cfg.out_channels, gain=0.5, bias_shift=0.5 if synthetic else 0.0, fold=True)
+
+    def build(self, B: int, L, c64: bool = True) -> "TinyVAEProgram":
+        """``L``: latent side, or a pair ``(H, W)`` in latent pixels.  ``c64``: LB_GEMM_C64 on the 64 -> 64 convs where ``use_c64``
+        says so (False: the same launches without the bit)."""
+        return TinyVAEProgram(self, B, L, c64=c64)
+
+
+class TinyVAEProgram:
+    """One recorded tiny decode for a fixed (batch, latent size); the surface of ``VAEProgram``."""
+
+    def __init__(self, net: NativeTinyVAEDecoder, B: int, L, c64: bool = True):
+        cfg = net.cfg
+        H, W = latent_hw(L)
+        self.net, self.B, self.H, self.W = net, B, H, W
+        self.L = H if H == W else None
+        self.c64 = bool(c64)
+        self.c64_launches = 0                   # convs recorded with the bit
+        dev = net.device
+        self.arena = Arena(dev)
+        self.em = Emitter(self.arena)
+        self.em.ragged_halo = H != W            # (the unflagged 3x3 convs of a non-square program, as in VAEProgram)
+        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
+        self.image_f32 = torch.zeros(B, SH, SW, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
+        self.prog = Program("tiny-vae-decode")
+        with self.prog.record():
+            self._emit()
+
+    def _conv64(self, x, name, B, hin, win, *, ups=0, relu=True, residual=None):
+        """One 64 -> 64 conv (on the nearest-2x upsampled map when ``ups``): flagged where the rule says so."""
+        w = self.net.w
+        ho, wo = hin << ups, win << ups
+        out = self.arena.alloc((B, ho, wo, 64))
+        flags = lib.GEMM_RELU if relu else 0
+        if self.c64 and use_c64(B, ho, wo):
+            flags |= lib.GEMM_C64
+            self.c64_launches += 1
+        self.em.gemm(x, w[name + ".weight"], out, M=B * ho * wo, bias=w[name + ".bias"], residual=residual, flags=flags, splitk=False,
+                     conv=dict(Hin=hin, Win=win, Cin=64, Hout=ho, Wout=wo, KH=3, KW=3, stride=1, pad=1, ups=ups, ldx=64))
+        return out
+
+    def _emit(self):
+        cfg, em, w, ar, B = self.net.cfg, self.em, self.net.w, self.arena, self.B
+        sh, sw = self.H, self.W
+        lc, lc_p = cfg.latent_channels, _pad(cfg.latent_channels, 8)
+        z8 = ar.alloc((B, sh, sw, lc_p))            # (pad channels written as zeros by the layout kernel)
+        api.lb_nchw_to_nhwc_f16(self.z_in.data_ptr(), z8.data_ptr(), B, lc, sh * sw, lc_p, 1.0, _stream())
+        h = None
+        for kind, n in layer_plan(cfg):
+            p = f"decoder.layers.{n}"
+            if kind == "in":
+                h = ar.alloc((B, sh, sw, 64))
+                em.gemm(z8, w[p + ".weight"], h, M=B * sh * sw, bias=w[p + ".bias"], flags=lib.GEMM_RELU, splitk=False,
+                        conv=dict(Hin=sh, Win=sw, Cin=lc_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=lc_p))
+                ar.release(z8)
+            elif kind == "block":
+                a = self._conv64(h, p + ".conv.0", B, sh, sw)
+                b = self._conv64(a, p + ".conv.2", B, sh, sw)
+                ar.release(a)
+                o = self._conv64(b, p + ".conv.4", B, sh, sw, residual=h)
+                ar.release(b)
+                ar.release(h)
+                h = o
+            elif kind == "up":
+                o = self._conv64(h, p, B, sh, sw, ups=1, relu=False)
+                ar.release(h)
+                h = o
+                sh, sw = 2 * sh, 2 * sw
+            else:
+                em.gemm(h, w[p + ".weight"], self.image_f32, M=B * sh * sw, bias=w[p + ".bias"], flags=lib.GEMM_OUT_F32, splitk=False,
+                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+                ar.release(h)
+        api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw, _pad(cfg.out_channels, 4), 1, _stream())
+
+    def decode(self, z: torch.Tensor) -> torch.Tensor:
+        """z [B,4,H,W] final latents (scaled units) -> uint8 [B,8H,8W,3].  The decoder's input clamp ``tanh(z / 3) * 3`` is applied
+        here, in torch (see the module docstring)."""
+        m = float(self.net.cfg.latent_magnitude)
+        self.z_in.copy_((m * torch.tanh(z.float() / m)).half())
+        self.prog.launch()
+        return self.frames

@@ -16,6 +16,7 @@ Host-side control only; the hot path below it is ``BlendingEngine.run_transition
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -51,7 +52,7 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          fps: int = 30, dp_parts: str = ".", keep_parts: bool = True,
                          on_segment: Optional[Callable[[int, List], None]] = None,
                          pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
-                         movie_size=None, movie_resample: Optional[str] = None) -> List[List]:
+                         movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -68,7 +69,33 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
 
     ``movie_encoder``: "host" / "device" for every part's ``write_movie_transition`` (None: the engine's ``movie_encoder``).
     ``movie_size`` / ``movie_resample``: its ``size_output=(W, H)`` / ``resample=`` (None: the engine's ``movie_size`` / ``movie_resample``).
+    ``decoder``: "full" / "tiny" = the native pipe's ``decoder`` for this chain (None: as the pipe stands); the previous value is
+    restored afterwards.
     """
+    with _decoder_as(be, decoder):
+        return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
+                                     keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample)
+
+
+@contextlib.contextmanager
+def _decoder_as(be, decoder: Optional[str]):
+    """Run the body with the engine's native pipe on ``decoder`` (None: untouched), then put the previous value back."""
+    if decoder is None:
+        yield
+        return
+    pipe = be.dh.pipe
+    if not hasattr(type(pipe), "decoder"):
+        raise ValueError("decoder=... needs the native pipe (NativeSDXLPipe)")
+    previous = pipe.decoder
+    pipe.decoder = decoder
+    try:
+        yield
+    finally:
+        pipe.decoder = previous
+
+
+def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts, keep_parts,
+                          on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample) -> List[List]:
     n = len(list_prompts)
     if n < 2:
         raise ValueError("run_multi_transition needs at least two prompts")
@@ -137,12 +164,13 @@ def _precompute_chain(be, list_prompts, list_seeds, list_negative_prompts):
 
 def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_single_trans: float = 10,
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
-                   movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None) -> List[List]:
-    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain."""
+                   movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
+                   decoder: Optional[str] = None) -> List[List]:
+    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder`` as there)."""
     header, items = load_movie_json(fp_json)
     be.set_dimensions((header["width"], header["height"]))
     be.set_num_inference_steps(header["num_inference_steps"])
     return run_multi_transition(be, [it["prompt"] for it in items], [it["seed"] for it in items], fp_movie,
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
-                                movie_size=movie_size, movie_resample=movie_resample)
+                                movie_size=movie_size, movie_resample=movie_resample, decoder=decoder)
