@@ -114,6 +114,15 @@ enum {
                               * ceiling division, the tile shape is the one that covers the image with fewer tile pixels (ties: 32 x 8),
                               * pixels of an overhanging tile outside the image are neither stored nor counted into LB_GEMM_CH_STATS.
                               * A shape that divides runs exactly what it runs without the flag; every other launcher ignores the bit. */
+    LB_GEMM_HALO_KSPLIT = 4096, /* opt-in, whole-tile 3x3 halo conv only (lb_conv3x3_halo_f16 and the router in lb_gemm_f16): the launch may
+                              * split its tiles along Cin so that every CU gets an even share of the (channel block, tile, 64-channel chunk)
+                              * units; cut tiles are summed inside the launch in a fixed order (same bits on every run; fp32 re-association
+                              * against the unsplit launch).  `partial` must then point to lb_conv_halo_ksplit_workspace_bytes() bytes whose
+                              * leading counters are ZERO on entry (the kernel leaves them zero; the slabs behind them - written and read write-through - need no
+                              * initialisation); NULL is refused.  Whether a flagged launch splits is lb_conv_halo_ksplit_plan's answer
+                              * (lb_conv_halo_set_ksplit); where it does not - ragged shapes, Cin < 128, shapes that fill whole rounds - and
+                              * without the bit every launch is exactly the unflagged one.  A flagged conv that lb_gemm_f16 routes to
+                              * another kernel runs there without split-K workspace. */
     LB_GEMM_C64 = 2048,      /* opt-in routing bit of lb_gemm_f16 (lb_gemm_plan: tile code 12; recorded as "conv3x3_c64"): the 64 -> 64 channel
                               * 3x3 conv with the layer's whole weight matrix resident in LDS (conv3_c64.hip).  Needs conv = 1, KH = KW = 3,
                               * stride 1, pad 1, scatter 0, Cin = N = 64, K = 576, ldx / ldw multiples of 8, ldc a multiple of 4, zero_page,
@@ -186,6 +195,18 @@ void lb_conv_halo_set_persistent(int on);
 /* Host arithmetic of a halo launch (no device work): kind 0 = not eligible, 3 = 3x3 form, 2 = 2x2 sub-pixel form; the
  * tile width (32 / 16), the number of (tile [, parity], channel block) work items and the grid that walks them. */
 void lb_conv_halo_plan(const LbGemmParams* params, int* kind, int* tile_w, long* items, long* grid);
+/* LB_GEMM_HALO_KSPLIT, host arithmetic only (launches nothing): the (channel block, tile, chunk) units of the launch, the grid
+ * (one block per CU, each walking units [b * units / grid, (b + 1) * units / grid)) and split = 1 if a launch with these
+ * parameters takes the K-split form, 0 = it stays unsplit even if flagged (then units = grid = 0 unless the shape is eligible).
+ * lb_conv_halo_plan keeps reporting the tile items and the unsplit grid. */
+/* Bytes of the workspace (`partial`) a launch with these parameters needs: one int counter per (channel block, tile), padded to
+ * 256 B, then two 256 x 128 fp32 slabs per block of the grid; 0 = the launch does not split.  Zero the counters once. */
+/* Tuning: mode 0 = never split, 1 = the step-count policy (default), 2 = every flagged whole-tile launch with Cin >= 128;
+ * grid > 0 overrides the grid (tests only: size the workspace under the same override), 0 = one block per CU. */
+/* The three prototypes (lb_conv_halo_ksplit_plan, lb_conv_halo_ksplit_workspace_bytes, lb_conv_halo_set_ksplit) live in
+ * lb_hip_ksplit.h: this header lists what hip/lib.py binds in SIGNATURES - the table of what a program can record, one replay case
+ * per entry - and these three launch nothing and take no stream (hip/lib.py: HOST_SIGNATURES). */
+#include "lb_hip_ksplit.h"
 /* LB_GEMM_CH_STATS: row blocks PER SAMPLE of the statistics buffer ([N][B * rows] float2) the launch lb_gemm_f16 would make
  * for these parameters writes - from the same routing and the same tile constants as the launch itself; 0 = this problem does
  * not run on a halo-tile kernel (no statistics: the consumer runs the two-pass GroupNorm).  Launches nothing. */

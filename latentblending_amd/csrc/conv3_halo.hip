@@ -82,9 +82,22 @@ template <int KS, int NR, int TAP> constexpr int halo_full_rounds_in_tap() {   /
 // overhangs the right / bottom edge stages zeros for the pixels outside the image (the loader's mask below does that for every form) and
 // its epilogue stores - and counts into the channel statistics - only the pixels inside it.  The request streams and their vmcnt counts
 // are those of the whole-tile form: masked requests are still issued.  RAG = false is the shipped code, instruction for instruction.
-template <int BN, int TW, int KS = 3, bool RAG = false>
+//
+// KSP (LB_GEMM_HALO_KSPLIT, whole-tile 3x3 form only): the launch's work is the list of UNITS (channel block, pixel tile, 64-channel
+// chunk) - chunk fastest, then tile, then channel block - and block b of G walks the contiguous range [b U / G, (b + 1) U / G): every CU
+// gets the same number of steps (+-9) whatever the tile count.  `item` is then the tile's index in that order (channel block * tiles +
+// pixel tile); only the first and the last tile of a range can be cut, the request streams run from unit to unit as they run from tile to
+// tile (the weight offsets follow the channel block).  A block whose range holds all chunks of a tile runs the epilogue as ever.  A cut
+// tile is summed inside the launch, and nobody waits for anybody: every contributor stores its fp32 accumulators to a slab of its own
+// (fragment order: 16 B per lane, 8 KiB per wave instruction; write-through stores), drains, and draws a ticket from the tile's counter
+// (relaxed, agent scope); the block that draws the LAST ticket adds ALL slabs (its own included; sc1 loads) in block = chunk order - the
+// sum does not depend on who arrived last - runs the epilogue on the sum and puts the counter back to zero.  Workspace (p.partial): the counters (one
+// int per tile, zero on entry, zero on exit; halo_ksplit_layout), then two slabs per block (2 b: the block's first tile, 2 b + 1: its last).
+// KSP = false is the shipped code, instruction for instruction.
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false>
 __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p) {
     static_assert(!RAG || KS == 3, "ragged tiles exist for the 3x3 form only");
+    static_assert(!KSP || (KS == 3 && !RAG), "the K-split form exists for the whole-tile 3x3 form only");
     constexpr int TH = 256 / TW;
     constexpr int NTAP = KS * KS;
     constexpr int HWP = TW + KS - 1;                    // halo width in pixels
@@ -127,10 +140,17 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         const int q = G / 8, r = G % 8, xcd = bid % 8, idx = bid / 8;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
     }
-    const int block_n = bid % n_blocks;
+    // KSP: this block's unit range [u_lo, u_hi) and the tile (in unit order) its first unit lies in
+    const int n_tiles = KSP ? n_items / n_blocks : 0;
+    const long n_units = KSP ? (long)n_items * (p.Cin / 64) : 0;
+    const long u_lo = KSP ? (long)bid * n_units / G : 0, u_hi = KSP ? (long)(bid + 1) * n_units / G : 0;
+    if constexpr (KSP)
+        if (u_lo >= u_hi) return;                       // (G <= units: the launcher never leaves a block without one)
+    const int first_item = KSP ? (int)(u_lo / (p.Cin / 64)) : bid;
+    const int block_n = KSP ? first_item / n_tiles : bid % n_blocks;
     const int par_x = KS == 2 ? (bid / n_blocks) & 1 : 0;          // output parity of a sub-pixel block
     const int par_y = KS == 2 ? ((bid / n_blocks) >> 1) & 1 : 0;
-    const int n0 = block_n * BN;
+    int n0 = block_n * BN;                              // (KSP: follows the tile's channel block; else fixed for the block's life)
     const int org_y = KS == 3 ? 1 : 1 - par_y, org_x = KS == 3 ? 1 : 1 - par_x;     // halo row 0 / col 0 = pixel (y0 - org_y, x0 - org_x)
     const lb_half* Wp = p.W + (KS == 2 ? (long)(par_y * 2 + par_x) * p.N * p.ldw : 0);
     const int nchunks = p.Cin / 64;
@@ -138,7 +158,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
 
     struct TileAt { int b, y0, x0; };
     auto tile_of = [&](int item) {                      // item -> image and tile origin (block-uniform: scalar registers)
-        int tile = item / n_blocks;
+        int tile = KSP ? item % n_tiles : item / n_blocks;
         if (KS == 2) tile >>= 2;
         TileAt t;
         t.x0 = (tile % tiles_x) * TW;
@@ -169,14 +189,18 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
     // wave-uniform base (tap / chunk position: scalar), and no mask - rows past N re-read row N - 1 (their output columns are never
     // stored, and every column's accumulator is its own), requests past the end of the block's work re-read the last tap / chunk (into
     // ring slots nobody reads again) - instead of a 64-bit address + two selects against the zero page per request.
-    long w_off[WI];
-    unsigned w_off32[WI];
+    long w_off[WI], w_offn[WI];                         // (..n: KSP, the channel block of the NEXT tile - requests that wrap past this tile's last chunk)
+    unsigned w_off32[WI], w_off32n[WI];
+    auto set_w_offsets = [&](int col_base, long (&o64)[WI], unsigned (&o32)[WI]) {
 #pragma unroll
-    for (int i = 0; i < WI; ++i) {
-        const int n = n0 + (tid >> 3) + i * 64;
-        w_off[i] = n < p.N ? (long)n * p.ldw + cl * 8 : -1;
-        w_off32[i] = (unsigned)(((long)(n < p.N ? n : p.N - 1) * p.ldw + cl * 8) * 2);
-    }
+        for (int i = 0; i < WI; ++i) {
+            const int n = col_base + (tid >> 3) + i * 64;
+            o64[i] = n < p.N ? (long)n * p.ldw + cl * 8 : -1;
+            o32[i] = (unsigned)(((long)(n < p.N ? n : p.N - 1) * p.ldw + cl * 8) * 2);
+        }
+    };
+    set_w_offsets(n0, w_off, w_off32);
+    if constexpr (KSP) set_w_offsets(n0, w_offn, w_off32n);
 
 #ifdef LB_STUDY_BUILD
     const int study = p.reserved_;                      // timing studies only (lb_conv_halo_set_study): 1 no epilogue, 2 halo from the zero page, 4 weights from the zero page
@@ -189,19 +213,22 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         f16* dst = halo0 + buf * (HRP * 64) + gidx * 8 * 64;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
     };
-    auto issue_weight = [&](int i, int chunk, bool exists, int tap, int slot) {
+    // (nxt_slab, KSP only: the request wrapped into the next tile - whose channel block may be another one)
+    auto issue_weight = [&](int i, int chunk, bool exists, int tap, int slot, bool nxt_slab = false) {
         f16* dst = wring + slot * (BN * 64) + (wave * 8 + i * 64) * 64;
         if constexpr (LB_HALO_LEAN_ADDR) {
             if (!(study & 4)) {
                 // (exists == false: chunk / tap are those of a request past the end: any staged bytes will do - the address stays inside W
                 //  because the caller wraps them to chunk 0 / a tap < NTAP)
                 const char* base = reinterpret_cast<const char*>(Wp) + ((long)tap * p.Cin + (long)chunk * 64) * 2;        // wave-uniform
-                __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)w_off32[i]), (lptr_t)dst, 16, 0, 0);
+                const unsigned o32 = KSP && nxt_slab ? w_off32n[i] : w_off32[i];
+                __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)o32), (lptr_t)dst, 16, 0, 0);
                 return;
             }
         }
-        const bool live = w_off[i] >= 0 && exists && !(study & 4);
-        const lb_half* src = live ? Wp + w_off[i] + (long)tap * p.Cin + (long)chunk * 64 : zero;
+        const long o64 = KSP && nxt_slab ? w_offn[i] : w_off[i];
+        const bool live = o64 >= 0 && exists && !(study & 4);
+        const lb_half* src = live ? Wp + o64 + (long)tap * p.Cin + (long)chunk * 64 : zero;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
     };
 
@@ -256,16 +283,21 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
     };
 
     // ---- prologue: halo of chunk 0 of the first tile, weight tiles of steps 0..2 ------------------------
-    int item = bid;
+    int item = first_item;
+    int c_lo = 0, c_end = nchunks;                      // the chunks [c_lo, c_end) of tile `item` are this block's (KSP: its range may cut the tile)
+    if constexpr (KSP) {
+        c_lo = (int)(u_lo - (long)item * nchunks);
+        c_end = (int)(u_hi - (long)item * nchunks < nchunks ? u_hi - (long)item * nchunks : nchunks);
+    }
     TileAt cur = tile_of(item);
     set_halo_offsets(cur, true);
 #pragma unroll
     for (int j = 0; j < NR; ++j)
-        if (j < NR - 1 || wave < EXTRA) issue_halo(j, 0, 0);
+        if (j < NR - 1 || wave < EXTRA) issue_halo(j, c_lo, 0);
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int i = 0; i < WI; ++i) issue_weight(i, 0, true, t, t);
+        for (int i = 0; i < WI; ++i) issue_weight(i, c_lo, true, t, t);
 
     // one step; TAP is a compile-time constant so that every count below is an immediate.  c = chunk within the tile,
     // cc = chunks since the block started (halo buffer / weight slot parity run on across tiles), more = another tile follows
@@ -284,7 +316,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         asm volatile("" : "+v"(shift));
         // requests of this step: rounds of the NEXT halo scheduled here (chunk c+1, or chunk 0 of the next tile: h_off
         // was re-pointed at the start of the tile's last chunk), then W(step + 3) (wrapping into the next tile likewise)
-        const bool last = c + 1 == nchunks;
+        const bool last = c + 1 == c_end;           // (c_end == nchunks unless a K-split range ends inside this tile)
         const int hc = last ? 0 : c + 1, hbuf = (cc + 1) & 1;
         constexpr int TAP3 = (TAP + 3) % NTAP;
         const bool wrap = (TAP + 3 >= NTAP) && last;
@@ -303,11 +335,11 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         mma_rows(a0, w0, 0, TM / 2);
         read_frags(hb, wb, shift, 1, a1, w1);
         __builtin_amdgcn_sched_barrier(0);
-        issue_weight(0, c3, w_exists, TAP3, slot3);
+        issue_weight(0, c3, w_exists, TAP3, slot3, wrap);
         __builtin_amdgcn_sched_barrier(0);
         mma_rows(a0, w0, TM / 2, TM);
         __builtin_amdgcn_sched_barrier(0);
-        issue_weight(1, c3, w_exists, TAP3, slot3);
+        issue_weight(1, c3, w_exists, TAP3, slot3, wrap);
         __builtin_amdgcn_sched_barrier(0);
         mma_rows(a1, w1, 0, TM);
     };
@@ -321,11 +353,15 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
 
     int cc = 0;
     for (;;) {
-        const int next_item = item + G;
-        const bool more = next_item < n_items;
+        const int next_item = KSP ? item + 1 : item + G;
+        const bool more = KSP ? (long)next_item * nchunks < u_hi : next_item < n_items;
         const TileAt nxt = tile_of(more ? next_item : item);
-        for (int c = 0; c < nchunks; ++c, ++cc) {
-            if (c + 1 == nchunks) set_halo_offsets(nxt, more);      // this tile's halos are all requested: aim at the next tile
+        const int n0_next = KSP && more ? (next_item / n_tiles) * BN : n0;
+        for (int c = c_lo; c < c_end; ++c, ++cc) {
+            if (c + 1 == c_end) {                                   // this tile's halos are all requested: aim at the next tile
+                set_halo_offsets(nxt, more);
+                if constexpr (KSP) set_w_offsets(n0_next, w_offn, w_off32n);
+            }
             step(std::integral_constant<int, 0>{}, c, cc, more);
             step(std::integral_constant<int, 1>{}, c, cc, more);
             step(std::integral_constant<int, 2>{}, c, cc, more);
@@ -336,6 +372,81 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
                 step(std::integral_constant<int, 6>{}, c, cc, more);
                 step(std::integral_constant<int, 7>{}, c, cc, more);
                 step(std::integral_constant<int, 8>{}, c, cc, more);
+            }
+        }
+        if constexpr (KSP) {
+            if (c_lo != 0 || c_end != nchunks) {        // (block-uniform) a cut tile: acc is a partial sum over chunks [c_lo, c_end)
+                // contributors of this tile = the blocks that own its first ... last unit (host twin: halo_ksplit_contributors);
+                // owner(u) = the largest b with b U / G <= u = ((u + 1) G - 1) / U
+                const long t0 = (long)item * nchunks;
+                const int b_first = (int)(((t0 + 1) * G - 1) / n_units), b_last = (int)(((t0 + nchunks) * G - 1) / n_units);
+                constexpr long SLAB = 256l * BN;        // floats per slab
+                int* const counters = reinterpret_cast<int*>(p.partial);
+                float* const slabs = p.partial + (((long)n_items * 4 + 255) / 256) * 64;
+                int tid_s = tid;                        // (opaque: the slab addresses are not held across the MFMA loop)
+                asm volatile("" : "+v"(tid_s));
+                // Slabs go through a buffer descriptor with WRITE-THROUGH (sc1, aux 16) 16-byte stores and are read back with sc1 loads
+                // only: the bytes are in memory when the store has retired, so the publish needs no agent-scope release - whose write-back
+                // of the XCD's whole L2 (full of every block's output tiles here) measured 15-25 us per launch - and the reader no
+                // acquire.  Offsets: lane * 16 B in the VGPR, slab and fragment (8 KiB apart) in the scalar offset.
+                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(slabs, 0, (int)(unsigned)(2l * G * SLAB * 4), 0x00020000);
+                const int voff = tid_s * 16;
+                const int mine = (2 * bid + (item == first_item ? 0 : 1)) * (int)(SLAB * 4);
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), srs, voff, mine + (i * TN + j) * 8192, 16);
+                // publish: every wave drains its write-through stores, barrier, then ONE lane draws the ticket (relaxed, agent scope); the
+                // block whose add came last reads the slabs, its other waves behind the barrier below.  Nobody waits for another block.
+                // (The drain also retires the next tile's requests in flight: the counted waits of the steps that follow then wait for
+                // fewer loads than they allow, never for more.)
+                volatile int* const flag = reinterpret_cast<volatile int*>(lds + 2 * HRP * 64 + 4 * BN * 64);   // (16 B past the weight ring)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (tid == 0) {
+                    const int ticket = __hip_atomic_fetch_add(counters + item, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const bool last_one = ticket == b_last - b_first;
+                    if (last_one) __hip_atomic_store(counters + item, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // zero for the next launch
+                    *flag = last_one ? 1 : 0;
+                }
+                __syncthreads();
+                // (block-uniform, and through readfirstlane so that the compiler knows: a branch on a value loaded from LDS would make the
+                //  whole tile state - item, origins, channel block - per-lane values; the flag is next written after another barrier)
+                const bool reduce = __builtin_amdgcn_readfirstlane(*flag) != 0;
+                if (!reduce) {                          // not the last arriver: on to the next tile (the tail of the loop below)
+                    if (!more) break;
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                    item = next_item;
+                    cur = nxt;
+                    n0 = n0_next;
+                    set_w_offsets(n0, w_off, w_off32);
+                    c_lo = 0;
+                    c_end = (int)(u_hi - (long)item * nchunks < nchunks ? u_hi - (long)item * nchunks : nchunks);
+                    continue;
+                }
+                // the sum, in block order = chunk order, every slab from memory (this block's too): the same bits whoever is last
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                for (int b = b_first; b <= b_last; ++b) {
+                    const bool first_tile_of_b = (long)b * n_units / G / nchunks == item;
+                    const int src = (2 * b + (first_tile_of_b ? 0 : 1)) * (int)(SLAB * 4);
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {      // (a row of fragments at a time: 16 more registers, not 64; EVERY slab load is sc1)
+                        f32x4 part[TN];
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            part[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, voff, src + (i * TN + j) * 8192, 16));
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) acc[i][j] += part[j];
+                    }
+                }
             }
         }
         // epilogue of this tile (registers -> global memory; the next tile's first operands are in flight meanwhile)
@@ -359,7 +470,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
             };
             if (p.flags & LB_GEMM_CH_STATS) {
                 const long stat_rows = (long)(n_items / n_blocks) * 4;
-                float2* chst = reinterpret_cast<float2*>(p.ch_stats) + ((long)(item / n_blocks) * 4 + wave_m);
+                float2* chst = reinterpret_cast<float2*>(p.ch_stats) + ((long)(KSP ? item % n_tiles : item / n_blocks) * 4 + wave_m);
                 lb_gemm_tile_epilogue_rows_ln<TM, TN, false, false, true, true>(q, acc, row_of, col0, 0, (const LbLnRows<TM>*)nullptr, chst, stat_rows);
             } else {
                 lb_gemm_tile_epilogue_rows<TM, TN, false>(q, acc, row_of, col0, 0);
@@ -382,7 +493,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
             const int colw = col0 - 4 * ((tid_o & 63) >> 4);
             if (p.flags & LB_GEMM_CH_STATS) {   // (wave-uniform) GroupNorm statistics of the stored tile: row block (item / n_blocks) * 4 + wave_m
                 const long stat_rows = (long)(n_items / n_blocks) * 4;          // row blocks of the whole launch
-                float2* chst = reinterpret_cast<float2*>(p.ch_stats) + ((long)(item / n_blocks) * 4 + wave_m);
+                float2* chst = reinterpret_cast<float2*>(p.ch_stats) + ((long)(KSP ? item % n_tiles : item / n_blocks) * 4 + wave_m);
                 if (!lb_gemm_tile_epilogue_lean<TM, TN, true, true>(q, acc, [&](int i) { return mbase + mloc[i]; }, mbase, row_hi, out_rel,
                                                                     out_lo, cur.b, colw, chst, stat_rows))
                     lb_gemm_tile_epilogue_rows_ln<TM, TN, false, false, true>(q, acc, [&](int i) { return mbase + mloc[i]; }, col0, 0,
@@ -401,6 +512,12 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
             for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         item = next_item;
         cur = nxt;
+        if constexpr (KSP) {                            // the next tile: maybe another channel block, all chunks unless the range ends in it
+            n0 = n0_next;
+            set_w_offsets(n0, w_off, w_off32);
+            c_lo = 0;
+            c_end = (int)(u_hi - (long)item * nchunks < nchunks ? u_hi - (long)item * nchunks : nchunks);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the masked tail requests still target this block's LDS: drain before exit
 }
@@ -454,25 +571,26 @@ long lb_conv_halo_stat_rows_total(const LbGemmParams& p) {
     return items / ((p.N + 127) / 128) * 4;
 }
 
-template <int BN, int TW, int KS = 3, bool RAG = false>
-static int launch_halo(const LbGemmParams& p, hipStream_t stream) {
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false>
+static int launch_halo(const LbGemmParams& p, hipStream_t stream, long ksp_grid = 0) {
     constexpr int TH = 256 / TW;
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
-    constexpr int SMEM = (2 * HRP * 64 + 4 * BN * 64) * (int)sizeof(f16);
+    constexpr int SMEM = (2 * HRP * 64 + 4 * BN * 64) * (int)sizeof(f16) + (KSP ? 16 : 0);   // (KSP: the "last arriver" word)
     static unsigned long long seen = 0;
     // (a recording does not come here: the first call on a device happens at the first replay - inside the stream capture of
     //  lb_program_instantiate when a program is instantiated before any eager run)
     LB_ONCE_PER_DEVICE(seen)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
     long nblk, grid;
     halo_grid(p, TW, KS, nblk, grid);          // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
+    if (KSP) grid = ksp_grid;                  // (one block per CU walks an even share of the units: halo_ksplit_plan)
     LbGemmParams pk = p;
 #ifdef LB_STUDY_BUILD
     pk.reserved_ = g_halo_study;
 #endif
-    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG, KSP>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
     return lb_check_launch(KS == 2 ? "lb_upconv2x_halo_f16" : "lb_conv3x3_halo_f16");
 }
 
@@ -540,6 +658,68 @@ int lb_conv3x3_halo_eligible(const LbGemmParams& p) {
 // (of an eligible problem) the image does not divide into tiles of the width lb_conv3x3_halo_eligible chose: the RAG instantiation
 static bool halo3_ragged(const LbGemmParams& p, int tw) { return p.Win % tw != 0 || p.Hin % (256 / tw) != 0; }
 
+// ---- K-split form (LB_GEMM_HALO_KSPLIT): host twins of the kernel's unit walk ------------------------------------------------------
+// mode 0 = never, 1 = the policy below (default), 2 = every flagged launch with Cin >= 128; grid > 0 overrides G (tests: a workspace
+// sized under one override must not be used under a larger one)
+static int g_halo_ksplit_mode = 1, g_halo_ksplit_grid = 0;
+extern "C" void lb_conv_halo_set_ksplit(int mode, int grid) {
+    g_halo_ksplit_mode = mode < 0 ? 1 : mode;
+    g_halo_ksplit_grid = grid > 0 ? grid : 0;
+}
+// Policy, in steps of one (chunk, tap) pair per block: unsplit = whole rounds of whole tiles, split = an even share of the units plus
+// an allowance for the (at most two) cut tiles of a block - slab store, drain, ticket and, for the last arriver, the slab reads: all
+// of it serial in a CU that holds one block.  Numbers from profiles/halo_ksplit_ab.txt (per-shape A/B of modes 0 / 2,
+// tools/halo_ksplit_ab.py; a step is 0.75 - 0.85 us there): what a split launch takes beyond its steps is 12 - 21 us more than what
+// an unsplit one takes beyond its own = 15 - 27 steps: 20.  (With plain slab stores behind an agent-scope release it was 15 - 25 us
+// MORE - profiles/halo_ksplit_ab_release_fence.txt - and no Cin 320 shape gained.)  5 % margin on top.  With these numbers every
+// partial-round shape of the programs is split; the three whose measured gain is inside the spread of their repeats - 16^2
+// 640 -> 1280 (+3.2 us), 64^2 320 -> 320 (+8.0 us), B = 2 64^2 320 -> 320 (+1.8 us) - were repeated 15 times
+// (profiles/halo_ksplit_ab_close.txt): +0.3 (a tie), +3.8 and +1.2 us, the last two beyond their spread.
+static constexpr long HALO_KSPLIT_FIXUP_STEPS = 20;
+static constexpr long HALO_KSPLIT_MARGIN_PCT = 5;       // split only where the estimate wins by this much
+static void halo_ksplit_plan(const LbGemmParams& p, long& units, long& grid, int& split) {
+    units = grid = 0;
+    split = 0;
+    if (!(p.flags & LB_GEMM_HALO_KSPLIT) || (p.flags & LB_GEMM_C64) || g_halo_ksplit_mode == 0) return;
+    const int tw = lb_conv3x3_halo_eligible(p);
+    if (!tw || halo3_ragged(p, tw) || p.Cin < 128) return;
+    long items, ugrid;
+    halo_grid(p, tw, 3, items, ugrid);
+    const long nchunks = p.Cin / 64;
+    if (items * nchunks >= (1l << 31)) return;
+    units = items * nchunks;
+    grid = g_halo_ksplit_grid > 0 ? g_halo_ksplit_grid : halo_num_cus();
+    if (grid > units) grid = units;
+    if (2 * grid * 256l * 128 * 4 >= (1l << 31)) {              // (the slabs sit behind ONE buffer descriptor: int byte offsets)
+        units = grid = 0;
+        return;
+    }
+    if (g_halo_ksplit_mode >= 2) {
+        split = 1;
+        return;
+    }
+    const long unsplit_steps = (items + ugrid - 1) / ugrid * 9 * nchunks;
+    const long split_steps = (units + grid - 1) / grid * 9 + HALO_KSPLIT_FIXUP_STEPS;
+    split = split_steps * (100 + HALO_KSPLIT_MARGIN_PCT) <= unsplit_steps * 100 ? 1 : 0;
+}
+// workspace layout: one int counter per tile (channel block x pixel tile), padded to 256 B, then two 256 x 128 fp32 slabs per block
+static long halo_ksplit_counter_bytes(long items) { return (items * 4 + 255) / 256 * 256; }
+extern "C" void lb_conv_halo_ksplit_plan(const LbGemmParams* pp, long* units, long* grid, int* split) {
+    long u = 0, g = 0;
+    int s = 0;
+    if (pp != nullptr && pp->M > 0 && pp->Hin > 0 && pp->Win > 0) halo_ksplit_plan(*pp, u, g, s);
+    if (units) *units = u;
+    if (grid) *grid = g;
+    if (split) *split = s;
+}
+extern "C" long lb_conv_halo_ksplit_workspace_bytes(const LbGemmParams* pp) {
+    long u = 0, g = 0;
+    int s = 0;
+    if (pp != nullptr && pp->M > 0 && pp->Hin > 0 && pp->Win > 0) halo_ksplit_plan(*pp, u, g, s);
+    if (!s) return 0;
+    return halo_ksplit_counter_bytes(u / (pp->Cin / 64)) + 2 * g * 256l * 128 * (long)sizeof(float);
+}
+
 long lb_conv3x3_halo_blocks(const LbGemmParams& p) {
     long tiles = (long)p.M / 256;                       // 256 output pixels per block
     if (const int tw = (p.flags & LB_GEMM_HALO_RAGGED) ? lb_conv3x3_halo_eligible(p) : 0)       // (ragged: blocks, not pixels / 256)
@@ -552,6 +732,13 @@ int lb_conv3x3_halo_check(const LbGemmParams& p) {
                "halo conv: LB_GEMM_CH_STATS needs ch_stats and a row-major output");
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || p.ch_stats_rows == lb_conv_halo_stat_rows_total(p),
                "halo conv: ch_stats_rows must be B * lb_gemm_ch_stat_rows() (the row blocks this launch writes per channel)");
+    {
+        long units, grid;
+        int split;
+        halo_ksplit_plan(p, units, grid, split);
+        LB_REQUIRE(!split || p.partial != nullptr,
+                   "halo conv: LB_GEMM_HALO_KSPLIT needs partial = a zeroed workspace of lb_conv_halo_ksplit_workspace_bytes()");
+    }
     return halo_tiles_check(p, lb_conv3x3_halo_eligible(p), 3);
 }
 
@@ -560,6 +747,11 @@ int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
     p.splitk = 1;
     const int tw = lb_conv3x3_halo_eligible(p);
     if (halo3_ragged(p, tw)) return tw == 32 ? launch_halo<128, 32, 3, true>(p, stream) : launch_halo<128, 16, 3, true>(p, stream);
+    long units, grid;
+    int split;
+    halo_ksplit_plan(p, units, grid, split);
+    if (split && p.partial != nullptr)
+        return tw == 32 ? launch_halo<128, 32, 3, false, true>(p, stream, grid) : launch_halo<128, 16, 3, false, true>(p, stream, grid);
     return tw == 32 ? launch_halo<128, 32>(p, stream) : launch_halo<128, 16>(p, stream);
 }
 

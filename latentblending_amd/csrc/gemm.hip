@@ -620,6 +620,10 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
         if (const int rc = lb_conv3x3_halo_check(p)) return rc;
         LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
     }
+    if (p.flags & LB_GEMM_HALO_KSPLIT) {           // not a halo launch: `partial` is the K-split workspace of that kernel, not split-K slabs
+        p.flags &= ~LB_GEMM_HALO_KSPLIT;
+        p.partial = nullptr;
+    }
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS), "lb_gemm_f16: LB_GEMM_CH_STATS is implemented by the halo-tile conv kernels only "
                                               "(check lb_gemm_plan == 6 / lb_conv_halo_plan before asking for it)");
     int tile = 0, splitk = 1;

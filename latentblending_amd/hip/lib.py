@@ -48,6 +48,7 @@ class LbAttnParams(C.Structure):
 GEMM_OUT_F32, GEMM_RES_F32, GEMM_GEGLU, GEMM_TRANS_OUT, GEMM_SILU, GEMM_RELU, GEMM_LN_A = 1, 2, 4, 8, 16, 32, 64
 GEMM_QUICK_GELU, GEMM_GELU, GEMM_CH_STATS = 128, 256, 512
 GEMM_HALO_RAGGED = 1024      # opt-in ragged tiles of the 3x3 halo conv (include/lb_hip.h)
+GEMM_HALO_KSPLIT = 4096     # opt-in K-split form of the 3x3 halo conv: partial = lb_conv_halo_ksplit_workspace_bytes (include/lb_hip.h)
 GEMM_C64 = 2048              # opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights: that kernel or a refusal (include/lb_hip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
@@ -139,8 +140,16 @@ STUDY_SIGNATURES = {
     "lb_conv_halo_set_study": (None, [_i]),
 }
 
+# host arithmetic and tuning switch of the K-split halo conv (LB_GEMM_HALO_KSPLIT): they launch nothing and take no stream, so they are
+# bound beside SIGNATURES - the table of what a program can record (tests/_replay.py holds one replay case per entry)
+HOST_SIGNATURES = {
+    "lb_conv_halo_ksplit_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "lb_conv_halo_ksplit_workspace_bytes": (_l, [C.POINTER(LbGemmParams)]),
+    "lb_conv_halo_set_ksplit": (None, [_i, _i]),
+}
+
 _NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
-             "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan", "lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
+             "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan","lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
              "lb_program_destroy", "lb_program_recording", "lb_program_num_ops", "lb_program_op_name"}
 
 
@@ -177,6 +186,11 @@ for _name, (_res, _args) in SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
     setattr(api, _name, _fn if _name in _NO_CHECK else _wrap(_name, _fn))
+for _name, (_res, _args) in HOST_SIGNATURES.items():
+    _fn = getattr(_lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+    setattr(api, _name, _fn)
 for _name, (_res, _args) in STUDY_SIGNATURES.items():
     _fn = getattr(_lib, _name, None)
     if _fn is not None:

@@ -148,6 +148,11 @@ class Emitter:
         # into halo tiles ask for the ragged-tile form (LB_GEMM_HALO_RAGGED) where ``geometry.use_ragged_halo`` says so.  False
         # (every square program): no plan call, no flag - the recorded ops are those of ever.
         self.ragged_halo = False
+        # 3x3 halo-tile convs whose tiles fill the last round of CUs badly run the K-split form (LB_GEMM_HALO_KSPLIT) where the
+        # library's own plan says so (lb_conv_halo_ksplit_plan); False: no plan call, no flag.  One workspace per emitter: a fixed
+        # counter area (zeroed once: every launch leaves its counters zero) in front of the slabs all launches share.
+        self.halo_ksplit = True
+        self.ws_ksplit: Optional[torch.Tensor] = None
 
     def _ragged_flag(self, p: LbGemmParams) -> int:
         """LB_GEMM_HALO_RAGGED or 0 for the 3x3 / stride 1 conv ``p`` describes (the library's own plan, with and without the bit).
@@ -177,6 +182,40 @@ class Emitter:
                 self._retired.append(self.ws_gemm)
             self.ws_gemm = torch.empty(max(need, 1 << 22), dtype=F32, device=self.device)
         return self.ws_gemm
+
+    _KSPLIT_COUNTER_BYTES = 1 << 20
+
+    def _halo_ksplit(self, p: LbGemmParams) -> bool:
+        """Flag the 3x3 conv ``p`` for the K-split form of the halo-tile kernel and point ``partial`` at its workspace if
+        lb_gemm_f16 routes it to that kernel (tile code 6) and the library's plan splits it.  The launch's counters end where the
+        shared slab area begins, so no launch's slabs ever overlap another launch's counters."""
+        if not self.halo_ksplit or not p.conv or p.KH != 3 or p.KW != 3 or p.stride != 1 or p.scatter or p.ups:
+            return False
+        tile, sk, nb = C.c_int(), C.c_int(), C.c_long()
+        api.lb_gemm_plan(C.byref(p), C.byref(tile), C.byref(sk), C.byref(nb))
+        if tile.value != 6:
+            return False
+        flags = p.flags
+        p.flags = flags | lib.GEMM_HALO_KSPLIT
+        units, grid, split = C.c_long(), C.c_long(), C.c_int()
+        api.lb_conv_halo_ksplit_plan(C.byref(p), C.byref(units), C.byref(grid), C.byref(split))
+        need = int(api.lb_conv_halo_ksplit_workspace_bytes(C.byref(p)))
+        if not split.value or need <= 0:
+            p.flags = flags
+            return False
+        counters = ((units.value // (p.Cin // 64)) * 4 + 255) // 256 * 256
+        slabs = need - counters
+        assert slabs > 0 and slabs % (256 * 128 * 4) == 0, (need, counters)
+        if counters > self._KSPLIT_COUNTER_BYTES:
+            p.flags = flags
+            return False
+        total = self._KSPLIT_COUNTER_BYTES + slabs
+        if self.ws_ksplit is None or self.ws_ksplit.numel() < total:
+            if self.ws_ksplit is not None:      # (recorded ops keep pointing into the old buffer)
+                self._retired.append(self.ws_ksplit)
+            self.ws_ksplit = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        p.partial = self.ws_ksplit.data_ptr() + self._KSPLIT_COUNTER_BYTES - counters
+        return True
 
     def _gn_ws(self, B: int, groups: int) -> torch.Tensor:
         need = api.lb_groupnorm_workspace_bytes(B, groups) // 8
@@ -227,6 +266,8 @@ class Emitter:
             p.partial = _p(self._gemm_ws(M, N))
         if self.ragged_halo:
             p.flags |= self._ragged_flag(p)
+        if conv is not None:
+            self._halo_ksplit(p)
         api.lb_gemm_f16(C.byref(p), _stream())
         mult = 4.0 if p.scatter == 2 else 1.0          # (four parities: four times the rows, weights and outputs)
         self.gemm_log.append({"M": M, "N": N, "K": K, "flops": mult * 2.0 * M * N * K, "conv": conv is not None,

@@ -1,0 +1,167 @@
+"""K-split form of the 3x3 halo-tile conv (LB_GEMM_HALO_KSPLIT): the host arithmetic of lb_conv_halo_ksplit_plan against an
+emulation of the kernel's unit walk (csrc/conv3_halo.hip).  Units are (channel block, pixel tile, 64-channel chunk), chunk fastest;
+block b of G walks [b U / G, (b + 1) U / G); a tile cut by a range boundary is summed by the last of its contributors."""
+import ctypes
+
+import pytest
+
+from latentblending_amd.hip import lib
+
+SLAB_BYTES = 256 * 128 * 4
+
+
+def conv_params(B, H, W, Cin, N, flags=0):
+    p = lib.LbGemmParams()
+    p.M, p.N, p.K, p.conv, p.flags = B * H * W, N, 9 * Cin, 1, flags
+    p.Hin, p.Hout, p.Win, p.Wout = H, H, W, W
+    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx, p.ldw, p.ldc = Cin, 3, 3, 1, 1, Cin, 9 * Cin, N
+    p.zero_page = 64
+    return p
+
+
+def ksplit_plan(p):
+    units, grid, split = ctypes.c_long(), ctypes.c_long(), ctypes.c_int()
+    lib.api.lb_conv_halo_ksplit_plan(ctypes.byref(p), ctypes.byref(units), ctypes.byref(grid), ctypes.byref(split))
+    return units.value, grid.value, split.value
+
+
+def halo_plan(p):
+    kind, tw, items, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_long(), ctypes.c_long()
+    lib.api.lb_conv_halo_plan(ctypes.byref(p), ctypes.byref(kind), ctypes.byref(tw), ctypes.byref(items), ctypes.byref(grid))
+    return kind.value, tw.value, items.value, grid.value
+
+
+@pytest.fixture
+def ksplit_switch():
+    yield lib.api.lb_conv_halo_set_ksplit
+    lib.api.lb_conv_halo_set_ksplit(1, 0)
+
+
+def walk(units, grid, nchunks):
+    """The kernel's walk: per block its segments (tile, c_lo, c_end, slab or None), per tile the contributors the kernel derives."""
+    covered = [0] * units
+    segments, slabs_used, arrivals = [], set(), {}
+    for b in range(grid):
+        u_lo, u_hi = b * units // grid, (b + 1) * units // grid
+        assert u_lo < u_hi, "a block without a unit"
+        first_item = u_lo // nchunks
+        item, c_lo = first_item, u_lo - first_item * nchunks
+        while True:
+            c_end = min(nchunks, u_hi - item * nchunks)
+            for c in range(c_lo, c_end):
+                covered[item * nchunks + c] += 1
+            slab = None
+            if c_lo != 0 or c_end != nchunks:
+                slab = 2 * b + (0 if item == first_item else 1)
+                assert slab not in slabs_used, "two partial sums in one slab"
+                slabs_used.add(slab)
+                arrivals.setdefault(item, []).append((b, slab))
+            segments.append((b, item, c_lo, c_end, slab))
+            if (item + 1) * nchunks >= u_hi:
+                break
+            item, c_lo = item + 1, 0
+    return covered, segments, slabs_used, arrivals
+
+
+def kernel_contributors(item, units, grid, nchunks):
+    """What the last arriver computes: first / last contributing block and the slab each one wrote."""
+    t0 = item * nchunks
+    b_first, b_last = ((t0 + 1) * grid - 1) // units, ((t0 + nchunks) * grid - 1) // units
+    return [(b, 2 * b + (0 if (b * units // grid) // nchunks == item else 1)) for b in range(b_first, b_last + 1)]
+
+
+SPLIT_SHAPES = [(17, 16, 16, 1280, 1280), (17, 32, 32, 640, 640), (17, 64, 64, 320, 320), (2, 64, 64, 320, 320), (17, 64, 64, 512, 512)]
+WHOLE_ROUND_SHAPES = [(17, 512, 512, 128, 128), (17, 128, 128, 512, 512)]
+
+
+@pytest.mark.parametrize("shape", SPLIT_SHAPES)
+def test_policy_splits_partial_rounds(shape):
+    """The five shapes the K-split form was built for: the policy splits them, on one block per CU.
+
+    Measured (profiles/halo_ksplit_ab.txt, us per launch unsplit -> split, one MI355X): (17,16,16,1280,1280) 121.7 -> 111.8,
+    (17,32,32,640,640) 141.8 -> 116.4, (17,64,64,320,320) 144.7 -> 136.7, (2,64,64,320,320) 33.9 -> 32.1, (17,64,64,512,512)
+    287.0 -> 270.4."""
+    B, H, W, Cin, N = shape
+    p = conv_params(B, H, W, Cin, N, lib.GEMM_HALO_KSPLIT)
+    kind, _, items, _ = halo_plan(p)
+    assert kind == 3
+    units, grid, split = ksplit_plan(p)
+    cus = halo_plan(conv_params(17, 512, 512, 128, 128))[3]      # a launch of 17408 one-channel-block items: one block per CU
+    assert split == 1 and grid == cus and units == items * (Cin // 64)
+    # the unflagged plan is what it was, and an unflagged launch never splits
+    assert halo_plan(conv_params(B, H, W, Cin, N))[2:] == halo_plan(p)[2:]
+    assert ksplit_plan(conv_params(B, H, W, Cin, N)) == (0, 0, 0)
+    assert lib.api.lb_conv_halo_ksplit_workspace_bytes(ctypes.byref(conv_params(B, H, W, Cin, N))) == 0
+
+
+@pytest.mark.parametrize("shape", WHOLE_ROUND_SHAPES)
+def test_policy_leaves_whole_rounds_unsplit(shape):
+    p = conv_params(*shape, lib.GEMM_HALO_KSPLIT)
+    _, _, items, grid = halo_plan(p)
+    assert items % grid == 0                                     # 68 / 17 whole rounds
+    assert ksplit_plan(p)[2] == 0
+    assert lib.api.lb_conv_halo_ksplit_workspace_bytes(ctypes.byref(p)) == 0
+
+
+def test_switch_modes(ksplit_switch):
+    p = conv_params(17, 32, 32, 640, 640, lib.GEMM_HALO_KSPLIT)
+    ksplit_switch(0, 0)
+    assert ksplit_plan(p)[2] == 0
+    ksplit_switch(2, 0)
+    assert ksplit_plan(p)[2] == 1
+    assert ksplit_plan(conv_params(17, 128, 128, 512, 512, lib.GEMM_HALO_KSPLIT))[2] == 1      # mode 2: every flagged launch ...
+    assert ksplit_plan(conv_params(17, 64, 64, 64, 128, lib.GEMM_HALO_KSPLIT))[2] == 0         # ... with Cin >= 128
+    assert ksplit_plan(conv_params(1, 40, 24, 128, 128, lib.GEMM_HALO_KSPLIT | lib.GEMM_HALO_RAGGED))[2] == 0    # ragged: out of scope
+    ksplit_switch(2, 7)
+    assert ksplit_plan(p)[1] == 7
+    ksplit_switch(2, 10 ** 6)                                    # never more blocks than units
+    units, grid, _ = ksplit_plan(p)
+    assert grid == units
+
+
+WALK_CASES = [(s, 0) for s in SPLIT_SHAPES] + [((4, 16, 32, 128, 128), 3), ((1, 32, 16, 320, 132), 7), ((2, 16, 16, 192, 256), 4),
+                                                ((1, 16, 16, 640, 128), 10), ((3, 16, 16, 128, 384), 5), ((1, 16, 16, 128, 128), 2)]
+
+
+@pytest.mark.parametrize("shape,forced_grid", WALK_CASES)
+def test_unit_walk(shape, forced_grid, ksplit_switch):
+    B, H, W, Cin, N = shape
+    ksplit_switch(2, forced_grid)                                # (the walk, not the policy: 0 = one block per CU)
+    p = conv_params(B, H, W, Cin, N, lib.GEMM_HALO_KSPLIT)
+    units, grid, split = ksplit_plan(p)
+    nchunks = Cin // 64
+    assert split == 1 and units == halo_plan(p)[2] * nchunks and (not forced_grid or grid == min(forced_grid, units))
+    covered, segments, slabs_used, arrivals = walk(units, grid, nchunks)
+    assert covered == [1] * units                                # every unit exactly once
+    for item, who in arrivals.items():                           # the contributors the kernel derives = the blocks that arrive
+        assert who == kernel_contributors(item, units, grid, nchunks)
+        assert sum(c_end - c_lo for b, it, c_lo, c_end, _ in segments if it == item) == nchunks
+    for b, item, c_lo, c_end, slab in segments:                  # whole tiles take no ticket
+        assert (slab is None) == (c_lo == 0 and c_end == nchunks)
+    need = lib.api.lb_conv_halo_ksplit_workspace_bytes(ctypes.byref(p))
+    counters = (units // nchunks * 4 + 255) // 256 * 256
+    assert need >= counters + (max(slabs_used) + 1 if slabs_used else 0) * SLAB_BYTES
+    assert need == counters + 2 * grid * SLAB_BYTES
+
+
+def test_cases_of_the_gpu_test_are_what_they_claim(ksplit_switch):
+    """The three protocol cases of tests/test_halo_ksplit_gpu.py: the walk has the features their descriptions promise."""
+    ksplit_switch(2, 3)
+    units, grid, _ = ksplit_plan(conv_params(4, 16, 32, 128, 128, lib.GEMM_HALO_KSPLIT))
+    _, segments, _, _ = walk(units, grid, 2)
+    # 16 units over 3 blocks = [0, 5), [5, 10), [10, 16): the head of tile 2 | its tail and two whole tiles | whole tiles
+    assert [(c_lo, c_end) for b, _, c_lo, c_end, _ in segments if b == 0] == [(0, 2), (0, 2), (0, 1)]
+    assert [(c_lo, c_end) for b, _, c_lo, c_end, _ in segments if b == 1] == [(1, 2), (0, 2), (0, 2)]
+    # (the same image with three chunks over 5 blocks: block 3 holds the tail of one tile, a whole tile and the head of the next)
+    ksplit_switch(2, 5)
+    units, grid, _ = ksplit_plan(conv_params(4, 16, 32, 192, 128, lib.GEMM_HALO_KSPLIT))
+    _, segments, _, _ = walk(units, grid, 3)
+    assert [(c_lo, c_end) for b, _, c_lo, c_end, _ in segments if b == 3] == [(2, 3), (0, 3), (0, 1)]
+    ksplit_switch(2, 7)
+    units, grid, _ = ksplit_plan(conv_params(1, 32, 16, 320, 132, lib.GEMM_HALO_KSPLIT))
+    _, _, _, arrivals = walk(units, grid, 5)
+    assert max(len(v) for v in arrivals.values()) == 3                           # a tile shared by three blocks
+    ksplit_switch(2, 4)
+    units, grid, _ = ksplit_plan(conv_params(2, 16, 16, 192, 256, lib.GEMM_HALO_KSPLIT))
+    _, _, slabs_used, arrivals = walk(units, grid, 3)
+    assert not slabs_used and not arrivals                                       # ranges end on tile boundaries: no partials
