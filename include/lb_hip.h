@@ -122,7 +122,8 @@ enum {
                               * initialisation); NULL is refused.  Whether a flagged launch splits is lb_conv_halo_ksplit_plan's answer
                               * (lb_conv_halo_set_ksplit); where it does not - ragged shapes, Cin < 128, shapes that fill whole rounds - and
                               * without the bit every launch is exactly the unflagged one.  A flagged conv that lb_gemm_f16 routes to
-                              * another kernel runs there without split-K workspace. */
+                              * another kernel runs there without split-K workspace; the bit never changes the route (an N <= 16 conv
+                              * still takes the narrow-N kernel), and lb_gemm_plan plans such a conv without the bit and `partial`. */
     LB_GEMM_C64 = 2048,      /* opt-in routing bit of lb_gemm_f16 (lb_gemm_plan: tile code 12; recorded as "conv3x3_c64"): the 64 -> 64 channel
                               * 3x3 conv with the layer's whole weight matrix resident in LDS (conv3_c64.hip).  Needs conv = 1, KH = KW = 3,
                               * stride 1, pad 1, scatter 0, Cin = N = 64, K = 576, ldx / ldw multiples of 8, ldc a multiple of 4, zero_page,
@@ -180,7 +181,9 @@ void lb_gemm_set_tuning(int tile, int splitk);   /* testing: force tile 1..5, 7 
 void lb_gemm_set_pp_auto(int on);                 /* A/B studies: 0 = the automatic tile policy never picks the ping-pong kernel (default 1) */
 void lb_gemm_pp_set_group(int gm);                /* tuning: tile order of the ping-pong kernel inside an XCD's run: gm block rows down, then the next block column (0 = strip order) */
 void lb_gemm_set_depth(int depth);               /* testing: 1 = one K-tile in flight, 0 = default ring */
-int lb_gemm_plan(const LbGemmParams* p, int* tile, int* splitk, long* blocks); /* the tile (1..5) / split-K / grid lb_gemm_f16 would use; launches nothing */
+int lb_gemm_plan(const LbGemmParams* p, int* tile, int* splitk, long* blocks); /* the tile (1..5) / split-K / grid lb_gemm_f16 would use; launches nothing.
+                                                  * As in lb_gemm_f16, a problem flagged LB_GEMM_HALO_KSPLIT that does not route to the halo kernel
+                                                  * (tile code 6) is planned without the flag and without `partial`: that workspace is no split-K one */
 /* 3x3 / stride 1 / pad 1 conv from an LDS-resident halo tile; same parameter block as lb_gemm_f16 (conv = 1,
  * KH = KW = 3, Cin % 64 == 0, Win % 16 == 0 - or any Hin x Win with LB_GEMM_HALO_RAGGED -, zero_page set).  lb_gemm_f16 routes eligible convs here by itself
  * (lb_gemm_plan reports tile code 6); lb_gemm_set_halo: 0 = never, 1 = when the halo grid fills the chip

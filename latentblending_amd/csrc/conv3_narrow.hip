@@ -123,7 +123,9 @@ int lb_conv3x3_narrow_eligible(const LbGemmParams& p) {
     if (!p.conv || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.ups || p.scatter) return 0;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.Cin % 64 != 0 || p.K != 9 * p.Cin) return 0;
     if (p.N > 16 || p.N % 4 != 0 || p.zero_page == nullptr) return 0;
-    if (p.flags & ~LB_GEMM_OUT_F32) return 0;           // plain bias epilogue only
+    // plain bias epilogue only (LB_GEMM_HALO_KSPLIT asks nothing of the epilogue: a hint for the halo kernel, which must not change
+    // the route of a conv that kernel does not get - `partial` is never read here)
+    if (p.flags & ~(LB_GEMM_OUT_F32 | LB_GEMM_HALO_KSPLIT)) return 0;
     if (p.residual != nullptr || p.rowvec != nullptr) return 0;
     if (p.Win % NARROW_T != 0 || p.Hin % NARROW_T != 0 || p.M % (p.Hin * p.Win) != 0) return 0;
     if ((long)p.M * p.ldx >= (1l << 34)) return 0;      // (32-bit piece offsets)

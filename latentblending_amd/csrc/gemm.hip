@@ -557,6 +557,12 @@ extern "C" int lb_gemm_plan(const LbGemmParams* pp, int* tile, int* splitk, long
     }
     else if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(*pp)) { t = 8; nb = (long)pp->M / 256; }   // tile code 8 = narrow-N conv kernel
     else if (use_halo(*pp)) { t = 6; nb = lb_conv3x3_halo_blocks(*pp); }     // tile code 6 = halo-tile conv kernel
+    else if (pp->flags & LB_GEMM_HALO_KSPLIT) {     // as lb_gemm_f16: not a halo launch, so `partial` is no split-K workspace
+        LbGemmParams q = *pp;
+        q.flags &= ~LB_GEMM_HALO_KSPLIT;
+        q.partial = nullptr;
+        gemm_plan(q, t, sk, nb);
+    }
     else gemm_plan(*pp, t, sk, nb);
     if (tile) *tile = t;
     if (splitk) *splitk = sk;

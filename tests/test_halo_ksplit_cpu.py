@@ -120,7 +120,9 @@ def test_switch_modes(ksplit_switch):
 
 
 WALK_CASES = [(s, 0) for s in SPLIT_SHAPES] + [((4, 16, 32, 128, 128), 3), ((1, 32, 16, 320, 132), 7), ((2, 16, 16, 192, 256), 4),
-                                                ((1, 16, 16, 640, 128), 10), ((3, 16, 16, 128, 384), 5), ((1, 16, 16, 128, 128), 2)]
+                                                ((1, 16, 16, 640, 128), 10), ((3, 16, 16, 128, 384), 5), ((1, 16, 16, 128, 128), 2),
+                                                # one_unit_per_block and default_grid of tests/_ksplit.py (the latter on 256 blocks here)
+                                                ((1, 16, 16, 1280, 128), 20), ((4, 32, 32, 1280, 256), 256)]
 
 
 @pytest.mark.parametrize("shape,forced_grid", WALK_CASES)
@@ -165,3 +167,62 @@ def test_cases_of_the_gpu_test_are_what_they_claim(ksplit_switch):
     units, grid, _ = ksplit_plan(conv_params(2, 16, 16, 192, 256, lib.GEMM_HALO_KSPLIT))
     _, _, slabs_used, arrivals = walk(units, grid, 3)
     assert not slabs_used and not arrivals                                       # ranges end on tile boundaries: no partials
+
+
+def test_new_cases_of_the_gpu_tests_are_what_they_claim(ksplit_switch):
+    """one_unit_per_block and default_grid of tests/_ksplit.py (tests/test_halo_ksplit_values_gpu.py)."""
+    ksplit_switch(2, 20)
+    units, grid, _ = ksplit_plan(conv_params(1, 16, 16, 1280, 128, lib.GEMM_HALO_KSPLIT))
+    assert (units, grid) == (20, 20)
+    _, segments, slabs_used, arrivals = walk(units, grid, 20)
+    assert [(b, item, c_lo, c_end) for b, item, c_lo, c_end, _ in segments] == [(c, 0, c, c + 1) for c in range(20)]
+    assert list(arrivals) == [0] and len(arrivals[0]) == 20 and slabs_used == {2 * b for b in range(20)}   # 20 contributors to one tile
+    ksplit_switch(2, 256)
+    units, grid, _ = ksplit_plan(conv_params(4, 32, 32, 1280, 256, lib.GEMM_HALO_KSPLIT))
+    assert (units, grid) == (640, 256)                                           # more units than blocks: 2.5 units per block
+    _, segments, _, arrivals = walk(units, grid, 20)
+    assert len(arrivals) == 32 and {len(v) for v in arrivals.values()} == {8}    # every tile is cut, into 8 partial sums of 2 or 3 chunks
+    assert {c_end - c_lo for _, _, c_lo, c_end, _ in segments} == {2, 3}
+
+
+def gemm_plan(p):
+    tile, splitk, blocks = ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
+    lib.api.lb_gemm_plan(ctypes.byref(p), ctypes.byref(tile), ctypes.byref(splitk), ctypes.byref(blocks))
+    return tile.value, splitk.value, blocks.value
+
+
+@pytest.fixture
+def halo_switch():
+    yield lib.api.lb_gemm_set_halo
+    lib.api.lb_gemm_set_halo(1)
+
+
+# (B, H, W, Cin, N, stride): 3x3 convs lb_gemm_f16 does not take to the halo kernel by default (too few halo blocks; stride 2; N = 4:
+# the narrow-N kernel, tile code 8, whenever the halo switch is not 0)
+PLAN_SHAPES = [(1, 16, 16, 1280, 128, 1), (2, 16, 16, 640, 320, 1), (1, 32, 32, 320, 64, 1), (2, 32, 32, 320, 320, 2),
+               (4, 16, 32, 128, 4, 1)]
+
+
+@pytest.mark.parametrize("shape", PLAN_SHAPES)
+def test_gemm_plan_of_a_flagged_conv_is_the_plan_of_the_launch(shape, ksplit_switch, halo_switch):
+    """lb_gemm_plan is "the tile / split-K / grid lb_gemm_f16 would use".  lb_gemm_f16 runs a flagged conv it does not route to the
+    halo kernel without the flag and without ``partial`` (the K-split workspace is no split-K workspace): the plan of the flagged
+    problem with ``partial`` set must be the plan of the unflagged problem without it - split-K 1, not 11 / 5 / 2 -, whatever the
+    two switches say."""
+    B, H, W, Cin, N, stride = shape
+
+    def problem(flagged):
+        p = conv_params(B, H, W, Cin, N, lib.GEMM_HALO_KSPLIT if flagged else 0)
+        p.stride, p.Hout, p.Wout = stride, (H - 1) // stride + 1, (W - 1) // stride + 1
+        p.M = B * p.Hout * p.Wout
+        p.partial = 4096 if flagged else None            # (host arithmetic only: never dereferenced)
+        return p
+
+    for halo_mode in (1, 0, 2):
+        halo_switch(halo_mode)
+        for mode in (0, 2):
+            ksplit_switch(mode, 0)
+            want = gemm_plan(problem(False))
+            assert gemm_plan(problem(True)) == want, (halo_mode, mode)
+            assert want[1] == 1 and (want[0] == 6) == (halo_mode == 2 and stride == 1 and N > 16)
+            assert (want[0] == 8) == (halo_mode != 0 and N <= 16)

@@ -5,101 +5,25 @@ uses.  tests/test_halo_ksplit_cpu.py checks that the walks of these cases have t
 
 Per case: the result (and the channel statistics) against F.conv2d in fp32 under the bar of test_conv3x3_halo_against_conv2d; ten
 launches bit-equal; slabs that start out as NaN never reach the result; guard bands around output and workspace intact; counters zero
-afterwards; eager = recorded replay = graph launch bit for bit.  The distance to the unsplit kernel is logged, not gated: fp32
-re-association of the chunk sums."""
+afterwards; eager = recorded replay = graph launch bit for bit.  The distance to the unsplit kernel is logged here (fp32
+re-association of the chunk sums) and gated, with the values against fp64, in tests/test_halo_ksplit_values_gpu.py; builder, launch
+and fixture are shared through tests/_ksplit.py."""
 import ctypes as C
-import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from _guard import guarded  # noqa: E402
-from _parity import check_close, rnd  # noqa: E402
+from _ksplit import DEV, F16, F32, SHAPES, forced_split, guarded_workspace, launch, lib, operands, params  # noqa: E402,F401
+from _parity import check_close  # noqa: E402
 
-DEV = "cuda"
-F16, F32 = torch.float16, torch.float32
-
-# name -> (B, H, W, Cin, N, forced grid)
-SHAPES = {
-    "tail_whole_whole": (4, 16, 32, 128, 128, 3),      # 16 units over 3 blocks: block 0 ends, block 1 starts inside tile 2
-    "tail_whole_head": (4, 16, 32, 192, 128, 5),       # block 3: the tail of one tile, a whole tile, the head of the next
-    "three_sharers": (1, 32, 16, 320, 132, 7),         # a tile shared by three blocks; the last channel block overhangs N
-    "tile_boundaries": (2, 16, 16, 192, 256, 4),       # ranges end on tile boundaries: no partial sums; two channel blocks
-}
 # (shape, epilogue): plain = bias only; res = bias + fp16 residual + alpha; rowvec = bias + time-embedding row vector; stats = bias +
 # LB_GEMM_CH_STATS
 CASES = [("tail_whole_whole", "plain"), ("tail_whole_head", "plain"), ("three_sharers", "plain"), ("tile_boundaries", "plain"),
          ("tail_whole_whole", "res"), ("tail_whole_whole", "rowvec"), ("tail_whole_whole", "stats"), ("tile_boundaries", "stats"),
          ("three_sharers", "stats")]
-ALPHA = 0.5
-
-
-def lib():
-    from latentblending_amd.hip import lib as l
-    return l
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-@functools.lru_cache(maxsize=None)
-def operands(shape):
-    """Inputs on the device and the fp32 conv2d of every epilogue, computed once per shape and never modified."""
-    from latentblending_amd.hip import ops as o
-    B, H, W, Cin, N, _ = SHAPES[shape]
-    x = rnd(B, Cin, H, W, seed=301)
-    w = rnd(N, Cin, 3, 3, seed=302, scale=(9 * Cin) ** -0.5)
-    bias = rnd(N, seed=303, dtype=F32)
-    res = rnd(B, H, W, N, seed=304)
-    rowvec = rnd(B, N, seed=305)
-    raw = F.conv2d(x.float(), w.float(), None, padding=1).permute(0, 2, 3, 1)
-    conv = raw + bias                                   # (the epilogue: alpha * sum + bias [+ residual | + row vector])
-    refs = {"plain": conv, "stats": conv, "res": ALPHA * raw + bias + res.float(), "rowvec": conv + rowvec.float()[:, None, None, :]}
-    dev = dict(x=x.permute(0, 2, 3, 1).contiguous().to(DEV), w=o.pack_conv_weight(w, Cin).to(DEV), bias=bias.to(DEV), res=res.to(DEV),
-               rowvec=rowvec.to(DEV), zero=o.zero_page(DEV))
-    return dev, refs
-
-
-def params(shape, epi, out, ksplit, ws=None, stats=None):
-    l = lib()
-    B, H, W, Cin, N, _ = SHAPES[shape]
-    d, _ = operands(shape)
-    p = l.LbGemmParams()
-    p.A, p.W, p.C, p.bias = d["x"].data_ptr(), d["w"].data_ptr(), out.data_ptr(), d["bias"].data_ptr()
-    p.M, p.N, p.K, p.ldw, p.ldc, p.ldr = B * H * W, N, 9 * Cin, d["w"].stride(0), out.stride(0), N
-    p.conv, p.Hin, p.Hout, p.Win, p.Wout = 1, H, H, W, W
-    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = Cin, 3, 3, 1, 1, Cin
-    p.alpha, p.zero_page = 1.0, d["zero"].data_ptr()
-    if epi == "res":
-        p.residual, p.alpha = d["res"].data_ptr(), ALPHA
-    if epi == "rowvec":
-        p.rowvec, p.ld_rowvec, p.rows_per_batch = d["rowvec"].data_ptr(), N, H * W
-    if stats is not None:
-        p.flags |= l.GEMM_CH_STATS
-        p.ch_stats, p.ch_stats_rows = stats.data_ptr(), stats.shape[1]
-    if ksplit:
-        p.flags |= l.GEMM_HALO_KSPLIT
-        p.partial = ws.data_ptr() if ws is not None else None
-    return p
-
-
-def launch(p):
-    lib().api.lb_conv3x3_halo_f16(C.byref(p), stream())
-
-
-@pytest.fixture
-def forced_split():
-    """mode 2 ("always") with the case's grid for the whole test - recorded ops read the switch when they are replayed."""
-    api = lib().api
-
-    def force(shape):
-        api.lb_conv_halo_set_ksplit(2, SHAPES[shape][5])
-    yield force
-    api.lb_conv_halo_set_ksplit(1, 0)
 
 
 @pytest.mark.parametrize("shape,epi", CASES)
@@ -125,8 +49,8 @@ def test_ksplit_conv(shape, epi, forced_split, results_log):
     n_counters = (M // 256) * ((N + 127) // 128)
     counter_floats = (n_counters * 4 + 255) // 256 * 64
     assert need == counter_floats * 4 + 2 * G * 256 * 128 * 4
-    ws, ws_guard = guarded(1, need // 4, need // 4, F32, DEV, back_rows=0)
-    ws[0, :counter_floats] = 0
+    ws, ws_guard, zeroed = guarded_workspace(probe)
+    assert zeroed == counter_floats and ws.shape == (1, need // 4)
     with pytest.raises(RuntimeError):                   # a split launch without a workspace is refused before anything runs
         launch(params(shape, epi, torch.empty(M, N, dtype=F16, device=DEV), True, ws=None, stats=fresh_stats()))
 
