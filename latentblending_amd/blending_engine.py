@@ -911,17 +911,11 @@ class BlendingEngine:
 
     @staticmethod
     def _draws_noise(sched) -> bool:
-        """Does this sampler consume per-step noise?  Euler-ancestral does; so does the latent-consistency sampler (``draws_noise``)."""
-        return bool(getattr(sched, "ancestral", False) or getattr(sched, "draws_noise", False))
+        return planner.draws_noise(sched)
 
     def _run_noise_draws(self, idx_start: int) -> int:
-        """Latent-shaped draws ONE denoising run from ``idx_start`` consumes: one per step for an ancestral sampler, one per step
-        but the schedule's last for the latent-consistency sampler (the scheduler's own ``noise_draws`` says so)."""
-        sched, steps = getattr(self.dh.pipe, "scheduler", None), self.num_inference_steps
-        own = getattr(sched, "noise_draws", None)
-        if own is not None:
-            return int(own(steps, idx_start))
-        return max(0, steps - int(idx_start)) if getattr(sched, "ancestral", False) else 0
+        """Latent-shaped draws ONE denoising run from ``idx_start`` consumes (``planner.noise_draws_per_run``)."""
+        return planner.noise_draws_per_run(getattr(self.dh.pipe, "scheduler", None), self.num_inference_steps, idx_start)
 
     def _skip_noise_draws(self, n):
         sched = getattr(self.dh.pipe, "scheduler", None)

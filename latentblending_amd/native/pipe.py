@@ -36,8 +36,8 @@ from ..hip.lib import api
 from .frames import DeviceImage
 from .geometry import program_key
 from .lpips import NativeLPIPS
-from .scheduler import (NativeDDIMScheduler, NativeDPMSolverPP2MScheduler, NativeEulerScheduler, NativeLCMScheduler,
-                        noise_draws_per_run)
+from ..planner import noise_draws_per_run
+from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .tiny_vae import NativeTinyVAEDecoder, TinyVAEConfig, TinyVAEProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
@@ -134,12 +134,9 @@ class StableDiffusionXLPipeline:
         prompt embeddings when no ``text_encoder_fn`` is given) are used silently when True (tests, bench: also
         ``LB_ALLOW_SYNTHETIC=1``); otherwise each stand-in announces itself ONCE with a ``UserWarning`` - frames
         rendered from them are noise-like and prompts have no semantic effect."""
-        if scheduler is not None and not isinstance(scheduler, str):
-            raise ValueError(f"NativeSDXLPipe: scheduler must be None, 'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras' "
-                             f"(got an object of type {type(scheduler).__name__})")
-        scheduler = None if scheduler is None else scheduler.strip().lower()
-        if scheduler not in (None, "euler", "ddim", "lcm", "dpmpp_2m", "dpmpp_2m_karras"):
-            raise ValueError(f"NativeSDXLPipe: unknown scheduler {scheduler!r} (None, 'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras')")
+        # (a bad name is refused before anything else - also on a machine without a device; the reference's SDXL pipes carry Euler /
+        # Euler-ancestral schedulers, the other names are this pipe's own)
+        self.scheduler = make_scheduler(scheduler, turbo, torch.device(device))
         self._decoder = self._check_decoder(decoder)
         if not torch.cuda.is_available():
             raise RuntimeError("NativeSDXLPipe needs an MI355X (HIP device); there is no CPU fallback")
@@ -165,13 +162,6 @@ class StableDiffusionXLPipeline:
         self.lpips_metric = NativeLPIPS(lpips_provider or SyntheticProvider(7), self.device)
         self.tiny_vae_native, self._tiny_vae_provider, self._tiny_seed = tiny_vae_native, tiny_vae_provider, seed + 2
         self.tiny_vae_cfg = tiny_vae_native.cfg if tiny_vae_native is not None else TinyVAEConfig()
-        # (the reference's SDXL pipes carry Euler / Euler-ancestral schedulers; scheduler="ddim" = diffusers' DDIMScheduler, eta 0)
-        if scheduler == "lcm":          # (diffusers' LCMScheduler: few-step sampling of distilled UNets / merged LCM-LoRAs)
-            self.scheduler = NativeLCMScheduler(device=self.device)
-        elif scheduler in ("dpmpp_2m", "dpmpp_2m_karras"):
-            self.scheduler = NativeDPMSolverPP2MScheduler(use_karras_sigmas=scheduler.endswith("karras"), device=self.device)
-        else:
-            self.scheduler = NativeDDIMScheduler(device=self.device) if scheduler == "ddim" else NativeEulerScheduler(ancestral=turbo, device=self.device)
         self.unet = _UNetFacade(self)
         self.vae = _VAEFacade(self)
         self.image_processor = _ImageProcessor()
@@ -251,18 +241,32 @@ class StableDiffusionXLPipeline:
         w = [float(g) - 1.0 for g in guidance_scales]
         return self.get_guidance_scale_embedding(w, embedding_dim=dim).to(self.device, F16)
 
-    def _step_kwargs(self, i: int, steps: int) -> dict:
-        # (the LCM step may run without noise on the schedule's last step only: the loop says which step this is - the kernel's
-        #  launcher never reads the device rows back)
-        return {"last": i == steps - 1} if self.scheduler.kind == "lcm" else {}
+    def _conditioning(self, conds: Sequence[tuple], cfg: bool):
+        """(context, pooled, time ids) of a UNet batch over ``conds`` = [(pos ctx, neg ctx, pos pooled, neg pooled), ...]: under CFG
+        the negative half first, then the positive one."""
+        ctx = torch.cat([c[0] for c in conds]).to(self.device, F16)
+        pooled = torch.cat([c[2] for c in conds]).to(self.device, F16)
+        if cfg:
+            neg_ctx = torch.cat([c[1] for c in conds]).to(self.device, F16)
+            neg_pool = torch.cat([c[3] for c in conds]).to(self.device, F16)
+            ctx, pooled = torch.cat([neg_ctx, ctx]), torch.cat([neg_pool, pooled])
+        time_ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
+        return ctx, pooled, time_ids
 
-    def _step_row(self, i: int, guidance: float, first: bool):
-        """The scheduler's row of step ``i``; a multistep sampler is also told whether this is the FIRST step the sample executes (it
-        has no history then: the reference's loop calls ``set_timesteps`` at the start of every run, which empties it)."""
-        sched = self.scheduler
-        return sched.step_row(i, guidance, first=first) if getattr(sched, "multistep", False) else sched.step_row(i, guidance)
+    def _launch_unet_step(self, prog, lat, params, n: int, cfg: bool, i: int, stream):
+        """One UNet forward of step ``i`` over the ``n`` latents ``lat`` (scaled into the program's input; eps = ``prog.eps``)."""
+        api.lb_scale_model_input_f16(lat.data_ptr(), prog.x_in.data_ptr(), params.data_ptr(), lat.numel() // n, n, int(cfg), stream)
+        prog.tvals.fill_(float(self.scheduler.timesteps_np[i]))
+        prog.prog_step.launch(stream)
+        self.stats["unet_forwards"] += 1
+        self.stats["unet_samples"] += prog.B
 
-    def _device_step(self, lat, hists, eps, params, noise, cfg: bool, i: int, steps: int, carry=None, mixed: bool = True):
+    @staticmethod
+    def _noise_slots(noise_slots, G: int) -> Tuple[int, List[int]]:
+        """(branches of the round noise is drawn for, which of them are this call's ``G``): all and every one without a farm."""
+        return (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
+
+    def _device_step(self, lat, hists, eps, params, noise, cfg: bool, i: int, carry=None, mixed: bool = True):
         """One batched scheduler step -> (latents, history, carry).  A single-step sampler has neither history nor carry (None).
         A multistep one gets a two-plane state: plane 0 the latents - AFTER any crossfeed / parental mix, which touch the latents
         only - and plane 1 the samples' previous x0 predictions.  ``carry`` is the state the previous call returned for the SAME
@@ -273,8 +277,8 @@ class StableDiffusionXLPipeline:
         plane 1 unwritten - the kernel does not read it.  The latents returned are a COPY of plane 0: the loops keep them in
         trajectories, which must neither pin the x0-prediction plane nor see the carry's plane 0 overwritten by a later mix."""
         sched = self.scheduler
-        if not getattr(sched, "multistep", False):
-            return sched.device_step(lat, eps, params, noise=noise, cfg=cfg, **self._step_kwargs(i, steps)), None, None
+        if not sched.multistep:
+            return sched.device_step(lat, eps, params, noise=noise, cfg=cfg, **sched.device_step_kwargs(i)), None, None
         if carry is not None:
             assert carry.shape[1:] == lat.shape
             state = carry
@@ -289,7 +293,7 @@ class StableDiffusionXLPipeline:
                     state[1, at:at + rows].copy_(h)
                 at += rows
             assert at == lat.shape[0]
-        out = sched.device_step(state, eps, params, cfg=cfg)
+        out = sched.device_step(state, eps, params, cfg=cfg, **sched.device_step_kwargs(i))
         return out[0].clone(), out[1], out
 
     def to(self, *_a, **_k):
@@ -441,20 +445,15 @@ class StableDiffusionXLPipeline:
 
     def vae_program(self, B: int, L):
         """The ACTIVE decoder's program (``pipe.decoder``): a ``VAEProgram`` or a ``TinyVAEProgram`` - the same surface."""
-        if self._decoder == "tiny":
-            def build_tiny():
-                prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64)
-                if self._use_graphs:
-                    prog.prog.instantiate()
-                return prog
-            return self._cached(self._tiny_vae_programs, program_key(B, L), build_tiny)
+        tiny = self._decoder == "tiny"
 
         def build():
-            prog = self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
+            prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64) if tiny else \
+                self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
             if self._use_graphs:
                 prog.prog.instantiate()
             return prog
-        return self._cached(self._vae_programs, program_key(B, L), build)
+        return self._cached(self._tiny_vae_programs if tiny else self._vae_programs, program_key(B, L), build)
 
     def enable_graphs(self, flag: bool = True):
         self._use_graphs = bool(flag)
@@ -509,25 +508,14 @@ class StableDiffusionXLPipeline:
         self._guidance_scale = float(guidance_scales[-1])
         cfg = wants[0]
         LH, LW = int(starts[0].shape[-2]), int(starts[0].shape[-1])
-        per_sample = starts[0][0].numel()
         prog = self.unet_program(G * (2 if cfg else 1), (LH, LW))
-
-        pos_ctx = torch.cat([c[0] for c in conds]).to(self.device, F16)
-        pos_pool = torch.cat([c[2] for c in conds]).to(self.device, F16)
-        if cfg:
-            neg_ctx = torch.cat([c[1] for c in conds]).to(self.device, F16)
-            neg_pool = torch.cat([c[3] for c in conds]).to(self.device, F16)
-            ctx, pooled = torch.cat([neg_ctx, pos_ctx]), torch.cat([neg_pool, pos_pool])
-        else:
-            ctx, pooled = pos_ctx, pos_pool
-        time_ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-        prog.set_conditioning(ctx, pooled, time_ids, timestep_cond=self._timestep_cond(guidance_scales))
+        prog.set_conditioning(*self._conditioning(conds, cfg), timestep_cond=self._timestep_cond(guidance_scales))
 
         latents = torch.cat([s.to(self.device, F16).reshape(1, -1, LH, LW) for s in starts]).contiguous()
         trajs: List[List[Optional[torch.Tensor]]] = [[None] * idx_start for _ in range(G)]
         stream = torch.cuda.current_stream().cuda_stream
         # every step's scalar coefficients in ONE upload: [steps][G][8]
-        rows = [self._step_row(i, float(guidance_scales[g]), first=i == idx_start) for i in range(idx_start, num_inference_steps)
+        rows = [sched.step_row(i, float(guidance_scales[g]), first=i == idx_start) for i in range(idx_start, num_inference_steps)
                 for g in range(G)]
         params_all = ops.step_params(rows, self.device).view(-1, G, 8) if rows else None
         # ancestral noise is drawn sample-major (all steps of branch 0, then branch 1, ...): the same
@@ -536,7 +524,7 @@ class StableDiffusionXLPipeline:
         nm = noise_draws_per_run(sched, num_inference_steps, idx_start)     # (ancestral: every step; LCM: every step but the last)
         if nm > 0:
             shape1 = (1,) + tuple(latents.shape[1:])
-            n_draw, keep = (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
+            n_draw, keep = self._noise_slots(noise_slots, G)
             drawn = sched.draw_noise_many(n_draw * nm, shape1, self.device).view(n_draw, nm, *shape1[1:])
             noise_all = drawn[keep].transpose(0, 1).contiguous()                             # [steps, G, 4, L, L]
         hist = carry = None         # (a multistep sampler's previous x0 predictions / two-plane state; every run starts without)
@@ -556,15 +544,9 @@ class StableDiffusionXLPipeline:
                         for g, o in zip(mix, outs):
                             latents[g:g + 1] = o
             params = params_all[i - idx_start]
-            api.lb_scale_model_input_f16(latents.data_ptr(), prog.x_in.data_ptr(), params.data_ptr(), per_sample, G,
-                                         int(cfg), stream)
-            prog.tvals.fill_(float(sched.timesteps_np[i]))
-            prog.prog_step.launch(stream)
-            self.stats["unet_forwards"] += 1
-            self.stats["unet_samples"] += prog.B
+            self._launch_unet_step(prog, latents, params, G, cfg, i, stream)
             noise = noise_all[i - idx_start] if noise_all is not None and i - idx_start < nm else None
-            latents, hist, carry = self._device_step(latents, [(hist, G)], prog.eps, params, noise, cfg, i, num_inference_steps,
-                                                     carry=carry, mixed=bool(mix))
+            latents, hist, carry = self._device_step(latents, [(hist, G)], prog.eps, params, noise, cfg, i, carry=carry, mixed=bool(mix))
             for g in range(G):
                 trajs[g].append(latents[g:g + 1])
         return trajs
@@ -620,16 +602,6 @@ class StableDiffusionXLPipeline:
         assert all(self.uses_cfg(g) == cfg for g in all_g), "wavefront batches must be uniformly CFG or non-CFG"
         mul = 2 if cfg else 1
         LH, LW = int(ref_start.shape[-2]), int(ref_start.shape[-1])
-        per_sample = ref_start[0].numel()
-
-        def conditioning(conds):
-            pos_ctx = torch.cat([c[0] for c in conds]).to(self.device, F16)
-            pos_pool = torch.cat([c[2] for c in conds]).to(self.device, F16)
-            if not cfg:
-                return pos_ctx, pos_pool
-            neg_ctx = torch.cat([c[1] for c in conds]).to(self.device, F16)
-            neg_pool = torch.cat([c[3] for c in conds]).to(self.device, F16)
-            return torch.cat([neg_ctx, pos_ctx]), torch.cat([neg_pool, pos_pool])
 
         def prepared(conds, side=None, after=None, guid=None):
             # (the program - arena, workspaces, first-time graph instantiation - is always obtained on the MAIN stream: its
@@ -639,25 +611,25 @@ class StableDiffusionXLPipeline:
             # small UNet step is already queued - waiting for it would also park the host in the side stream's host-to-device copies)
             n_conds = A + G if callable(conds) else len(conds)
             prog = self.unet_program(n_conds * mul, (LH, LW))
+
+            def set_conditioning():
+                # (copies into program-owned buffers, then the conditioning program: all on the stream that is current here - under
+                # `side` the temporaries never meet another stream)
+                prog.set_conditioning(*self._conditioning(conds() if callable(conds) else conds, cfg),
+                                      timestep_cond=self._timestep_cond(guid))
             if side is None:
-                conds = conds() if callable(conds) else conds
-                ctx, pooled = conditioning(conds)
-                ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-                prog.set_conditioning(ctx, pooled, ids, timestep_cond=self._timestep_cond(guid))
+                set_conditioning()
                 return prog, None
             if after is not None:
                 side.wait_event(after)
             else:
                 side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                conds = conds() if callable(conds) else conds
-                ctx, pooled = conditioning(conds)
-                ids = torch.tensor([self._time_ids_row()] * ctx.shape[0], dtype=F32, device=self.device)
-                prog.set_conditioning(ctx, pooled, ids, timestep_cond=self._timestep_cond(guid))     # (copies into program-owned buffers, then the conditioning program: all
-                return prog, side.record_event()            # on `side` - the temporaries above never meet another stream)
+                set_conditioning()
+                return prog, side.record_event()
 
         # G == 0: a farm rank that owns no mid branch of the round (fewer gaps than ranks) still runs both anchors
-        if elide_dead_steps and getattr(sched, "multistep", False):
+        if elide_dead_steps and sched.multistep:
             if "elide-multistep" not in self._warned:
                 self._warned.add("elide-multistep")
                 warnings.warn(f"elide_dead_steps is ignored under the multistep sampler {sched.kind!r}: a skipped step leaves no x0 "
@@ -684,9 +656,9 @@ class StableDiffusionXLPipeline:
         else:
             prog_all = prepared(list(anchor_conds) + list(mid_conds() if lazy_mids else mid_conds), guid=all_g)[0] if G else prog_a
         stream = torch.cuda.current_stream().cuda_stream
-        rows_a = [self._step_row(i, all_g[0], first=i == 0) for i in range(steps)]
+        rows_a = [sched.step_row(i, all_g[0], first=i == 0) for i in range(steps)]
         par_a = ops.step_params([r for r in rows_a for _ in range(A)], self.device).view(steps, A, 8) if A else None
-        par_all = ops.step_params([self._step_row(i, all_g[s], first=i == (0 if s < A else idx_injection)) for i in range(idx_injection, steps)
+        par_all = ops.step_params([sched.step_row(i, all_g[s], first=i == (0 if s < A else idx_injection)) for i in range(idx_injection, steps)
                                    for s in range(A + G)], self.device).view(-1, A + G, 8) if G else None
         shape1 = (1,) + tuple(ref_start.shape[1:])
         noise_a = noise_m = None
@@ -694,7 +666,7 @@ class StableDiffusionXLPipeline:
         # step but the schedule's last, so both kinds of run have noise at exactly the steps < nd_a
         nd_a, nm = noise_draws_per_run(sched, steps, 0), noise_draws_per_run(sched, steps, idx_injection)
         if nd_a > 0:              # sample-major draws: anchor 1, anchor 2 (those denoised here), then every mid branch
-            n_draw, keep = (G, list(range(G))) if noise_slots is None else (int(noise_slots[0]), list(noise_slots[1]))
+            n_draw, keep = self._noise_slots(noise_slots, G)
             flat = sched.draw_noise_many(A * nd_a + n_draw * nm, shape1, self.device)      # ONE launch on the device RNG
             # (contiguous per step: the step kernels take noise[i] by pointer)
             noise_a = flat[:A * nd_a].view(A, nd_a, *shape1[1:]).transpose(0, 1).contiguous() if A else None          # [nd_a, A, 4, L, L]
@@ -708,7 +680,7 @@ class StableDiffusionXLPipeline:
         traj_m: List[List[Optional[torch.Tensor]]] = [[None] * idx_injection for _ in range(G)]
         # mixing fractions / crossfeed coefficients live on the device: every step's parental mix (ONE pair of anchor
         # latents at G fractions) and crossfeed (G pairs) is one strided-slerp launch, no host pointer tables
-        n_lat = per_sample
+        n_lat = ref_start[0].numel()
         fr_dev = torch.tensor([float(f) for f in mid_fracts], dtype=torch.float64, device=self.device) if G else None
         coef_dev = torch.tensor([[float(mid_coeffs[g][i]) for g in range(G)] for i in range(steps)],
                                 dtype=torch.float64, device=self.device) if G else None
@@ -750,13 +722,8 @@ class StableDiffusionXLPipeline:
                     noise = None
                     if noise_m is not None and i < nd_a:
                         noise = torch.cat([noise_a[i], noise_m[i - idx_injection]]) if A else noise_m[i - idx_injection]
-                api.lb_scale_model_input_f16(lat.data_ptr(), prog.x_in.data_ptr(), params.data_ptr(), per_sample, n,
-                                             int(cfg), stream)
-                prog.tvals.fill_(float(sched.timesteps_np[i]))
-                prog.prog_step.launch(stream)
-                self.stats["unet_forwards"] += 1
-                self.stats["unet_samples"] += prog.B
-                out, hist, _ = self._device_step(lat, hists, prog.eps, params, noise, cfg, i, steps)      # (the batch changes size: no carry)
+                self._launch_unet_step(prog, lat, params, n, cfg, i, stream)
+                out, hist, _ = self._device_step(lat, hists, prog.eps, params, noise, cfg, i)      # (the batch changes size: no carry)
                 if deferred:            # the first small step is launched: now the host work the big batch needs (runs beside it)
                     deferred = False
                     prog_all, cond_ready = prepared(lambda: list(anchor_conds) + list(mid_conds()), side=self._side_stream, after=before_first, guid=all_g)

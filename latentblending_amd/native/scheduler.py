@@ -1,21 +1,26 @@
-"""Host side of the Euler / Euler-ancestral schedulers (diffusers 0.25 semantics for SDXL base
-and SDXL-Turbo).  Only the sigma / timestep tables and per-step scalar
-coefficients live here (float64 numpy); the tensor work — ``x / sqrt(sigma^2+1)``, CFG combine
-and the update — runs in ``lb_scale_model_input_f16`` / ``lb_euler_step_f16``.  ``NativeDDIMScheduler`` and
-``NativeLCMScheduler`` (few-step sampling: diffusers' ``LCMScheduler``) keep the same interface over an fp32 abar table;
-their tensor work is ``lb_ddim_step_f16`` and mode 2 of ``lb_euler_step_f16``.
+"""Host side of the native samplers: Euler / Euler-ancestral (diffusers 0.25 semantics for SDXL base and SDXL-Turbo; SURVEY.md
+Appendix B.2), DDIM (eta 0), the latent-consistency sampler (LCM) and DPM-Solver++ 2M on uniform or Karras sigmas.  Only the
+sigma / abar / timestep tables and the per-step scalar coefficients live here (``step_row``: Python floats, float64 numpy or
+0-dim fp32 tensors, as each sampler's diffusers counterpart forms them); the tensor work runs in ``lb_scale_model_input_f16``,
+``lb_euler_step_f16`` (Euler; mode 2 = LCM) and ``lb_ddim_step_f16`` (DDIM; bit 1 of ``cfg`` = DPM-Solver++ 2M).
+
+Every sampler derives from :class:`NativeScheduler`, which owns what they share - the schedule bookkeeping, the diffusers-style
+``scale_model_input`` / ``step`` pair the generic holder loop drives, the noise draws and the questions the native loops
+(native/pipe.py) ask: ``step_row``, ``device_step``, ``device_step_kwargs``, ``multistep``, ``noise_draws``.  A subclass adds
+its tables, ``set_timesteps``, ``step_row`` and the two launches.  ``make_scheduler`` maps a pipe's ``scheduler=`` name to one.
 
 Reference call sites: /root/reference/latentblending/diffusers_holder.py:42,53,247 (set_timesteps),
-:301 (order), :330 (scale_model_input), :356 (step).  Known answers: tests/golden/scheduler.json.
+:301 (order), :330 (scale_model_input), :356 (step).  Known answers: tests/golden/scheduler.json, tests/golden/sampler_rows.json.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
 from ..hip import ops
+from ..planner import noise_draws_per_run          # noqa: F401  (its home is the planner; importable from here as before)
 
 NUM_TRAIN_TIMESTEPS = 1000
 
@@ -24,6 +29,12 @@ def _sigma_table() -> np.ndarray:
     betas = np.linspace(0.00085 ** 0.5, 0.012 ** 0.5, NUM_TRAIN_TIMESTEPS, dtype=np.float64) ** 2
     alphas_cumprod = np.cumprod(1.0 - betas)
     return ((1 - alphas_cumprod) / alphas_cumprod) ** 0.5
+
+
+def _alphas_cumprod_f32() -> torch.Tensor:
+    """The abar table in fp32, built exactly as diffusers builds it (``torch.cumprod`` of fp32 alphas): DDIM's and LCM's."""
+    betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, NUM_TRAIN_TIMESTEPS, dtype=torch.float32) ** 2
+    return torch.cumprod(1.0 - betas, dim=0)
 
 
 class SeededDeviceNoise:
@@ -45,66 +56,58 @@ class SeededDeviceNoise:
         return torch.randn((int(n),) + tuple(shape[1:]), generator=self.gen, device=self.device, dtype=torch.float16)
 
 
-class NativeEulerScheduler:
-    order = 1
-    kind = "euler"
+class NativeScheduler:
+    """What every native sampler is to its two callers.  The native loops (native/pipe.py) upload ``step_row(i, guidance, first)``
+    for every step of a run and call ``device_step(x, eps, params, noise=, cfg=, **device_step_kwargs(i))`` once per step for the
+    whole batch; the generic diffusers-style loop calls ``scale_model_input`` / ``step`` with timesteps taken from ``timesteps``.
+    A subclass sets its tables in ``__init__`` BEFORE calling this one's (which installs the default schedule) and provides
+    ``set_timesteps`` (ending in ``_install``), ``step_row``, ``device_step`` and ``_step_tensors``."""
+    order = 1                    # model evaluations per step (as diffusers reports it; the engine's loops read this)
+    kind = ""
+    multistep = False            # True: ``device_step`` takes and returns a two-plane state (latents, previous x0 prediction)
+    ancestral = False            # the Euler-ancestral update (whether ANY per-step noise is drawn is ``draws_noise`` / ``noise_draws``)
+    draws_noise = False
+    init_noise_sigma = 1.0
+    default_steps = 30
 
-    def __init__(self, ancestral: bool, timestep_spacing: Optional[str] = None, device="cuda"):
-        self.ancestral = ancestral
-        self.timestep_spacing = timestep_spacing or ("trailing" if ancestral else "leading")
+    def __init__(self, device="cuda"):
         self.device = device
-        self._table = _sigma_table()
         self.noise_source = None          # callable(shape) -> tensor; None = device RNG
         self._step_index = None
-        self.set_timesteps(30)
+        self.set_timesteps(self.default_steps)
 
-    # ---- tables -----------------------------------------------------------------------------
-    def set_timesteps(self, num_inference_steps: int, device=None):
-        n = int(num_inference_steps)
-        if self.timestep_spacing == "trailing":
-            ts = np.round(np.arange(NUM_TRAIN_TIMESTEPS, 0, -NUM_TRAIN_TIMESTEPS / n)) - 1
-        elif self.timestep_spacing == "leading":
-            ts = (np.arange(0, n) * (NUM_TRAIN_TIMESTEPS // n)).round()[::-1].copy() + 1   # steps_offset = 1
-        else:
-            raise ValueError(f"unsupported timestep_spacing {self.timestep_spacing}")
-        ts = ts.astype(np.float32)
-        sig = np.interp(ts, np.arange(0, NUM_TRAIN_TIMESTEPS), self._table)
-        self.sigmas_np = np.concatenate([sig, [0.0]]).astype(np.float32)
-        self.timesteps_np = ts
-        self.timesteps = torch.from_numpy(ts)                  # host tensor: iterating it never syncs
-        self.sigmas = torch.from_numpy(self.sigmas_np)
+    # ---- schedule ---------------------------------------------------------------------------
+    def _install(self, timesteps: np.ndarray, n: int):
+        """The end of every ``set_timesteps``: the schedule's timesteps, and a fresh run (no step located, no history)."""
+        self.timesteps_np = timesteps.astype(np.float32)
+        self.timesteps = torch.from_numpy(self.timesteps_np)   # host tensor: iterating it never syncs
         self.num_inference_steps = n
         self._step_index = None
+        self._reset_history()
 
-    @property
-    def init_noise_sigma(self) -> float:
-        m = float(self.sigmas_np.max())
-        return m if self.timestep_spacing in ("linspace", "trailing") else (m * m + 1) ** 0.5
+    def _reset_history(self):
+        self._m1 = None                   # (a multistep sampler's previous x0 prediction under ``step``; the others never set it)
 
     def index_of(self, t) -> int:
-        hits = np.nonzero(self.timesteps_np == float(t))[0]
-        return int(hits[0])
+        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
 
-    def step_row(self, i: int, guidance: float = 0.0) -> Tuple[float, float, float, float, float]:
-        """(sigma_from, sigma_next, sigma_up, guidance, dt) for ``lb_euler_step_f16``; computed in
-        Python floats exactly like the scheduler's own scalar arithmetic."""
-        s_from, s_to = float(self.sigmas_np[i]), float(self.sigmas_np[i + 1])
-        if self.ancestral:
-            s_up = (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
-            s_down = (s_to ** 2 - s_up ** 2) ** 0.5
-            return (s_from, s_down, s_up, guidance, s_down - s_from)
-        return (s_from, s_to, 0.0, guidance, s_to - s_from)
-
-    # ---- diffusers-style tensor API (generic holder loop / foreign callers) ------------------
     def _locate(self, t) -> int:
         if self._step_index is None:
             self._step_index = self.index_of(float(t))
         return self._step_index
 
-    def scale_model_input(self, sample: torch.Tensor, timestep) -> torch.Tensor:
-        i = self._locate(timestep)
-        params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
-        return ops.scale_model_input(sample.contiguous(), params)
+    def is_last(self, i: int) -> bool:
+        return i == self.num_inference_steps - 1
+
+    def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
+        """The scalar coefficients of step ``i`` for the sampler's step kernel.  ``first`` = this is the first step the sample
+        executes: a multistep sampler has no history then; a single-step sampler returns the same row either way."""
+        raise NotImplementedError
+
+    # ---- noise ------------------------------------------------------------------------------
+    def noise_draws(self, steps: int, idx_start: int) -> int:
+        """Latent-shaped noise draws one run from ``idx_start`` of a ``steps``-step schedule consumes."""
+        return 0
 
     def draw_noise(self, shape, device) -> torch.Tensor:
         if self.noise_source is not None:
@@ -125,55 +128,114 @@ class NativeEulerScheduler:
             return many(n, tuple(shape)).to(device=device, dtype=torch.float16)
         return torch.cat([self.draw_noise(shape, device) for _ in range(n)])
 
+    # ---- the native loops' batched step ------------------------------------------------------
+    def device_step(self, x, eps, params, noise=None, cfg=False, **kw):
+        """One launch for all samples of the batch, per-sample rows in ``params``."""
+        raise NotImplementedError
+
+    def device_step_kwargs(self, i: int) -> dict:
+        """What ``device_step`` of step ``i`` takes beside the tensors (``params`` is usually a view of one upload of all steps'
+        rows, which carries no host mirror: what the launcher must know about the step, the scheduler says here)."""
+        return {}
+
+    # ---- diffusers-style tensor API (generic holder loop / foreign callers) ------------------
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        return sample
+
     def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
         i = self._locate(timestep)
-        B = sample.shape[0]
-        params = ops.step_params([self.step_row(i)] * B, sample.device)
-        noise = self.draw_noise(sample.shape, sample.device) if self.ancestral else None
-        out = ops.euler_step(sample.contiguous(), model_output.contiguous(), params, noise=noise,
-                             ancestral=self.ancestral)
+        first = self.multistep and self._m1 is None
+        params = ops.step_params([self.step_row(i, first=first)] * sample.shape[0], sample.device)
+        out = self._step_tensors(i, sample, model_output.contiguous(), params)
         self._step_index += 1
         return (out,)
 
-    def device_step(self, latents, eps, params, noise=None, cfg=False):
-        """The batched step of the native loops (native/pipe.py): one launch for all samples, per-sample rows in ``params``."""
-        return ops.euler_step(latents, eps, params, noise=noise, cfg=cfg, ancestral=self.ancestral)
+    def _step_tensors(self, i: int, sample, eps, params) -> torch.Tensor:
+        raise NotImplementedError
 
 
-class NativeDDIMScheduler:
+def _no_noise(self, shape, device) -> torch.Tensor:
+    """``draw_noise`` of a deterministic sampler (never called; it must not consume the device RNG)."""
+    return torch.zeros(shape, device=device, dtype=torch.float16)
+
+
+class NativeEulerScheduler(NativeScheduler):
+    kind = "euler"
+
+    def __init__(self, ancestral: bool, timestep_spacing: Optional[str] = None, device="cuda"):
+        self.ancestral = ancestral
+        self.timestep_spacing = timestep_spacing or ("trailing" if ancestral else "leading")
+        self._table = _sigma_table()
+        super().__init__(device)
+
+    draws_noise = property(lambda self: self.ancestral)
+
+    # ---- tables -----------------------------------------------------------------------------
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n = int(num_inference_steps)
+        if self.timestep_spacing == "trailing":
+            ts = np.round(np.arange(NUM_TRAIN_TIMESTEPS, 0, -NUM_TRAIN_TIMESTEPS / n)) - 1
+        elif self.timestep_spacing == "leading":
+            ts = (np.arange(0, n) * (NUM_TRAIN_TIMESTEPS // n)).round()[::-1].copy() + 1   # steps_offset = 1
+        else:
+            raise ValueError(f"unsupported timestep_spacing {self.timestep_spacing}")
+        ts = ts.astype(np.float32)
+        sig = np.interp(ts, np.arange(0, NUM_TRAIN_TIMESTEPS), self._table)
+        self.sigmas_np = np.concatenate([sig, [0.0]]).astype(np.float32)
+        self.sigmas = torch.from_numpy(self.sigmas_np)
+        self._install(ts, n)
+
+    @property
+    def init_noise_sigma(self) -> float:
+        m = float(self.sigmas_np.max())
+        return m if self.timestep_spacing in ("linspace", "trailing") else (m * m + 1) ** 0.5
+
+    def step_row(self, i: int, guidance: float = 0.0, first: bool = False) -> Tuple[float, float, float, float, float]:
+        """(sigma_from, sigma_next, sigma_up, guidance, dt) for ``lb_euler_step_f16``; computed in
+        Python floats exactly like the scheduler's own scalar arithmetic."""
+        s_from, s_to = float(self.sigmas_np[i]), float(self.sigmas_np[i + 1])
+        if self.ancestral:
+            s_up = (s_to ** 2 * (s_from ** 2 - s_to ** 2) / s_from ** 2) ** 0.5
+            s_down = (s_to ** 2 - s_up ** 2) ** 0.5
+            return (s_from, s_down, s_up, guidance, s_down - s_from)
+        return (s_from, s_to, 0.0, guidance, s_to - s_from)
+
+    def noise_draws(self, steps: int, idx_start: int) -> int:
+        return max(0, int(steps) - int(idx_start)) if self.ancestral else 0
+
+    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
+        i = self._locate(timestep)
+        params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
+        return ops.scale_model_input(sample.contiguous(), params)
+
+    def device_step(self, x, eps, params, noise=None, cfg=False, **kw):
+        return ops.euler_step(x, eps, params, noise=noise, cfg=cfg, ancestral=self.ancestral)
+
+    def _step_tensors(self, i, sample, eps, params):
+        noise = self.draw_noise(sample.shape, sample.device) if self.ancestral else None
+        return ops.euler_step(sample.contiguous(), eps, params, noise=noise, ancestral=self.ancestral)
+
+
+class NativeDDIMScheduler(NativeScheduler):
     """DDIM (eta = 0, epsilon prediction) as diffusers configures it for SD / SDXL: scaled-linear betas, leading spacing,
     steps_offset = 1, set_alpha_to_one = False, clip_sample = False.  Host side = the fp32 abar table built exactly as
     diffusers builds it (``torch.cumprod`` of fp32 alphas) and the per-step coefficients; the tensor work is
-    ``lb_ddim_step_f16``.  Same interface as :class:`NativeEulerScheduler` (``step_row`` / ``device_step`` for the native loops,
-    ``scale_model_input`` / ``step`` for the generic diffusers-style loop); ``scale_model_input`` is the identity and
-    ``init_noise_sigma`` is 1.  Reached from /root/reference/latentblending/diffusers_holder.py:330,356 when a pipe carries
-    this scheduler (``NativeSDXLPipe(scheduler="ddim")``); the reference's own SDXL pipes carry Euler schedulers (:42)."""
-    order = 1
+    ``lb_ddim_step_f16``.  ``scale_model_input`` is the identity and ``init_noise_sigma`` is 1.  Reached from
+    /root/reference/latentblending/diffusers_holder.py:330,356 when a pipe carries this scheduler
+    (``NativeSDXLPipe(scheduler="ddim")``); the reference's own SDXL pipes carry Euler schedulers (:42)."""
     kind = "ddim"
-    ancestral = False
-    init_noise_sigma = 1.0
 
     def __init__(self, device="cuda"):
-        self.device = device
-        betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, NUM_TRAIN_TIMESTEPS, dtype=torch.float32) ** 2
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)            # fp32, as diffusers holds it
+        self.alphas_cumprod = _alphas_cumprod_f32()                         # fp32, as diffusers holds it
         self.final_alpha_cumprod = self.alphas_cumprod[0]                   # set_alpha_to_one = False
-        self.noise_source = None
-        self._step_index = None
-        self.set_timesteps(30)
+        super().__init__(device)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         n = int(num_inference_steps)
         ratio = NUM_TRAIN_TIMESTEPS // n
         ts = (np.arange(0, n) * ratio).round()[::-1].copy().astype(np.int64) + 1          # leading, steps_offset = 1
-        self.timesteps_np = ts.astype(np.float32)
-        self.timesteps = torch.from_numpy(self.timesteps_np)
-        self.num_inference_steps = n
         self._ratio = ratio
-        self._step_index = None
-
-    def index_of(self, t) -> int:
-        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
+        self._install(ts, n)
 
     def alpha_pair(self, i: int):
         """(abar_t, abar_prev) of step ``i`` as 0-dim fp32 tensors (prev_timestep = t - 1000 // n; below 0: final_alpha_cumprod)."""
@@ -181,7 +243,7 @@ class NativeDDIMScheduler:
         prev = t - self._ratio
         return self.alphas_cumprod[t], (self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod)
 
-    def step_row(self, i: int, guidance: float = 0.0):
+    def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
         """(0, sqrt(abar_t), sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t)) in fp32 tensor
         arithmetic, the scalars diffusers forms inside DDIMScheduler.step (beta_prod_t ** 0.5, alpha_prod_t ** 0.5, ...).  The last
         one is the fp32 reciprocal the device library forms when a tensor is divided by a 0-dim host tensor (its true-division
@@ -191,26 +253,13 @@ class NativeDDIMScheduler:
         inv = torch.ones((), dtype=torch.float32) / sa_t.to(torch.float32)
         return (0.0, float(sa_t), float(a_p ** 0.5), guidance, float((1 - a_t) ** 0.5), float((1 - a_p) ** 0.5), float(inv))
 
-    def _locate(self, t) -> int:
-        if self._step_index is None:
-            self._step_index = self.index_of(float(t))
-        return self._step_index
+    draw_noise = _no_noise                                      # (eta = 0)
 
-    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
-        return sample
+    def device_step(self, x, eps, params, noise=None, cfg=False, **kw):
+        return ops.ddim_step(x, eps, params, cfg=cfg)
 
-    def draw_noise(self, shape, device) -> torch.Tensor:        # (never used: eta = 0)
-        return torch.zeros(shape, device=device, dtype=torch.float16)
-
-    def device_step(self, latents, eps, params, noise=None, cfg=False):
-        return ops.ddim_step(latents, eps, params, cfg=cfg)
-
-    def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
-        i = self._locate(timestep)
-        params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
-        out = ops.ddim_step(sample.contiguous(), model_output.contiguous(), params)
-        self._step_index += 1
-        return (out,)
+    def _step_tensors(self, i, sample, eps, params):
+        return ops.ddim_step(sample.contiguous(), eps, params)
 
 
 LCM_ORIGINAL_STEPS = 50          # diffusers 0.25.0 LCMScheduler: original_inference_steps
@@ -226,36 +275,21 @@ def lcm_boundary_scalings(t: int) -> Tuple[float, float]:
     return sd2 / (s ** 2 + sd2), s / (s ** 2 + sd2) ** 0.5
 
 
-def noise_draws_per_run(sched, steps: int, idx_start: int) -> int:
-    """Latent-shaped noise draws one denoising run from ``idx_start`` consumes under ``sched``: a scheduler that knows says so
-    itself (``noise_draws``: LCM draws at every step but the schedule's last); an ancestral one draws once per step; others none."""
-    own = getattr(sched, "noise_draws", None)
-    if own is not None:
-        return int(own(steps, idx_start))
-    return max(0, int(steps) - int(idx_start)) if getattr(sched, "ancestral", False) else 0
-
-
-class NativeLCMScheduler:
+class NativeLCMScheduler(NativeScheduler):
     """Latent-consistency multistep sampler (Luo et al. 2023, "Latent Consistency Models", algorithm 3) as diffusers 0.25.0's
     ``LCMScheduler`` configures it for SDXL: scaled-linear betas, original_inference_steps = 50, timestep_scaling = 10,
     sigma_data = 0.5, epsilon prediction, no thresholding / clipping.  Restated from the published algorithm and that class's
-    documented behaviour - not checked against diffusers itself.  Host side = the fp32 abar table (as the DDIM class builds it),
-    the timestep selection and the per-step coefficients; the tensor work is mode 2 of ``lb_euler_step_f16``.  Same interface as
-    :class:`NativeDDIMScheduler`; ``scale_model_input`` is the identity and ``init_noise_sigma`` is 1.  Every step but the LAST
-    of the schedule re-noises the denoised latent with one fresh fp16 draw (``noise_draws``)."""
-    order = 1
+    documented behaviour - not checked against diffusers itself.  Host side = the fp32 abar table (DDIM's), the timestep
+    selection and the per-step coefficients; the tensor work is mode 2 of ``lb_euler_step_f16``.  ``scale_model_input`` is the
+    identity and ``init_noise_sigma`` is 1.  Every step but the LAST of the schedule re-noises the denoised latent with one fresh
+    fp16 draw (``noise_draws``)."""
     kind = "lcm"
-    ancestral = False            # (not the Euler-ancestral update; whether noise is drawn is ``draws_noise`` / ``noise_draws``)
-    draws_noise = True
-    init_noise_sigma = 1.0
+    draws_noise = True           # (``ancestral`` stays False: this is not the Euler-ancestral update)
+    default_steps = 4
 
     def __init__(self, device="cuda"):
-        self.device = device
-        betas = torch.linspace(0.00085 ** 0.5, 0.012 ** 0.5, NUM_TRAIN_TIMESTEPS, dtype=torch.float32) ** 2
-        self.alphas_cumprod = torch.cumprod(1.0 - betas, dim=0)            # fp32, as diffusers holds it
-        self.noise_source = None
-        self._step_index = None
-        self.set_timesteps(4)
+        self.alphas_cumprod = _alphas_cumprod_f32()                         # fp32, as diffusers holds it
+        super().__init__(device)
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         n = int(num_inference_steps)
@@ -264,21 +298,12 @@ class NativeLCMScheduler:
         origin = np.arange(1, LCM_ORIGINAL_STEPS + 1) * (NUM_TRAIN_TIMESTEPS // LCM_ORIGINAL_STEPS) - 1
         skip = LCM_ORIGINAL_STEPS // n
         ts = origin[::-1][::skip][:n].copy().astype(np.int64)
-        self.timesteps_np = ts.astype(np.float32)
-        self.timesteps = torch.from_numpy(self.timesteps_np)
-        self.num_inference_steps = n
-        self._step_index = None
-
-    def index_of(self, t) -> int:
-        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
+        self._install(ts, n)
 
     def noise_draws(self, steps: int, idx_start: int) -> int:
         return max(0, int(steps) - int(idx_start) - 1)
 
-    def is_last(self, i: int) -> bool:
-        return i == self.num_inference_steps - 1
-
-    def step_row(self, i: int, guidance: float = 0.0):
+    def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
         """(0, c_skip, sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t), c_out): the boundary
         scalings in Python floats, the roots and the reciprocal in 0-dim fp32 tensor arithmetic (as ``NativeDDIMScheduler.step_row``
         forms its own).  The last step of the schedule has no previous timestep: its slots 2 and 5 are 0, which is how the kernel
@@ -294,29 +319,17 @@ class NativeLCMScheduler:
             sa_p, sb_p = float(a_p ** 0.5), float((1 - a_p) ** 0.5)
         return (0.0, c_skip, sa_p, guidance, float((1 - a_t) ** 0.5), sb_p, float(inv), c_out)
 
-    def _locate(self, t) -> int:
-        if self._step_index is None:
-            self._step_index = self.index_of(float(t))
-        return self._step_index
+    def device_step(self, x, eps, params, noise=None, cfg=False, last: Optional[bool] = None, **kw):
+        """``last``: the loop's statement that this is the schedule's last step for every sample of the batch - only then may
+        ``noise`` be None (the launcher never reads the device rows back)."""
+        return ops.lcm_step(x, eps, params, noise=noise, cfg=cfg, all_last=last)
 
-    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
-        return sample
+    def device_step_kwargs(self, i: int) -> dict:
+        return {"last": self.is_last(i)}
 
-    draw_noise = NativeEulerScheduler.draw_noise
-    draw_noise_many = NativeEulerScheduler.draw_noise_many
-
-    def device_step(self, latents, eps, params, noise=None, cfg=False, last: Optional[bool] = None):
-        """``last``: the loop's statement that this is the schedule's last step for every sample of the batch (``params`` is
-        usually a view of one upload of all steps' rows, which carries no host mirror) - only then may ``noise`` be None."""
-        return ops.lcm_step(latents, eps, params, noise=noise, cfg=cfg, all_last=last)
-
-    def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
-        i = self._locate(timestep)
-        params = ops.step_params([self.step_row(i)] * sample.shape[0], sample.device)
+    def _step_tensors(self, i, sample, eps, params):
         noise = None if self.is_last(i) else self.draw_noise(sample.shape, sample.device)
-        out = ops.lcm_step(sample.contiguous(), model_output.contiguous(), params, noise=noise)
-        self._step_index += 1
-        return (out,)
+        return ops.lcm_step(sample.contiguous(), eps, params, noise=noise)
 
 
 KARRAS_RHO = 7.0
@@ -362,33 +375,26 @@ def dpmpp_2m_row(sigmas: np.ndarray, i: int, guidance: float = 0.0, first: bool 
     return (0.0, s_i, s_n / s_i, guidance, c0, 0.5 * c0, 1.0 / a_i, 1.0 / r0)
 
 
-class NativeDPMSolverPP2MScheduler:
+class NativeDPMSolverPP2MScheduler(NativeScheduler):
     """DPM-Solver++ 2M (Lu et al. 2022, "DPM-Solver++", algorithm 2: second-order multistep, data prediction) in the form diffusers'
     ``DPMSolverMultistepScheduler`` takes with algorithm_type "dpmsolver++", solver_type "midpoint", final_sigmas_type "zero" and
     epsilon prediction, over uniform ("leading", steps_offset 1) or Karras (Karras et al. 2022, eq. 5, rho = 7) sigmas - what user
     interfaces call "DPM++ 2M" / "DPM++ 2M Karras".  Restated from the paper and that class's documented behaviour - not checked
     against diffusers itself.  Host side = the float64 sigma table (``_sigma_table``, as for Euler), the schedule and the per-step
-    coefficients, each rounded ONCE to fp32 on upload; the tensor work is bit 1 of ``cfg`` of ``lb_ddim_step_f16``.  Same interface
-    as :class:`NativeDDIMScheduler`, except that the sampler has a history: ``device_step`` takes and returns a two-plane state
-    (latents, previous x0 prediction), and ``step_row`` takes ``first`` - the first step a sample executes has no history and is
-    first order, like the schedule's last step (whose target sigma is 0).  The reference's restartable loop calls
-    ``set_timesteps`` at the start of every run, which empties a multistep scheduler's history: a branch entering at
-    ``idx_start > 0`` starts first order too."""
-    order = 1                    # model evaluations per step (as diffusers reports it; the engine's loops read this)
+    coefficients, each rounded ONCE to fp32 on upload; the tensor work is bit 1 of ``cfg`` of ``lb_ddim_step_f16``.  The sampler
+    has a history (``multistep``): ``device_step`` takes and returns a two-plane state (latents, previous x0 prediction), and
+    ``step_row`` heeds ``first`` - the first step a sample executes has no history and is first order, like the schedule's last
+    step (whose target sigma is 0).  The reference's restartable loop calls ``set_timesteps`` at the start of every run, which
+    empties a multistep scheduler's history: a branch entering at ``idx_start > 0`` starts first order too."""
     solver_order = 2
     kind = "dpmpp_2m"
     multistep = True
-    ancestral = False
-    init_noise_sigma = 1.0
+    default_steps = 20
 
     def __init__(self, use_karras_sigmas: bool = False, device="cuda"):
         self.use_karras_sigmas = bool(use_karras_sigmas)
-        self.device = device
         self._table = _sigma_table()
-        self.noise_source = None
-        self._step_index = None
-        self._m1 = None
-        self.set_timesteps(20)
+        super().__init__(device)
 
     # ---- tables -----------------------------------------------------------------------------
     def _schedule(self, n: int):
@@ -409,53 +415,49 @@ class NativeDPMSolverPP2MScheduler:
             raise ValueError(f"NativeDPMSolverPP2MScheduler: the timesteps of a {n}-step schedule are not strictly decreasing "
                              f"inside 0..{NUM_TRAIN_TIMESTEPS - 1} (the UNet would see one timestep twice, or one it was never trained on); the largest valid step count here is {best}")
         self.sigmas_np = sig                                                # float64 [n + 1]; sigma_n = 0
-        self.timesteps_np = ts.astype(np.float32)
-        self.timesteps = torch.from_numpy(self.timesteps_np)
         self.sigmas = torch.from_numpy(self.sigmas_np.astype(np.float32))
-        self.num_inference_steps = n
-        self._step_index = None
-        self._m1 = None
-
-    def index_of(self, t) -> int:
-        return int(np.nonzero(self.timesteps_np == float(t))[0][0])
-
-    def noise_draws(self, steps: int, idx_start: int) -> int:
-        return 0
-
-    def is_last(self, i: int) -> bool:
-        return i == self.num_inference_steps - 1
+        self._install(ts, n)
 
     def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
         """The row of step ``i`` (``dpmpp_2m_row`` over this schedule's sigmas).  ``first`` = the sample has no history at this
         step - the first step it executes: a first-order row."""
         return dpmpp_2m_row(self.sigmas_np, i, guidance, first)
 
-    # ---- diffusers-style tensor API (generic holder loop / foreign callers) ------------------
-    def _locate(self, t) -> int:
-        if self._step_index is None:
-            self._step_index = self.index_of(float(t))
-        return self._step_index
+    draw_noise = _no_noise                                      # (the solver is deterministic)
 
-    def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
-        return sample
+    def device_step(self, x, eps, params, noise=None, cfg=False, out=None, **kw):
+        """``x`` [2, B, ...] (latents, previous x0 prediction) -> the next state."""
+        return ops.dpmpp2m_step(x, eps, params, cfg=cfg, out=out)
 
-    def draw_noise(self, shape, device) -> torch.Tensor:        # (never used: the solver is deterministic)
-        return torch.zeros(shape, device=device, dtype=torch.float16)
-
-    def device_step(self, state, eps, params, noise=None, cfg=False, out=None):
-        """The batched step of the native loops: ``state`` [2, B, ...] (latents, previous x0 prediction) -> the next state."""
-        return ops.dpmpp2m_step(state, eps, params, cfg=cfg, out=out)
-
-    def step(self, model_output, timestep, sample, generator=None, return_dict=False, **_):
+    def _step_tensors(self, i, sample, eps, params):
         """One step with the history kept HERE (``_m1``, the previous call's x0 prediction; ``set_timesteps`` drops it)."""
-        i = self._locate(timestep)
-        first = self._m1 is None
-        params = ops.step_params([self.step_row(i, first=first)] * sample.shape[0], sample.device)
         state = torch.empty((2,) + tuple(sample.shape), dtype=torch.float16, device=sample.device)
         state[0].copy_(sample)
-        if not first:
+        if self._m1 is not None:
             state[1].copy_(self._m1)
-        out = ops.dpmpp2m_step(state, model_output.contiguous(), params)
+        out = ops.dpmpp2m_step(state, eps, params)
         self._m1 = out[1]
-        self._step_index += 1
-        return (out[0],)
+        return out[0]
+
+
+SCHEDULER_NAMES = ("euler", "ddim", "lcm", "dpmpp_2m", "dpmpp_2m_karras")
+_NAMES_TEXT = "'euler', 'ddim' or 'lcm'; also 'dpmpp_2m', 'dpmpp_2m_karras'"
+
+
+def make_scheduler(name, turbo: bool, device) -> NativeScheduler:
+    """The sampler a pipe's ``scheduler=`` argument names (case-insensitive, surrounding blanks ignored).  None or "euler" = the
+    reference pipes' choice: Euler-ancestral for Turbo, Euler for base.  Anything else raises ``ValueError`` (a misspelt
+    "DDIM " or a scheduler object used to fall through to Euler silently)."""
+    if name is not None and not isinstance(name, str):
+        raise ValueError(f"NativeSDXLPipe: scheduler must be None, {_NAMES_TEXT} "
+                         f"(got an object of type {type(name).__name__})")
+    name = "euler" if name is None else name.strip().lower()
+    if name not in SCHEDULER_NAMES:
+        raise ValueError(f"NativeSDXLPipe: unknown scheduler {name!r} (None, {_NAMES_TEXT})")
+    if name == "euler":
+        return NativeEulerScheduler(ancestral=turbo, device=device)
+    if name == "ddim":
+        return NativeDDIMScheduler(device=device)
+    if name == "lcm":
+        return NativeLCMScheduler(device=device)
+    return NativeDPMSolverPP2MScheduler(use_karras_sigmas=name.endswith("karras"), device=device)

@@ -113,6 +113,23 @@ def time_based_branching(num_steps: int, depth_strength: float, dt_unet_step: fl
     return levels, stems
 
 
+def draws_noise(sched) -> bool:
+    """Does this sampler consume per-step noise?  Euler-ancestral does (``ancestral``); so does the latent-consistency sampler
+    (``draws_noise``).  Duck-typed: the native schedulers, the oracle's, the tests' restatements and diffusers' own all pass here."""
+    return bool(getattr(sched, "ancestral", False) or getattr(sched, "draws_noise", False))
+
+
+def noise_draws_per_run(sched, steps: int, idx_start: int) -> int:
+    """Latent-shaped noise draws ONE denoising run from ``idx_start`` consumes under ``sched`` - THE noise-accounting rule: the
+    native loops size their draws by it and a farm rank skips other ranks' draws by it, so a shared stream stays aligned.  A
+    scheduler that knows says so itself (``noise_draws``: LCM draws at every step but the schedule's last); otherwise an
+    ancestral one draws once per step and any other none."""
+    own = getattr(sched, "noise_draws", None)
+    if own is not None:
+        return int(own(steps, idx_start))
+    return max(0, int(steps) - int(idx_start)) if getattr(sched, "ancestral", False) else 0
+
+
 def transition_census(num_steps: int, levels: Sequence[int], stems: Sequence[int]) -> dict:
     """Work count of one ``run_transition`` with fresh anchors (SURVEY.md §3.6 schema)."""
     mid = int(np.sum(stems))
