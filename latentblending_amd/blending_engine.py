@@ -123,6 +123,10 @@ class BlendingEngine:
         self.text_embedding2 = None
         self.image1_lowres = None
         self.image2_lowres = None
+        self.anchor_image1 = None           # image anchors (set_anchor_image1 / 2): the picture a transition starts from / arrives at
+        self.anchor_image2 = None
+        self.anchor_image_strength1 = 0.5
+        self.anchor_image_strength2 = 0.5
         self.negative_prompt = None
         self.stats = {}
         self._preset_anchor_frames = None      # (frame of anchor 1, frame of anchor 2) for the next transition: see preset_anchors
@@ -253,6 +257,34 @@ class BlendingEngine:
     def set_image2(self, image: Image):
         self.image2_lowres = image
 
+    def set_anchor_image1(self, image, strength: float = 0.5):
+        """Start the next transitions FROM a picture the user has (a photo, a frame of the previous movie, an earlier render)
+        instead of one invented from ``prompt1`` and ``seed1``.  The anchor's trajectory - the tree mixes from a latent at EVERY
+        step - is defined from the picture's latents ``x0`` (``DiffusersHolder.image2latent``) and the unit noise of the
+        anchor's seed, ``eps = get_unit_noise(seed1)``, by diffusers' img2img rule: ``t_start = steps - min(int(steps *
+        strength), steps)``; the entries of the steps below ``t_start`` are the forward-noised picture ``a x0 + b eps`` with
+        ``(a, b) = scheduler.noise_level(i + 1)`` (the latent AFTER step i), and the steps from ``t_start`` on are the ordinary
+        denoising from ``entry[t_start - 1]`` under the anchor's own conditioning (``prompt1``) and guidance.  ``strength`` 0: the
+        anchor IS the picture, no UNet evaluation; 1: re-imagined from full noise.  Mid branches inject and crossfeed from it
+        exactly as from a prompt anchor.  ``strength`` outside [0, 1] raises ``ValueError``.  A picture of another size is
+        resized to the engine's size (PIL, LANCZOS) when the transition RUNS, so ``set_dimensions`` / ``set_num_inference_steps``
+        called afterwards are honoured; one that has the size already is not resampled.  Not available under a farm of more
+        than one rank (``run_transition`` raises ``NotImplementedError``)."""
+        planner.img2img_start(1, strength)
+        self.anchor_image1, self.anchor_image_strength1 = image, float(strength)
+
+    def set_anchor_image2(self, image, strength: float = 0.5):
+        """Arrive AT a picture: as ``set_anchor_image1`` with ``prompt2`` / ``seed2``.  The second anchor takes the branch-1
+        crossfeed as before over the steps it denoises; coefficients of steps below ``t_start`` have nothing to act on (those
+        entries are the forward-noised picture) and are ignored."""
+        planner.img2img_start(1, strength)
+        self.anchor_image2, self.anchor_image_strength2 = image, float(strength)
+
+    def clear_anchor_images(self):
+        """Both anchors come from their prompts and seeds again."""
+        self.anchor_image1 = self.anchor_image2 = None
+        self.anchor_image_strength1 = self.anchor_image_strength2 = 0.5
+
     def set_num_inference_steps(self, num_inference_steps=None):
         if num_inference_steps is None:
             num_inference_steps = 4 if self.dh.is_sdxl_turbo else 30
@@ -305,6 +337,9 @@ class BlendingEngine:
 
         steps = self.num_inference_steps
         use_frontier = self.frontier_width > 1 or self.farm is not None
+        if (self.anchor_image1 is not None or self.anchor_image2 is not None) and self._farm_on():
+            raise NotImplementedError("image anchors are not available under a farm of more than one rank "
+                                      "(the ranks' noise streams would have to be aligned around the anchors' own runs)")
         keep1 = recycle_img1 and len(self.tree_latents[0]) == steps
         keep2 = recycle_img2 and len(self.tree_latents[-1]) == steps
         # frames handed over by preset_anchors belong to the trajectories it installed: an anchor that is denoised again
@@ -313,6 +348,17 @@ class BlendingEngine:
         self._anchor_frames_given = (preset[0] if preset is not None and keep1 else None,
                                      preset[1] if preset is not None and keep2 else None)
         prefilled = None
+        # an image anchor that is not recycled is computed first and handed on as a kept trajectory: the sequential, batched and
+        # fused anchor paths below then serve it like any recycled anchor (its frame is decoded with the others)
+        if self.anchor_image1 is not None and not keep1:
+            self.compute_latents_image(1)
+            keep1 = True
+        if self.anchor_image2 is not None and not keep2:
+            if self.branch1_crossfeed_power > 0.0 and not keep1:
+                self.compute_latents1()                      # (the crossfeed's source must exist first, as in the sequential order)
+                keep1 = True
+            self.compute_latents_image(2)
+            keep2 = True
         restore_noise = self._farm_begin(keep1, keep2) if self._farm_on() else None
         try:
             recycled_ok = self.fuse_recycled_anchor and not self._farm_on()
@@ -429,6 +475,58 @@ class BlendingEngine:
             traj = self.run_diffusion(cond, start)
         self.tree_latents[-1] = traj
         return self.dh.latent2image(traj[-1]) if return_image else traj
+
+    def _anchor_picture(self, image):
+        """The picture at the engine's size: resized with PIL's LANCZOS filter unless it has that size already."""
+        w, h = self.dh.width_img, self.dh.height_img
+        if isinstance(image, Image.Image):
+            if image.size == (w, h):
+                return image
+            return image.convert("RGB").resize((w, h), Image.LANCZOS)
+        arr = np.asarray(image)
+        if arr.ndim != 3 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
+            raise ValueError(f"image anchor: expected a PIL image or a uint8 [H, W, 3] picture (got {arr.dtype} {arr.shape})")
+        if arr.shape[:2] == (h, w):
+            return image
+        return Image.fromarray(arr).resize((w, h), Image.LANCZOS)
+
+    def compute_latents_image(self, which: int):
+        """Full trajectory of image anchor ``which`` (1 or 2), as ``set_anchor_image1`` defines it; stored in ``tree_latents[0]``
+        / ``[-1]`` and returned.  Steps below ``t_start`` cost no UNet evaluation."""
+        assert which in (1, 2)
+        image, strength, seed = ((self.anchor_image1, self.anchor_image_strength1, self.seed1) if which == 1 else
+                                 (self.anchor_image2, self.anchor_image_strength2, self.seed2))
+        assert image is not None, f"set_anchor_image{which}(...) first"
+        steps = self.num_inference_steps
+        t_start = planner.img2img_start(steps, strength)
+        self.dh.set_num_inference_steps(steps)
+        level = getattr(self.dh.pipe.scheduler, "noise_level", None)
+        if level is None:
+            raise ValueError(f"image anchors need a scheduler that states its noise levels (noise_level(i) -> (a, b)); "
+                             f"{type(self.dh.pipe.scheduler).__name__} does not")
+        x0 = self.dh.image2latent(self._anchor_picture(image))
+        eps = self.dh.get_unit_noise(seed)
+
+        def noised(i):
+            """``a x0 + b eps`` at the level a sample has ENTERING step ``i``: evaluated in fp32, rounded to fp16 once."""
+            a, b = level(i)
+            if (a, b) == (1.0, 0.0):
+                return x0.clone()
+            return (a * x0.float() + b * eps.float().to(x0.device)).to(torch.float16)
+        traj = [noised(i + 1) for i in range(t_start)]
+        if t_start < steps:
+            cond = self.get_mixed_conditioning(0 if which == 1 else 1)
+            start = traj[t_start - 1] if t_start > 0 else noised(0)
+            if which == 2 and self.branch1_crossfeed_power > 0.0:
+                coeffs = planner.anchor_crossfeed_coeffs(steps, self.branch1_crossfeed_power, self.branch1_crossfeed_range,
+                                                         self.branch1_crossfeed_decay)
+                tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start, list_latents_mixing=self.tree_latents[0],
+                                          mixing_coeffs=coeffs)
+            else:
+                tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start)
+            traj += list(tail[t_start:])
+        self.tree_latents[0 if which == 1 else -1] = traj
+        return traj
 
     def _compute_anchors_batched(self):
         """Both anchors as ONE batch-2 denoising run (native pipes; they are independent when the
@@ -1107,6 +1205,9 @@ class BlendingEngine:
         self.prompt1 = self.prompt2
         self.text_embedding1 = self.text_embedding2
         self.tree_final_imgs = []
+        # an image anchor travels with its key frame: the second anchor's picture and strength become the first's
+        self.anchor_image1, self.anchor_image_strength1 = self.anchor_image2, self.anchor_image_strength2
+        self.anchor_image2, self.anchor_image_strength2 = None, 0.5
 
     # ------------------------------------------------------------------ metric ------------
     def get_lpips_similarity(self, imgA, imgB):

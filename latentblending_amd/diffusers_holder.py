@@ -99,6 +99,43 @@ class DiffusersHolder:
             1, self.pipe.unet.config.in_channels, self.height_img, self.width_img,
             torch.float16, self.pipe._execution_device, generator, None)
 
+    def get_unit_noise(self, seed=420):
+        """The tensor ``get_noise(seed)`` draws - same generator, shape, dtype and device - WITHOUT the multiplication by the
+        scheduler's ``init_noise_sigma``: the ``eps`` of a forward-noised picture (``a x0 + b eps``, image anchors)."""
+        generator = torch.Generator(device=self.device).manual_seed(int(seed))
+        pipe = self.pipe
+        if _is_native(pipe):
+            return pipe.unit_noise(1, pipe.unet.config.in_channels, self.height_img, self.width_img, torch.float16,
+                                   pipe._execution_device, generator)
+        # a diffusers-like pipe: its prepare_latents is randn_tensor(...) * init_noise_sigma and offers the draw in no other way, so
+        # the sigma is divided out again (nothing to do when it is 1; otherwise within one fp16 rounding of the draw)
+        sigma = float(getattr(pipe.scheduler, "init_noise_sigma", 1.0))
+        z = pipe.prepare_latents(1, pipe.unet.config.in_channels, self.height_img, self.width_img, torch.float16,
+                                 pipe._execution_device, generator, None)
+        return z if sigma == 1.0 else (z.float() / sigma).to(z.dtype)
+
+    @torch.no_grad()
+    def image2latent(self, image) -> torch.Tensor:
+        """Encode a picture (PIL image, or what the pipe's encoder takes) of the holder's size to scaled latents [1, 4, h, w]:
+        the native pipe's TAESDXL encoder, else ``pipe.vae.encode`` of the picture in [-1, 1] (``latent_dist.mode()`` when the
+        VAE returns a distribution, else ``.latents``) times ``vae.config.scaling_factor``."""
+        pipe = self.pipe
+        if _is_native(pipe):
+            pipe.render_size = (self.height_img, self.width_img)
+            return pipe.native_image2latent(image)
+        vae = pipe.vae
+        if not callable(getattr(vae, "encode", None)):
+            raise ValueError(f"image2latent: the pipe's VAE ({type(vae).__name__}) has no encode(); an image anchor needs an encoder")
+        u8 = np.asarray(image.convert("RGB") if hasattr(image, "convert") else image, dtype=np.uint8)
+        if u8.shape[:2] != (self.height_img, self.width_img):
+            raise ValueError(f"image2latent: the picture is {u8.shape[1]} x {u8.shape[0]} (width x height) but the holder renders "
+                             f"{self.width_img} x {self.height_img}")
+        x = torch.from_numpy(u8.copy()).permute(2, 0, 1)[None].to(device=pipe._execution_device, dtype=torch.float32) / 127.5 - 1.0
+        out = vae.encode(x.to(getattr(vae, "dtype", x.dtype)))
+        dist = getattr(out, "latent_dist", None)
+        z = dist.mode() if dist is not None else out.latents
+        return (z * vae.config.scaling_factor).to(torch.float16)
+
     @torch.no_grad()
     def latent2image(self, latents: torch.Tensor, output_type="pil"):
         """Decode a final latent to an image ("pil" or "np")."""

@@ -2,9 +2,9 @@
 from .pipe import NativeSDXLPipe, StableDiffusionXLPipeline
 from .unet import NativeUNet, UNetConfig
 from .vae import NativeVAEDecoder, VAEConfig
-from .tiny_vae import NativeTinyVAEDecoder, TinyVAEConfig, TinyVAEProgram
+from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
 from .clip import CLIPTextConfig, NativeCLIPText, NativeTextEncoders
 from .weights import DictProvider, SyntheticProvider, from_safetensors, lpips_provider
 
 __all__ = ["NativeSDXLPipe", "StableDiffusionXLPipeline", "NativeUNet", "UNetConfig", "NativeVAEDecoder",
-           "VAEConfig", "NativeTinyVAEDecoder", "TinyVAEConfig", "TinyVAEProgram", "DictProvider", "SyntheticProvider", "from_safetensors", "lpips_provider", "CLIPTextConfig", "NativeCLIPText", "NativeTextEncoders"]
+           "VAEConfig", "NativeTinyVAEDecoder", "NativeTinyVAEEncoder", "TinyVAEConfig", "TinyVAEProgram", "TinyEncoderProgram", "DictProvider", "SyntheticProvider", "from_safetensors", "lpips_provider", "CLIPTextConfig", "NativeCLIPText", "NativeTextEncoders"]

@@ -39,7 +39,7 @@ from .lpips import NativeLPIPS
 from ..planner import noise_draws_per_run
 from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
-from .tiny_vae import NativeTinyVAEDecoder, TinyVAEConfig, TinyVAEProgram
+from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
 from .weights import SyntheticProvider
 
@@ -121,7 +121,8 @@ class StableDiffusionXLPipeline:
         a speed / preview option - a distilled approximation, its LPIPS tree is computed on its own frames).  Case-insensitive,
         anything else raises ``ValueError``; ``pipe.decoder`` switches it afterwards (preview tiny, render full).  The tiny network
         is built on first use from ``tiny_vae_native`` / ``tiny_vae_provider`` (``native.from_safetensors(<dir>/taesdxl)``), else
-        from the seeded synthetic stand-in (announced like the others).
+        from the seeded synthetic stand-in (announced like the others).  The same provider serves the TAESDXL ENCODER
+        (``native_image2latent``: pictures -> latents, whatever ``decoder`` says), built on first use as well.
         ``scheduler``: None or "euler" = the reference pipes' choice (Euler-ancestral for Turbo, Euler for base); "ddim" = diffusers'
         DDIMScheduler (eta 0) behind the same native loops - also with ``turbo=True`` (the Turbo guidance / branching defaults
         stay, only the sampler changes: deterministic, "leading" spacing); "lcm" = the latent-consistency sampler (diffusers'
@@ -185,6 +186,13 @@ class StableDiffusionXLPipeline:
         # False = the library's own routing everywhere (A/B runs, tests).  Read when a program is BUILT: the setter drops the
         # cached tiny programs.
         self._tiny_conv_c64 = True
+        # the TAESDXL encoder (native_image2latent): built on first use from the tiny decoder's provider; its programs are cached
+        # like the tiny decoder's and dropped by the same switch
+        self.tiny_vae_encoder_native: Optional[NativeTinyVAEEncoder] = None
+        self._tiny_encoder_programs: "OrderedDict[Tuple[int, ...], TinyEncoderProgram]" = OrderedDict()
+        self.vae_encodes = 0                # pictures encoded by native_image2latent
+        side = self.unet_cfg.sample_size * self.vae_cfg.scale_factor
+        self.render_size = (side, side)     # (H, W) of the pictures this pipe is rendering: what prepare_latents was last asked for
         # non-square programs send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo kernel
         # (geometry.use_ragged_halo); False = the implicit GEMM there (A/B runs, tests).  Read when a program is BUILT: the
         # setter drops the cached non-square programs.
@@ -358,10 +366,18 @@ class StableDiffusionXLPipeline:
         ``randn_tensor(shape, generator, device, dtype)`` (reached from
         /root/reference/latentblending/diffusers_holder.py:98-111 with dtype = float16): on the CPU generator an fp16
         draw is a different stream from an fp32 draw that is cast afterwards."""
+        self.render_size = (int(height), int(width))
+        return (self._host_noise(batch, channels, height, width, dtype, generator) * self.scheduler.init_noise_sigma).to(self.device)
+
+    def _host_noise(self, batch, channels, height, width, dtype, generator) -> torch.Tensor:
         shape = (batch, channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
         host_gen = torch.Generator().manual_seed(generator.initial_seed())
-        z = torch.randn(shape, generator=host_gen, dtype=dtype)
-        return (z * self.scheduler.init_noise_sigma).to(self.device)
+        return torch.randn(shape, generator=host_gen, dtype=dtype)
+
+    def unit_noise(self, batch, channels, height, width, dtype, device, generator) -> torch.Tensor:
+        """The draw of ``prepare_latents`` (same generator, shape and dtype) WITHOUT the scheduler's initial sigma: the ``eps`` of a
+        forward-noised picture."""
+        return self._host_noise(batch, channels, height, width, dtype, generator).to(self.device)
 
     def _get_add_time_ids(self, original_size, crops_coords_top_left, target_size, dtype,
                           text_encoder_projection_dim=None):
@@ -422,9 +438,10 @@ class StableDiffusionXLPipeline:
         flag = bool(flag)
         if flag != self._tiny_conv_c64:
             self._tiny_conv_c64 = flag
-            if self._tiny_vae_programs:
+            if self._tiny_vae_programs or self._tiny_encoder_programs:
                 torch.cuda.synchronize(self.device)
             self._tiny_vae_programs.clear()
+            self._tiny_encoder_programs.clear()
 
     def _tiny_net(self) -> NativeTinyVAEDecoder:
         if self.tiny_vae_native is None:
@@ -433,6 +450,23 @@ class StableDiffusionXLPipeline:
             self.tiny_vae_native = NativeTinyVAEDecoder(self.tiny_vae_cfg, self._tiny_vae_provider or SyntheticProvider(self._tiny_seed),
                                                         self.device)
         return self.tiny_vae_native
+
+    def _tiny_encoder_net(self) -> NativeTinyVAEEncoder:
+        if self.tiny_vae_encoder_native is None:
+            if self._tiny_vae_provider is None:
+                self._synthetic_notice("tiny VAE encoder (TAESDXL) weights", "pass tiny_vae_provider=native.from_safetensors(<dir>/taesdxl)")
+            self.tiny_vae_encoder_native = NativeTinyVAEEncoder(self.tiny_vae_cfg, self._tiny_vae_provider or SyntheticProvider(self._tiny_seed),
+                                                                self.device)
+        return self.tiny_vae_encoder_native
+
+    def tiny_encoder_program(self, B: int, L) -> TinyEncoderProgram:
+        """The TAESDXL encoder's program for ``B`` pictures of latent size ``L`` (side or ``(H, W)``)."""
+        def build():
+            prog = self._tiny_encoder_net().build(B, L, c64=self._tiny_conv_c64)
+            if self._use_graphs:
+                prog.prog.instantiate()
+            return prog
+        return self._cached(self._tiny_encoder_programs, program_key(B, L), build)
 
     def unet_program(self, B: int, L) -> UNetProgram:
         """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named)."""
@@ -460,7 +494,7 @@ class StableDiffusionXLPipeline:
         if flag:
             for p in self._unet_programs.values():
                 p.enable_graphs()
-            for p in list(self._vae_programs.values()) + list(self._tiny_vae_programs.values()):
+            for p in list(self._vae_programs.values()) + list(self._tiny_vae_programs.values()) + list(self._tiny_encoder_programs.values()):
                 p.prog.instantiate()
 
     def synchronize(self):
@@ -757,6 +791,46 @@ class StableDiffusionXLPipeline:
 
     def native_latent2image(self, latents, output_type="pil"):
         return self.native_latent2image_batch([latents], output_type)[0]
+
+    def _pictures_u8(self, images) -> torch.Tensor:
+        """A PIL image / device frame, a list of them, or a uint8 [B, H, W, 3] (or [H, W, 3]) tensor or array -> uint8 [B, H, W, 3]
+        on the device."""
+        if isinstance(images, (Image.Image, DeviceImage)):
+            images = [images]
+        if isinstance(images, (list, tuple)):
+            if not images:
+                raise ValueError("native_image2latent: no picture given")
+            one = [self._frame_u8(im) if isinstance(im, DeviceImage) else
+                   torch.from_numpy(np.array(im.convert("RGB") if isinstance(im, Image.Image) else im)) for im in images]
+            if any(t.ndim != 3 or t.shape != one[0].shape for t in one):
+                raise ValueError(f"native_image2latent: the pictures must share one [H, W, 3] shape (got {[tuple(t.shape) for t in one]})")
+            u8 = torch.stack(one)
+        else:
+            u8 = images if torch.is_tensor(images) else torch.from_numpy(np.array(images))
+            if u8.ndim == 3:
+                u8 = u8[None]
+        if u8.dtype != torch.uint8 or u8.ndim != 4 or u8.shape[-1] != 3:
+            raise ValueError(f"native_image2latent: pictures must be uint8 [B, H, W, 3] (got {u8.dtype} {tuple(u8.shape)})")
+        return u8.to(self.device).contiguous()
+
+    @torch.no_grad()
+    def native_image2latent(self, images) -> torch.Tensor:
+        """Pictures -> the latents the TAESDXL encoder gives them: fp16 [B, 4, H / 8, W / 8] on the device, in scaled units
+        (UNet latents as they stand, whatever ``decoder`` is active).  ``images``: a PIL image, a list of them, or a uint8
+        [B, H, W, 3] tensor or array; H and W must be the pipe's current render size (``render_size``: what ``prepare_latents``
+        was last asked for - the holder states its own before it calls) - any other size is a ``ValueError``."""
+        u8 = self._pictures_u8(images)
+        H, W = int(u8.shape[1]), int(u8.shape[2])
+        if (H, W) != tuple(self.render_size):
+            raise ValueError(f"native_image2latent: the pictures are {W} x {H} (width x height) but the pipe renders "
+                             f"{self.render_size[1]} x {self.render_size[0]}; resize them first")
+        f = self.tiny_vae_cfg.scale_factor
+        if H % f or W % f:
+            raise ValueError(f"native_image2latent: the render size {W} x {H} is no multiple of {f}")
+        prog = self.tiny_encoder_program(u8.shape[0], (H // f, W // f))
+        z = prog.encode(u8).clone()
+        self.vae_encodes += int(u8.shape[0])
+        return z
 
     @torch.no_grad()
     def native_frame_distances(self, pairs) -> List[float]:

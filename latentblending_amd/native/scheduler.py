@@ -104,6 +104,18 @@ class NativeScheduler:
         executes: a multistep sampler has no history then; a single-step sampler returns the same row either way."""
         raise NotImplementedError
 
+    def noise_level(self, i: int) -> Tuple[float, float]:
+        """``(a, b)`` with which a sample ENTERING step ``i`` is ``a x0 + b eps`` in this sampler's own units (``0 <= i <
+        num_inference_steps``); ``i = num_inference_steps`` is where the last step lands.  Read from the tables ``step_row``
+        reads, so that a forward-noised picture (an image anchor of the engine) sits on the trajectory the step kernel walks."""
+        n = self.num_inference_steps
+        if not 0 <= int(i) <= n:
+            raise ValueError(f"noise_level: step {i} outside 0..{n}")
+        return self._noise_level(int(i))
+
+    def _noise_level(self, i: int) -> Tuple[float, float]:
+        raise NotImplementedError
+
     # ---- noise ------------------------------------------------------------------------------
     def noise_draws(self, steps: int, idx_start: int) -> int:
         """Latent-shaped noise draws one run from ``idx_start`` of a ``steps``-step schedule consumes."""
@@ -200,6 +212,10 @@ class NativeEulerScheduler(NativeScheduler):
             return (s_from, s_down, s_up, guidance, s_down - s_from)
         return (s_from, s_to, 0.0, guidance, s_to - s_from)
 
+    def _noise_level(self, i: int) -> Tuple[float, float]:
+        """Sigma space: the latent is ``x0 + sigma_i eps`` (``sigmas_np`` ends in 0)."""
+        return 1.0, float(self.sigmas_np[i])
+
     def noise_draws(self, steps: int, idx_start: int) -> int:
         return max(0, int(steps) - int(idx_start)) if self.ancestral else 0
 
@@ -253,6 +269,13 @@ class NativeDDIMScheduler(NativeScheduler):
         inv = torch.ones((), dtype=torch.float32) / sa_t.to(torch.float32)
         return (0.0, float(sa_t), float(a_p ** 0.5), guidance, float((1 - a_t) ** 0.5), float((1 - a_p) ** 0.5), float(inv))
 
+    def _noise_level(self, i: int) -> Tuple[float, float]:
+        """(sqrt(abar), sqrt(1 - abar)) in the fp32 tensor arithmetic of ``step_row``; the landing point of the last step is its
+        ``abar_prev`` side - ``final_alpha_cumprod``, not 1 (set_alpha_to_one = False)."""
+        n = self.num_inference_steps
+        a = self.alpha_pair(i)[0] if i < n else self.alpha_pair(n - 1)[1]
+        return float(a ** 0.5), float((1 - a) ** 0.5)
+
     draw_noise = _no_noise                                      # (eta = 0)
 
     def device_step(self, x, eps, params, noise=None, cfg=False, **kw):
@@ -302,6 +325,13 @@ class NativeLCMScheduler(NativeScheduler):
 
     def noise_draws(self, steps: int, idx_start: int) -> int:
         return max(0, int(steps) - int(idx_start) - 1)
+
+    def _noise_level(self, i: int) -> Tuple[float, float]:
+        """(sqrt(abar_t), sqrt(1 - abar_t)) as ``step_row`` forms them; the last step returns the denoised latent itself."""
+        if i == self.num_inference_steps:
+            return 1.0, 0.0
+        a = self.alphas_cumprod[int(self.timesteps_np[i])]
+        return float(a ** 0.5), float((1 - a) ** 0.5)
 
     def step_row(self, i: int, guidance: float = 0.0, first: bool = False):
         """(0, c_skip, sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t), c_out): the boundary
@@ -422,6 +452,12 @@ class NativeDPMSolverPP2MScheduler(NativeScheduler):
         """The row of step ``i`` (``dpmpp_2m_row`` over this schedule's sigmas).  ``first`` = the sample has no history at this
         step - the first step it executes: a first-order row."""
         return dpmpp_2m_row(self.sigmas_np, i, guidance, first)
+
+    def _noise_level(self, i: int) -> Tuple[float, float]:
+        """(alpha_i, sigma'_i) of ``dpmpp_2m_row``'s variance-preserving form over the same ``sigmas_np`` (sigma_n = 0 -> (1, 0))."""
+        sig = float(self.sigmas_np[i])
+        a = 1.0 / (sig ** 2 + 1.0) ** 0.5
+        return a, sig * a
 
     draw_noise = _no_noise                                      # (the solver is deterministic)
 

@@ -12,7 +12,7 @@ diffusers run - the tests hold it to a float64 restatement of this description, 
         every stage but the last:  nearest-2x upsample, then conv 64 -> 64 WITHOUT bias
         the last stage:            conv 64 -> 3 with bias
     image = 2 x - 1  in [-1, 1]
-    layer indices: 0, [2-4], 6, [7-9], 11, [12-14], 16, [17], 18; the checkpoint's ``encoder.*`` keys are ignored.
+    layer indices: 0, [2-4], 6, [7-9], 11, [12-14], 16, [17], 18; the checkpoint's ``encoder.*`` keys are the encoder's (below).
 
 No normalisation, no attention: the program is ``lb_nchw_to_nhwc_f16``, about thirty 3x3 convs and ``lb_postprocess_u8``.  The
 64 -> 64 convs (block convs; the three upsample convs with ``ups = 1``: the gather reads the low-resolution map) go through
@@ -116,7 +116,9 @@ def state_dict_keys(cfg: TinyVAEConfig = None):
     return keys
 
 
-class NativeTinyVAEDecoder:
+class _TinyNet:
+    """What the two halves of TAESDXL share: the packed weights of a stack of 3x3 convs, loaded from one provider."""
+
     def __init__(self, cfg: TinyVAEConfig, provider, device="cuda"):
         self.cfg, self.device = cfg, torch.device(device)
         self.w: Dict[str, torch.Tensor] = {}
@@ -141,6 +143,8 @@ class NativeTinyVAEDecoder:
         self.w[name + ".weight"] = self._dev(packed.reshape(cout_p, 9 * cin_p), F16)
         self.w[name + ".bias"] = self._dev(b, F32) if (bias or fold) else None
 
+
+class NativeTinyVAEDecoder(_TinyNet):
     def _load(self, pv):
         cfg = self.cfg
         # the synthetic stand-in: the last conv at gain 0.5 with 0.5 added to its biases, so that frames centre on mid-grey
@@ -239,3 +243,153 @@ class TinyVAEProgram:
         self.z_in.copy_((m * torch.tanh(z.float() / m)).half())
         self.prog.launch()
         return self.frames
+
+
+# ====================================================================== encoder
+# The other half of the same checkpoint (``encoder.*``): the decoder's mirror image, restated from the published AutoencoderTiny
+# encoder and held to a float64 restatement (tests/_taesd_enc_ref.py), as the decoder is:
+#
+#     x01 = (x + 1) / 2 with x in [-1, 1]                  (a uint8 picture: u8 / 255)
+#     encoder.layers.0        conv 3 -> 64, bias, NO activation
+#     per stage i (num_blocks mirrored: (1, 3, 3, 3)):
+#         every stage but the first:  conv 64 -> 64, stride 2, pad 1, WITHOUT bias, no activation
+#         block               relu(conv(relu(conv(relu(conv(x))))) + x), biased 64 -> 64 convs at encoder.layers.N.conv.{0,2,4}
+#     encoder.layers.14       conv 64 -> 4, bias
+#     layer indices: 0, [1], 2, [3-5], 6, [7-9], 10, [11-13], 14
+#
+# The output is latents in SCALED units (scaling_factor 1.0): UNet latents as they stand.  35 convs and one layout launch: the
+# thirty block convs are the shape LB_GEMM_C64 was written for and take it where ``use_c64`` says so (``c64=False``: the same
+# launches without the bit); the three stride-2 convs and conv_in (Cin padded to 8) run on the library's own routing - the
+# implicit GEMM takes ``stride`` - and the last conv takes the narrow-N route.  No new kernel: LB_GEMM_C64 refuses stride 2 and
+# three launches on maps of at most a quarter of the picture do not justify widening it (tools/tiny_encoder_bench.py ->
+# profiles/tiny_encoder.txt holds the per-op record).  The picture is staged as fp16 ``u8 / 255`` by one torch elementwise
+# (the counterpart of the decoder's tanh; the C ABI stays closed).  With the seeded synthetic stand-in weights nothing can be
+# said about reconstruction quality.
+def encoder_layer_plan(cfg: TinyVAEConfig = None):
+    """The encoder's parameterised layers in order: ("in" | "down" | "block" | "out", index into ``encoder.layers``)."""
+    cfg = cfg or TinyVAEConfig()
+    plan, idx = [("in", 0)], 1
+    for i, n in enumerate(reversed(cfg.num_blocks)):
+        if i:
+            plan.append(("down", idx))
+            idx += 1
+        for _ in range(n):
+            plan.append(("block", idx))
+            idx += 1
+    plan.append(("out", idx))
+    return plan
+
+
+def encoder_state_dict_keys(cfg: TinyVAEConfig = None):
+    """The ``encoder.*`` keys of ``taesdxl``'s ``diffusion_pytorch_model.safetensors`` the encoder reads, in layer order."""
+    keys = []
+    for kind, n in encoder_layer_plan(cfg):
+        p = f"encoder.layers.{n}"
+        if kind == "block":
+            for k in (0, 2, 4):
+                keys += [f"{p}.conv.{k}.weight", f"{p}.conv.{k}.bias"]
+        elif kind == "down":
+            keys.append(p + ".weight")
+        else:
+            keys += [p + ".weight", p + ".bias"]
+    return keys
+
+
+class NativeTinyVAEEncoder(_TinyNet):
+    def _load(self, pv):
+        cfg = self.cfg
+        for kind, n in encoder_layer_plan(cfg):
+            p = f"encoder.layers.{n}"
+            if kind == "in":
+                self._conv(pv, p, cfg.out_channels, 64)
+            elif kind == "block":
+                for k in (0, 2, 4):
+                    self._conv(pv, f"{p}.conv.{k}", 64, 64)
+            elif kind == "down":
+                self._conv(pv, p, 64, 64, bias=False)
+            else:
+                self._conv(pv, p, 64, cfg.latent_channels)
+
+    def build(self, B: int, L, c64: bool = True) -> "TinyEncoderProgram":
+        """``L``: LATENT side, or a pair ``(H, W)`` in latent pixels (the picture is 8 times that).  ``c64`` as in the decoder."""
+        return TinyEncoderProgram(self, B, L, c64=c64)
+
+
+class TinyEncoderProgram:
+    """One recorded tiny encode for a fixed (batch, latent size): uint8 pictures [B, 8H, 8W, 3] -> fp16 latents [B, 4, H, W]."""
+
+    def __init__(self, net: NativeTinyVAEEncoder, B: int, L, c64: bool = True):
+        cfg = net.cfg
+        H, W = latent_hw(L)
+        self.net, self.B, self.H, self.W = net, B, H, W
+        self.L = H if H == W else None
+        self.c64 = bool(c64)
+        self.c64_launches = 0
+        dev = net.device
+        self.arena = Arena(dev)
+        self.em = Emitter(self.arena)
+        self.em.ragged_halo = H != W
+        self.SH, self.SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.pc, self.pc_p = cfg.out_channels, _pad(cfg.out_channels, 8)
+        self.x_in = torch.zeros(B, self.SH, self.SW, self.pc_p, dtype=F16, device=dev)      # NHWC; the pad channels stay zero
+        self.latents = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.prog = Program("tiny-vae-encode")
+        with self.prog.record():
+            self._emit()
+
+    def _conv64(self, x, name, B, h, w, *, residual=None):
+        """One biased 64 -> 64 block conv with ReLU: flagged where the rule says so."""
+        wt = self.net.w
+        out = self.arena.alloc((B, h, w, 64))
+        flags = lib.GEMM_RELU
+        if self.c64 and use_c64(B, h, w):
+            flags |= lib.GEMM_C64
+            self.c64_launches += 1
+        self.em.gemm(x, wt[name + ".weight"], out, M=B * h * w, bias=wt[name + ".bias"], residual=residual, flags=flags, splitk=False,
+                     conv=dict(Hin=h, Win=w, Cin=64, Hout=h, Wout=w, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+        return out
+
+    def _emit(self):
+        cfg, em, w, ar, B = self.net.cfg, self.em, self.net.w, self.arena, self.B
+        sh, sw = self.SH, self.SW
+        lc_p = _pad(cfg.latent_channels, 4)
+        h = None
+        for kind, n in encoder_layer_plan(cfg):
+            p = f"encoder.layers.{n}"
+            if kind == "in":
+                h = ar.alloc((B, sh, sw, 64))
+                em.gemm(self.x_in, w[p + ".weight"], h, M=B * sh * sw, bias=w[p + ".bias"], flags=0, splitk=False,
+                        conv=dict(Hin=sh, Win=sw, Cin=self.pc_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=self.pc_p))
+            elif kind == "block":
+                a = self._conv64(h, p + ".conv.0", B, sh, sw)
+                b = self._conv64(a, p + ".conv.2", B, sh, sw)
+                ar.release(a)
+                o = self._conv64(b, p + ".conv.4", B, sh, sw, residual=h)
+                ar.release(b)
+                ar.release(h)
+                h = o
+            elif kind == "down":
+                ho, wo = sh // 2, sw // 2
+                o = ar.alloc((B, ho, wo, 64))
+                em.gemm(h, w[p + ".weight"], o, M=B * ho * wo, flags=0, splitk=False,
+                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=ho, Wout=wo, KH=3, KW=3, stride=2, pad=1, ups=0, ldx=64))
+                ar.release(h)
+                h, sh, sw = o, ho, wo
+            else:
+                o = ar.alloc((B, sh, sw, lc_p))
+                em.gemm(h, w[p + ".weight"], o, M=B * sh * sw, bias=w[p + ".bias"], flags=0, splitk=False,
+                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+                ar.release(h)
+                api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.latents.data_ptr(), B, cfg.latent_channels, sh * sw, lc_p, _stream())
+                ar.release(o)
+        assert (sh, sw) == (self.H, self.W)
+
+    def encode(self, u8: torch.Tensor) -> torch.Tensor:
+        """uint8 pictures [B, 8H, 8W, 3] on the device -> fp16 latents [B, 4, H, W] in scaled units (the program's own buffer:
+        clone what must outlive the next call).  ``u8 / 255`` is staged here, in torch (see the note above)."""
+        if tuple(u8.shape) != (self.B, self.SH, self.SW, self.pc) or u8.dtype != torch.uint8:
+            raise ValueError(f"TinyEncoderProgram.encode: expected uint8 {(self.B, self.SH, self.SW, self.pc)}, "
+                             f"got {u8.dtype} {tuple(u8.shape)}")
+        torch.div(u8, 255.0, out=self.x_in[..., :self.pc])
+        self.prog.launch()
+        return self.latents

@@ -130,6 +130,16 @@ def noise_draws_per_run(sched, steps: int, idx_start: int) -> int:
     return max(0, int(steps) - int(idx_start)) if getattr(sched, "ancestral", False) else 0
 
 
+def img2img_start(num_steps: int, strength: float) -> int:
+    """First step an image anchor of ``strength`` denoises (diffusers' img2img rule, ``get_timesteps``): the picture is noised to
+    the level of step ``t_start`` and the last ``min(int(steps * strength), steps)`` steps run.  ``strength`` 0 -> ``num_steps``
+    (no step runs: the anchor is the picture), 1 -> 0 (re-imagined from full noise).  ``ValueError`` outside [0, 1]."""
+    strength = float(strength)
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError(f"image anchor strength must be in [0, 1] (got {strength})")
+    return int(num_steps) - min(int(int(num_steps) * strength), int(num_steps))
+
+
 def transition_census(num_steps: int, levels: Sequence[int], stems: Sequence[int]) -> dict:
     """Work count of one ``run_transition`` with fresh anchors (SURVEY.md §3.6 schema)."""
     mid = int(np.sum(stems))

@@ -12,6 +12,9 @@ the gradio UI saves (``gradio_ui.py:168-190``):
     [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S},
       {"iteration": i, "seed": s, "prompt": "...", "negative_prompt": "...", "preview_image": ...}, ... ]
 
+An item may also carry ``"image"`` (a picture file, path relative to the JSON file) and ``"image_strength"`` (default 0.5): that
+key frame is an image anchor (``BlendingEngine.set_anchor_image1`` / ``2``) instead of a picture invented from its prompt.
+
 Host-side control only; the hot path below it is ``BlendingEngine.run_transition``.
 """
 from __future__ import annotations
@@ -52,7 +55,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          fps: int = 30, dp_parts: str = ".", keep_parts: bool = True,
                          on_segment: Optional[Callable[[int, List], None]] = None,
                          pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
-                         movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None) -> List[List]:
+                         movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
+                         list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -71,10 +75,34 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     ``movie_size`` / ``movie_resample``: its ``size_output=(W, H)`` / ``resample=`` (None: the engine's ``movie_size`` / ``movie_resample``).
     ``decoder``: "full" / "tiny" = the native pipe's ``decoder`` for this chain (None: as the pipe stands); the previous value is
     restored afterwards.
+    ``list_images`` / ``list_image_strengths``: one entry per key frame, ``None`` = a prompt key frame; a picture makes that key
+    frame an image anchor (``set_anchor_image1`` / ``2``; strength ``None`` = 0.5).  The image anchors are set and cleared per
+    segment; a shared image key frame is computed (and encoded) once and recycled through ``swap_forward`` like any other.  The
+    engine's image anchors are cleared when the chain ends.  Together with ``pipeline_keyframes=True``: ``ValueError``.
     """
+    images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
+    if images is not None and pipeline_keyframes:
+        raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
+                         "it cannot be combined with image key frames (list_images)")
     with _decoder_as(be, decoder):
-        return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
-                                     keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample)
+        try:
+            return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
+                                         keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
+        finally:
+            if images is not None:
+                be.clear_anchor_images()
+
+
+def _image_keyframes(list_images, list_image_strengths, n):
+    """[(picture or None, strength)] per key frame, or None when no key frame is a picture."""
+    if list_images is None or all(im is None for im in list_images):
+        return None
+    if len(list_images) < n:
+        raise ValueError("run_multi_transition needs one list_images entry (a picture or None) per prompt")
+    strengths = list(list_image_strengths) if list_image_strengths is not None else [None] * len(list_images)
+    if len(strengths) < n:
+        raise ValueError("run_multi_transition needs one list_image_strengths entry per prompt")
+    return [(im, 0.5 if s is None else float(s)) for im, s in zip(list_images[:n], strengths[:n])]
 
 
 @contextlib.contextmanager
@@ -95,7 +123,7 @@ def _decoder_as(be, decoder: Optional[str]):
 
 
 def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts, keep_parts,
-                          on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample) -> List[List]:
+                          on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images=None) -> List[List]:
     n = len(list_prompts)
     if n < 2:
         raise ValueError("run_multi_transition needs at least two prompts")
@@ -121,6 +149,10 @@ def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_singl
                 be.set_negative_prompt(list_negative_prompts[i])
             be.set_prompt2(list_prompts[i + 1])
             recycle_img1 = False
+            if images is not None:
+                be.clear_anchor_images()
+                if images[0][0] is not None:
+                    be.set_anchor_image1(*images[0])
         else:
             be.swap_forward()
             if list_negative_prompts is not None:
@@ -128,6 +160,8 @@ def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_singl
             be.set_prompt2(list_prompts[i + 1])
             recycle_img1 = True
         if keys is None:
+            if images is not None and images[i + 1][0] is not None:     # (swap_forward carried the previous one to anchor 1 and cleared 2)
+                be.set_anchor_image2(*images[i + 1])
             fixed_seeds = [int(s) for s in list_seeds[i:i + 2]]
             frames = be.run_transition(recycle_img1=recycle_img1, fixed_seeds=fixed_seeds)
         segments.append(frames)
@@ -166,11 +200,19 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
                    decoder: Optional[str] = None) -> List[List]:
-    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder`` as there)."""
+    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder`` as there).
+    Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames."""
     header, items = load_movie_json(fp_json)
+    images = strengths = None
+    if any(it.get("image") is not None for it in items):
+        from PIL import Image
+        base = os.path.dirname(os.path.abspath(fp_json))
+        images = [None if it.get("image") is None else Image.open(os.path.join(base, it["image"])).convert("RGB") for it in items]
+        strengths = [it.get("image_strength") for it in items]
     be.set_dimensions((header["width"], header["height"]))
     be.set_num_inference_steps(header["num_inference_steps"])
     return run_multi_transition(be, [it["prompt"] for it in items], [it["seed"] for it in items], fp_movie,
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
-                                movie_size=movie_size, movie_resample=movie_resample, decoder=decoder)
+                                movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
+                                list_image_strengths=strengths)
