@@ -132,6 +132,14 @@ enum {
                               * refused.  A flagged problem runs there or fails with a message naming the violated condition - it never takes
                               * another route; lb_gemm_ch_stat_rows is 0 and lb_conv_halo_plan's kind is 0 for it.  The direct entry points
                               * (lb_conv3x3_halo_f16, lb_conv3x3_narrow_f16, lb_upconv2x_halo_f16) ignore the bit. */
+    LB_GEMM_GN_A = 8192,     /* whole-tile 3x3 halo conv (lb_conv3x3_halo_f16) and narrow-N conv (lb_conv3x3_narrow_f16), also when lb_gemm_f16
+                              * routes there: A is consumed through a GroupNorm given as an affine table - the kernel multiplies
+                              * f16(silu(fma(A[b, y, x, c], gn_table[b][c].scale, gn_table[b][c].shift))) (SiLU when gn_silu), the very
+                              * fp16 value lb_groupnorm_from_stats would have stored, transformed in LDS after staging; zero padding stays
+                              * zero.  gn_table = [B][Cin] float2 from lb_groupnorm_affine_from_stats (lb_hip_gn_a.h).  A flagged problem
+                              * runs on one of the two kernels or is refused: no table, a ragged (LB_GEMM_HALO_RAGGED shape that does not
+                              * divide into tiles) or K-split (LB_GEMM_HALO_KSPLIT) launch, a sub-pixel upconv, LB_GEMM_C64, or a route to
+                              * any other kernel.  Whether fusing pays is lb_conv_halo_gn_a_plan's answer (lb_conv_halo_set_gn_a). */
     LB_GEMM_LN_A = 64        /* A is consumed through a LayerNorm over its K columns (K = the normalised width):
                                 C = LN(A) . Wt computed as rstd_m * (A . W'^T - mean_m * colsum) + bias with
                                 W' = W * gamma (folded by the caller), ln_colsum[n] = sum_k W'[n][k],
@@ -173,6 +181,8 @@ typedef struct LbGemmParams {
     float* ch_stats;         /* LB_GEMM_CH_STATS: output [N][row blocks] float2 (sum, sum of squares), else unused */
     int ch_stats_rows;       /* LB_GEMM_CH_STATS: row blocks per channel the caller's buffer holds = B * lb_gemm_ch_stat_rows();
                               * the launcher refuses any other value (the kernel's layout and the buffer cannot drift apart) */
+    const float* gn_table;   /* LB_GEMM_GN_A: [B][Cin] float2 (scale, shift), else unused */
+    int gn_silu;             /* LB_GEMM_GN_A: SiLU after the affine map */
 } LbGemmParams;
 
 int lb_gemm_f16(const LbGemmParams* params, void* stream);
@@ -210,6 +220,9 @@ void lb_conv_halo_plan(const LbGemmParams* params, int* kind, int* tile_w, long*
  * lb_hip_ksplit.h: this header lists what hip/lib.py binds in SIGNATURES - the table of what a program can record, one replay case
  * per entry - and these three launch nothing and take no stream (hip/lib.py: HOST_SIGNATURES). */
 #include "lb_hip_ksplit.h"
+/* LB_GEMM_GN_A: the table launcher (lb_groupnorm_affine_from_stats), the plan the emitter asks (lb_conv_halo_gn_a_plan) and the
+ * policy switch (lb_conv_halo_set_gn_a) live in lb_hip_gn_a.h for the same reason (hip/lib.py: GN_A_SIGNATURES). */
+#include "lb_hip_gn_a.h"
 /* LB_GEMM_CH_STATS: row blocks PER SAMPLE of the statistics buffer ([N][B * rows] float2) the launch lb_gemm_f16 would make
  * for these parameters writes - from the same routing and the same tile constants as the launch itself; 0 = this problem does
  * not run on a halo-tile kernel (no statistics: the consumer runs the two-pass GroupNorm).  Launches nothing. */

@@ -54,6 +54,10 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 template <int N> __device__ __forceinline__ void halo_wait_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
+// GNA form: the wave's in-place LDS writes of the transformed halo pieces must have completed before the barrier publishes them
+template <int N> __device__ __forceinline__ void halo_wait_barrier_lds() {
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
+}
 
 // KS = 3: the 3x3 / stride 1 / pad 1 convolution described above (9 taps per 64-channel chunk).
 // KS = 2: the SUB-PIXEL form of "nearest-2x upsample, then 3x3 conv" (LbGemmParams.scatter == 2): four 2x2 convolutions
@@ -94,10 +98,31 @@ template <int KS, int NR, int TAP> constexpr int halo_full_rounds_in_tap() {   /
 // sum does not depend on who arrived last - runs the epilogue on the sum and puts the counter back to zero.  Workspace (p.partial): the counters (one
 // int per tile, zero on entry, zero on exit; halo_ksplit_layout), then two slabs per block (2 b: the block's first tile, 2 b + 1: its last).
 // KSP = false is the shipped code, instruction for instruction.
-template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false>
+//
+// GNA (LB_GEMM_GN_A, whole-tile unsplit 3x3 form only): the A operand is f16(silu(fma(x, scale, shift))) with (scale, shift) =
+// p.gn_table[sample][channel] - the GroupNorm (+ SiLU) of the producing layer, whose apply pass (one read and one write of the whole
+// activation) then does not run at all.  The halo arrives by direct-to-LDS requests, so the map runs IN PLACE in LDS, once per staged
+// piece: round j of the next chunk's halo is requested in tap j, the counted wait before tap j + 3 guarantees the issuing wave that its
+// own request has landed, so in tap j + 3 (rounds 0..5 -> taps 3..8) every lane transforms exactly the 16-byte piece it requested
+// itself - one ds_read_b128, 8 x lb_gn_apply, one ds_write_b128, placed after the second MFMA group of the step, where the first
+// fragment set is dead (the map's ~26 registers are transient).  The barrier of the next chunk's first step publishes the result
+// (halo_wait_barrier_lds: lgkmcnt(0) in front of every barrier).  Pieces that came from the zero page (h_off[j] < 0: out-of-image
+// pixels, absent rounds, requests past the end of the work) are left alone: zero padding stays zero.  The first halo of a block is
+// transformed in the prologue, behind a counted wait that leaves only the weight requests in flight.
+//   The table: a lane's channels are fixed by cl and the chunk - 8 (scale, shift) pairs = 64 bytes per chunk.  In tap 0 of every
+// chunk EVERY wave issues ONE more direct-to-LDS request: the 64 pairs (512 B, twice: lanes 32..63 repeat lanes 0..31) of the sample
+// and chunk the halo requested during this chunk belongs to (the tile being REQUESTED: nxt.b during a tile's last chunk, as
+// set_halo_offsets re-points h_off), into a 1 KiB area of the wave's OWN behind the weight ring (8 KiB in all).  It is older than
+// halo round 0, so it has landed where round 0 has; the wave reads it in taps 3..8 and overwrites it in the next tap 0, in program
+// order.  Because every wave issues it in every chunk, the hand-counted waits stay compile-time constants: cnt(tap 0) is one larger
+// (halo_gna_loads_in_tap), nothing else moves.  GNA = false is the shipped code, instruction for instruction.
+template <bool GNA, int TAP> constexpr int halo_gna_loads_in_tap() { return GNA && TAP == 0 ? 1 : 0; }
+
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false>
 __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p) {
     static_assert(!RAG || KS == 3, "ragged tiles exist for the 3x3 form only");
     static_assert(!KSP || (KS == 3 && !RAG), "the K-split form exists for the whole-tile 3x3 form only");
+    static_assert(!GNA || (KS == 3 && !RAG && !KSP), "the GroupNorm-on-A form exists for the whole-tile unsplit 3x3 form only");
     constexpr int TH = 256 / TW;
     constexpr int NTAP = KS * KS;
     constexpr int HWP = TW + KS - 1;                    // halo width in pixels
@@ -232,6 +257,31 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
     };
 
+    // ---- GNA: the wave's table area, its request, and the in-place map of one staged piece ---------------
+    f16* const gn_area = wring + 4 * BN * 64 + wave * 512;      // (1 KiB per wave: 128 float2, the chunk's 64 pairs twice)
+    auto issue_gn_table = [&](int b_req, int chunk) {
+        const float* src = p.gn_table + ((long)b_req * p.Cin + chunk * 64) * 2 + (lane & 31) * 4;
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)gn_area, 16, 0, 0);
+    };
+    auto gn_transform = [&](int j, int buf) {           // round j of the halo in buffer `buf`: the piece this lane requested
+        if (h_off[j] >= 0) {
+            f16* pc = halo0 + buf * (HRP * 64) + (j * 8 + wave) * 8 * 64 + lane * 8;
+            const f32x4* tb = reinterpret_cast<const f32x4*>(gn_area) + cl * 4;      // pairs of channels cl * 8 .. cl * 8 + 7
+            const f32x4 t0 = tb[0], t1 = tb[1], t2 = tb[2], t3 = tb[3];
+            const f16x8 v = *reinterpret_cast<const f16x8*>(pc);
+            f16x8 o;
+            o[0] = lb_gn_apply((float)v[0], t0[0], t0[1], p.gn_silu);
+            o[1] = lb_gn_apply((float)v[1], t0[2], t0[3], p.gn_silu);
+            o[2] = lb_gn_apply((float)v[2], t1[0], t1[1], p.gn_silu);
+            o[3] = lb_gn_apply((float)v[3], t1[2], t1[3], p.gn_silu);
+            o[4] = lb_gn_apply((float)v[4], t2[0], t2[1], p.gn_silu);
+            o[5] = lb_gn_apply((float)v[5], t2[2], t2[3], p.gn_silu);
+            o[6] = lb_gn_apply((float)v[6], t3[0], t3[1], p.gn_silu);
+            o[7] = lb_gn_apply((float)v[7], t3[2], t3[3], p.gn_silu);
+            *reinterpret_cast<f16x8*>(pc) = o;
+        }
+    };
+
     // ---- consumer state -----------------------------------------------------------------------------
     int hbase[TM];                                      // halo row of tap (0, 0) of the lane's pixel i
     int mloc[TM];                                       // the pixel's offset from the tile origin, in image pixels
@@ -291,6 +341,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
     }
     TileAt cur = tile_of(item);
     set_halo_offsets(cur, true);
+    if constexpr (GNA) issue_gn_table(cur.b, c_lo);
 #pragma unroll
     for (int j = 0; j < NR; ++j)
         if (j < NR - 1 || wave < EXTRA) issue_halo(j, c_lo, 0);
@@ -298,14 +349,21 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
     for (int t = 0; t < 3; ++t)
 #pragma unroll
         for (int i = 0; i < WI; ++i) issue_weight(i, c_lo, true, t, t);
+    if constexpr (GNA) {                                // the first halo: everything but the 3 * WI weight requests has landed
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * WI) : "memory");
+#pragma unroll
+        for (int j = 0; j < NR; ++j) gn_transform(j, 0);
+    }
 
     // one step; TAP is a compile-time constant so that every count below is an immediate.  c = chunk within the tile,
     // cc = chunks since the block started (halo buffer / weight slot parity run on across tiles), more = another tile follows
-    auto step = [&](auto tap_c, int c, int cc, bool more) {
+    auto step = [&](auto tap_c, int c, int cc, bool more, int gn_b = 0) {
         constexpr int TAP = decltype(tap_c)::value;
         constexpr int P1 = (TAP + NTAP - 1) % NTAP, P2 = (TAP + NTAP - 2) % NTAP;          // taps of the two previous steps
-        constexpr int CNT = (2 + halo_full_rounds_in_tap<KS, NR, P1>()) + (2 + halo_full_rounds_in_tap<KS, NR, P2>());
-        halo_wait_barrier<CNT>();
+        constexpr int CNT = (2 + halo_full_rounds_in_tap<KS, NR, P1>() + halo_gna_loads_in_tap<GNA, P1>()) +
+                            (2 + halo_full_rounds_in_tap<KS, NR, P2>() + halo_gna_loads_in_tap<GNA, P2>());
+        if constexpr (GNA) halo_wait_barrier_lds<CNT>();
+        else halo_wait_barrier<CNT>();
         const int slot = KS == 3 ? ((cc + TAP) & 3) : TAP;   // (NTAP cc + TAP) mod 4
         const f16* hb = halo0 + (cc & 1) * (HRP * 64);
         const f16* wb = wring + slot * (BN * 64);
@@ -325,6 +383,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         const int slot3 = (slot + 3) & 3;
         f16x8 a0[TM], w0[TN], a1[TM], w1[TN];
         read_frags(hb, wb, shift, 0, a0, w0);
+        if constexpr (GNA && TAP == 0) issue_gn_table(gn_b, hc);     // (older than round 0 of the halo it belongs to)
         if constexpr (HaloSched<KS, 0>::tap == TAP) issue_halo(0, hc, hbuf);
         if constexpr (NR > 2 && HaloSched<KS, 1>::tap == TAP) issue_halo(1, hc, hbuf);
         if constexpr (NR > 3 && HaloSched<KS, 2>::tap == TAP) issue_halo(2, hc, hbuf);
@@ -339,6 +398,10 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
         __builtin_amdgcn_sched_barrier(0);
         mma_rows(a0, w0, TM / 2, TM);
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (GNA && TAP >= 3) {                // round TAP - 3 of the next halo: this wave's own request, landed (see above)
+            gn_transform(TAP - 3, hbuf);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         issue_weight(1, c3, w_exists, TAP3, slot3, wrap);
         __builtin_amdgcn_sched_barrier(0);
         mma_rows(a1, w1, 0, TM);
@@ -362,7 +425,7 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
                 set_halo_offsets(nxt, more);
                 if constexpr (KSP) set_w_offsets(n0_next, w_offn, w_off32n);
             }
-            step(std::integral_constant<int, 0>{}, c, cc, more);
+            step(std::integral_constant<int, 0>{}, c, cc, more, GNA ? (c + 1 == c_end ? nxt.b : cur.b) : 0);
             step(std::integral_constant<int, 1>{}, c, cc, more);
             step(std::integral_constant<int, 2>{}, c, cc, more);
             step(std::integral_constant<int, 3>{}, c, cc, more);
@@ -571,26 +634,36 @@ long lb_conv_halo_stat_rows_total(const LbGemmParams& p) {
     return items / ((p.N + 127) / 128) * 4;
 }
 
-template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false>
+static int g_halo_gn_a_mode = 1, g_halo_gn_a_grid = 0;     // (lb_conv_halo_set_gn_a, below)
+
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false>
 static int launch_halo(const LbGemmParams& p, hipStream_t stream, long ksp_grid = 0) {
     constexpr int TH = 256 / TW;
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
-    constexpr int SMEM = (2 * HRP * 64 + 4 * BN * 64) * (int)sizeof(f16) + (KSP ? 16 : 0);   // (KSP: the "last arriver" word)
+    // (KSP: the "last arriver" word; GNA: 1 KiB of table per wave)
+    constexpr int SMEM = (2 * HRP * 64 + 4 * BN * 64) * (int)sizeof(f16) + (KSP ? 16 : 0) + (GNA ? 8 * 1024 : 0);
+    static_assert(SMEM <= 160 * 1024, "LDS of one CU");
     static unsigned long long seen = 0;
     // (a recording does not come here: the first call on a device happens at the first replay - inside the stream capture of
     //  lb_program_instantiate when a program is instantiated before any eager run)
     LB_ONCE_PER_DEVICE(seen)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
     long nblk, grid;
     halo_grid(p, TW, KS, nblk, grid);          // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
     if (KSP) grid = ksp_grid;                  // (one block per CU walks an even share of the units: halo_ksplit_plan)
+    if (GNA && g_halo_gn_a_grid > 0) {         // (tests: a multiple of the weight-slab period, at most one block per item)
+        const long period = (p.N + BN - 1) / BN;
+        grid = g_halo_gn_a_grid / period * period;
+        if (grid < period) grid = period;
+        if (grid > nblk) grid = nblk;
+    }
     LbGemmParams pk = p;
 #ifdef LB_STUDY_BUILD
     pk.reserved_ = g_halo_study;
 #endif
-    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG, KSP>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
     return lb_check_launch(KS == 2 ? "lb_upconv2x_halo_f16" : "lb_conv3x3_halo_f16");
 }
 
@@ -616,6 +689,7 @@ static int halo_tiles_check(const LbGemmParams& p, int tw, int ks) {
 }
 
 int lb_upconv_halo_check(const LbGemmParams& p) {
+    LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "halo upconv: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only");
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || (p.ch_stats != nullptr && p.ch_stats_rows == lb_conv_halo_stat_rows_total(p)),
                "halo upconv: LB_GEMM_CH_STATS needs ch_stats with ch_stats_rows = B * lb_gemm_ch_stat_rows()");
     return halo_tiles_check(p, lb_upconv_halo_eligible(p), 2);
@@ -681,6 +755,7 @@ static void halo_ksplit_plan(const LbGemmParams& p, long& units, long& grid, int
     units = grid = 0;
     split = 0;
     if (!(p.flags & LB_GEMM_HALO_KSPLIT) || (p.flags & LB_GEMM_C64) || g_halo_ksplit_mode == 0) return;
+    if (p.flags & LB_GEMM_GN_A) return;         // (refused together by lb_conv3x3_halo_check: the K-split form has no GroupNorm-on-A twin)
     const int tw = lb_conv3x3_halo_eligible(p);
     if (!tw || halo3_ragged(p, tw) || p.Cin < 128) return;
     long items, ugrid;
@@ -739,13 +814,60 @@ int lb_conv3x3_halo_check(const LbGemmParams& p) {
         LB_REQUIRE(!split || p.partial != nullptr,
                    "halo conv: LB_GEMM_HALO_KSPLIT needs partial = a zeroed workspace of lb_conv_halo_ksplit_workspace_bytes()");
     }
+    if (p.flags & LB_GEMM_GN_A) {
+        LB_REQUIRE(p.gn_table != nullptr, "halo conv: LB_GEMM_GN_A needs gn_table = the [B][Cin] float2 table of lb_groupnorm_affine_from_stats");
+        LB_REQUIRE(!(p.flags & LB_GEMM_HALO_KSPLIT), "halo conv: LB_GEMM_GN_A and LB_GEMM_HALO_KSPLIT exclude each other (the K-split form has no GroupNorm-on-A twin)");
+        LB_REQUIRE(!halo3_ragged(p, lb_conv3x3_halo_eligible(p)), "halo conv: LB_GEMM_GN_A needs an image that divides into whole tiles (no ragged form)");
+        LB_REQUIRE((reinterpret_cast<uintptr_t>(p.gn_table) & 15) == 0, "halo conv: gn_table must be 16-byte aligned");
+    }
     return halo_tiles_check(p, lb_conv3x3_halo_eligible(p), 3);
+}
+
+// ---- GroupNorm on A (LB_GEMM_GN_A): policy ---------------------------------------------------------------------------------------
+// The consumer repeats the map once per channel block (N / 128) and 1.33x for the halo overlap, as VALU work between the MFMA groups
+// of six of a chunk's nine steps; what it saves is one read and one write of the activation by the apply pass.  Whether that pays was
+// MEASURED per shape (profiles/halo_gn_ab.txt: table kernel + flagged conv against lb_groupnorm_from_stats + conv, modes alternated,
+// tools/halo_gn_ab.py); a shape is in only where its gain exceeds 3 x the larger spread of the repeats.  At B = 17:
+//   one channel block  (512^2, 256 -> 128 and 128 -> 128; 68 tiles per block):  +359 us (12.1 %) and +181 us (11.5 %)   in
+//   two channel blocks (256^2, 512 -> 256 and 256 -> 256):                      +17 us and -1 us, inside the spread     out
+//   four channel blocks (64^2 and 128^2, 512 -> 512):                           -30 us and -105 us (-9 %, -10 %)        out
+// At B = 2 the one-block shapes (8 tiles per block) gained +35 us (8.7 %) and +13 us (6.1 %) - just inside 3 x their spread (39 and
+// 13 us), so by the rule they stay out; the only thing that tells them from the B = 17 launches is the tiles a block walks, so the
+// rule is: one channel block, and at least HALO_GN_A_MIN_TILES_PER_BLOCK tiles per block of the persistent grid (32: between the 8
+// that did not pass and the 68 that did; nothing in between was measured).
+static constexpr int HALO_GN_A_MAX_BLOCKS = 1;
+static constexpr long HALO_GN_A_MIN_TILES_PER_BLOCK = 32;
+extern "C" void lb_conv_halo_set_gn_a(int mode, int grid) {
+    g_halo_gn_a_mode = mode < 0 ? 1 : mode;
+    g_halo_gn_a_grid = grid > 0 ? grid : 0;
+}
+// 1 = the policy includes this (eligible, whole-tile, unsplit) halo launch
+int lb_conv3x3_halo_gn_a_policy(const LbGemmParams& p) {
+    if (g_halo_gn_a_mode == 0) return 0;
+    if (g_halo_gn_a_mode >= 2) return 1;
+    if ((p.N + 127) / 128 > HALO_GN_A_MAX_BLOCKS) return 0;
+    long items, grid;
+    halo_grid(p, lb_conv3x3_halo_eligible(p), 3, items, grid);
+    return items >= HALO_GN_A_MIN_TILES_PER_BLOCK * grid ? 1 : 0;
+}
+int lb_conv_halo_gn_a_mode() { return g_halo_gn_a_mode; }
+// 1 = a launch of `p` (flags as it would be launched WITHOUT LB_GEMM_GN_A) on this kernel could carry the flag: the whole-tile form,
+// and the K-split plan leaves it unsplit
+int lb_conv3x3_halo_gn_a_able(const LbGemmParams& p) {
+    const int tw = lb_conv3x3_halo_eligible(p);
+    if (!tw || halo3_ragged(p, tw)) return 0;
+    long units, grid;
+    int split;
+    halo_ksplit_plan(p, units, grid, split);
+    return split ? 0 : 1;
 }
 
 int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
     const int tw = lb_conv3x3_halo_eligible(p);
+    if (p.flags & LB_GEMM_GN_A)                     // (lb_conv3x3_halo_check passed: whole tiles, no K-split, a table)
+        return tw == 32 ? launch_halo<128, 32, 3, false, false, true>(p, stream) : launch_halo<128, 16, 3, false, false, true>(p, stream);
     if (halo3_ragged(p, tw)) return tw == 32 ? launch_halo<128, 32, 3, true>(p, stream) : launch_halo<128, 16, 3, true>(p, stream);
     long units, grid;
     int split;

@@ -28,6 +28,13 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 #define NARROW_HRG ((NARROW_HR + 7) / 8)              // 41 groups of 8 rows
 #define NARROW_LDS (NARROW_HRG * 8 * 64)              // halves
 
+//
+// GNA (LB_GEMM_GN_A): the A operand is f16(silu(fma(x, scale, shift))) with (scale, shift) = p.gn_table[sample][channel] (the VAE's
+// conv_norm_out + SiLU; see conv3_halo.hip).  This kernel drains its requests once per chunk, so the map needs no counting: the
+// lane's 8 pairs of the chunk (its channels are fixed by cl) arrive by ordinary loads behind the same vmcnt(0), and between that
+// wait and the barrier every lane maps, in place, the pieces it requested itself; pieces from the zero page stay zero.
+// GNA = false is the shipped code, instruction for instruction.
+template <bool GNA>
 __global__ void __launch_bounds__(256, 2) conv3x3_narrow_kernel(const LbGemmParams p) {
     __shared__ __attribute__((aligned(16))) f16 halo[NARROW_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -83,7 +90,27 @@ __global__ void __launch_bounds__(256, 2) conv3x3_narrow_kernel(const LbGemmPara
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 wf[tap][s] = n_ok ? *reinterpret_cast<const f16x8*>(wrow + (long)tap * p.Cin + c * 64 + s * 32) : zero8;
+        f32x4 gt[GNA ? 4 : 1];                          // GNA: (scale, shift) of channels c * 64 + cl * 8 .. + 7
+        if constexpr (GNA) {
+            const f32x4* tb = reinterpret_cast<const f32x4*>(p.gn_table + ((long)b * p.Cin + c * 64 + cl * 8) * 2);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) gt[k] = tb[k];
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's halo pieces (LDS-DMA) and weight fragments have landed
+        if constexpr (GNA) {
+#pragma unroll
+            for (int j = 0; j < NR; ++j) {
+                const int gidx = j * 4 + wave;
+                if (gidx < NARROW_HRG && h_off[j] >= 0) {
+                    f16* pc = halo + gidx * 8 * 64 + lane * 8;
+                    const f16x8 v = *reinterpret_cast<const f16x8*>(pc);
+                    f16x8 o;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) o[e] = lb_gn_apply((float)v[e], gt[e >> 1][(e & 1) * 2], gt[e >> 1][(e & 1) * 2 + 1], p.gn_silu);
+                    *reinterpret_cast<f16x8*>(pc) = o;
+                }
+            }
+        }
         __syncthreads();
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -125,7 +152,7 @@ int lb_conv3x3_narrow_eligible(const LbGemmParams& p) {
     if (p.N > 16 || p.N % 4 != 0 || p.zero_page == nullptr) return 0;
     // plain bias epilogue only (LB_GEMM_HALO_KSPLIT asks nothing of the epilogue: a hint for the halo kernel, which must not change
     // the route of a conv that kernel does not get - `partial` is never read here)
-    if (p.flags & ~(LB_GEMM_OUT_F32 | LB_GEMM_HALO_KSPLIT)) return 0;
+    if (p.flags & ~(LB_GEMM_OUT_F32 | LB_GEMM_HALO_KSPLIT | LB_GEMM_GN_A)) return 0;
     if (p.residual != nullptr || p.rowvec != nullptr) return 0;
     if (p.Win % NARROW_T != 0 || p.Hin % NARROW_T != 0 || p.M % (p.Hin * p.Win) != 0) return 0;
     if ((long)p.M * p.ldx >= (1l << 34)) return 0;      // (32-bit piece offsets)
@@ -139,13 +166,16 @@ static long narrow_tiles(const LbGemmParams& p) {
 // What a launch refuses, checked by every entry point BEFORE it dispatches: a recording refuses what a direct call refuses.
 int lb_conv3x3_narrow_check(const LbGemmParams& p) {
     LB_REQUIRE(narrow_tiles(p) < (1l << 31), "conv3x3 narrow: too many tiles for one launch");
+    LB_REQUIRE(!(p.flags & LB_GEMM_GN_A) || (p.gn_table != nullptr && (reinterpret_cast<uintptr_t>(p.gn_table) & 15) == 0),
+               "conv3x3 narrow: LB_GEMM_GN_A needs gn_table = the 16-byte aligned [B][Cin] float2 table of lb_groupnorm_affine_from_stats");
     return 0;
 }
 
 int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream) {     // (trusts its caller: lb_conv3x3_narrow_check passed)
     if (p.alpha == 0.f) p.alpha = 1.f;
     const long tiles = narrow_tiles(p);
-    hipLaunchKernelGGL(conv3x3_narrow_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    if (p.flags & LB_GEMM_GN_A) hipLaunchKernelGGL(conv3x3_narrow_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(conv3x3_narrow_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
     return lb_check_launch("lb_conv3x3_narrow_f16");
 }
 

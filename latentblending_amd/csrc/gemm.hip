@@ -584,6 +584,30 @@ extern "C" int lb_gemm_ch_stat_rows(const LbGemmParams* pp) {
     return samples > 0 ? (int)(lb_conv_halo_stat_rows_total(p) / samples) : 0;
 }
 
+// LB_GEMM_GN_A: what the emitter asks before it folds a GroupNorm (+ SiLU) into the 3x3 conv `pp` describes (include/lb_hip_gn_a.h) -
+// the routing of lb_gemm_f16 below, then the kernel's own conditions and the measured policy (conv3_halo.hip).  The narrow-N kernel
+// is a streaming kernel that saves a read and a write of its whole input for a map it runs once: +239 us (29.9 %) at B = 17 and
+// +32 us (28.2 %) at B = 2 for the VAE's conv_out (profiles/halo_gn_ab.txt), so it is in wherever the mode allows.
+int lb_conv3x3_halo_gn_a_able(const LbGemmParams& p);
+int lb_conv3x3_halo_gn_a_policy(const LbGemmParams& p);
+int lb_conv_halo_gn_a_mode();
+extern "C" void lb_conv_halo_gn_a_plan(const LbGemmParams* pp, int* fuse, int* kind) {
+    int f = 0, k = 0;
+    if (pp != nullptr && pp->conv && pp->M > 0 && pp->N > 0 && pp->Hin > 0 && pp->Win > 0 && pp->scatter == 0 &&
+        !(pp->flags & (LB_GEMM_C64 | LB_GEMM_GN_A))) {
+        const LbGemmParams& p = *pp;
+        if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p)) {
+            k = 8;
+            f = lb_conv_halo_gn_a_mode() != 0;
+        } else if (use_halo(p) && lb_conv3x3_halo_gn_a_able(p)) {
+            k = 3;
+            f = lb_conv3x3_halo_gn_a_policy(p);
+        }
+    }
+    if (fuse) *fuse = f;
+    if (kind) *kind = k;
+}
+
 extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     LbGemmParams p = *pp;
     const bool geglu = (p.flags & LB_GEMM_GEGLU) != 0;
@@ -610,6 +634,7 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     if (p.flags & LB_GEMM_C64) {                    // opt-in: this kernel or a refusal, never another route
+        LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "lb_gemm_f16: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only");
         if (const int rc = lb_conv3_c64_check(p)) return rc;
         LB_DISPATCH("conv3x3_c64", lb_conv3_c64_launch(p, s));
     }
@@ -626,6 +651,8 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
         if (const int rc = lb_conv3x3_halo_check(p)) return rc;
         LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
     }
+    LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "lb_gemm_f16: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only "
+                                          "(ask lb_conv_halo_gn_a_plan before flagging a conv)");
     if (p.flags & LB_GEMM_HALO_KSPLIT) {           // not a halo launch: `partial` is the K-split workspace of that kernel, not split-K slabs
         p.flags &= ~LB_GEMM_HALO_KSPLIT;
         p.partial = nullptr;

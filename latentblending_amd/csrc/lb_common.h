@@ -139,6 +139,21 @@ __device__ __forceinline__ float lb_silu(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f));
 }
 
+// GroupNorm as a per-(sample, channel) affine map, shared by gn_apply_kernel (norm.hip), the table kernel behind
+// lb_groupnorm_affine_from_stats and the convs that apply the map to their A operand (LB_GEMM_GN_A: conv3_halo.hip,
+// conv3_narrow.hip): ONE spelling of each expression, so that the fp16 operand a fused conv multiplies is bit for bit
+// the value the apply pass would have stored.
+__device__ __forceinline__ void lb_gn_affine(float rstd, float mean, float gamma, float beta, float& sc, float& sh) {
+    const float a = rstd * gamma;
+    sc = a;
+    sh = beta - mean * a;
+}
+__device__ __forceinline__ f16 lb_gn_apply(float x, float sc, float sh, int silu) {
+    float t = __builtin_fmaf(x, sc, sh);
+    if (silu) t = lb_silu(t);
+    return (f16)t;
+}
+
 // erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, far below the fp16 output rounding): branch-free,
 // 1 rcp + 1 exp2 + 8 FMA-class ops instead of the ~40-instruction libm erff with its two branches.
 __device__ __forceinline__ float lb_erf(float x) {

@@ -157,20 +157,14 @@ __global__ void __launch_bounds__(256) gn_apply_kernel(const T* __restrict__ x,
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int grp = (c0 + e) / cpg;
-            const float a = rstd_s[grp] * gamma[c0 + e];
-            sc[e] = a;
-            sh[e] = beta[c0 + e] - mean_s[grp] * a;
+            lb_gn_affine(rstd_s[grp], mean_s[grp], gamma[c0 + e], beta[c0 + e], sc[e], sh[e]);
         }
         const T* src = x + ((long)b * HW) * ldx + c0;
         f16* dst = y + ((long)b * HW) * ldy + c0;
         auto finish = [&](const float (&val)[8], int px) {
             f16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float t = __builtin_fmaf(val[e], sc[e], sh[e]);
-                if (silu) t = lb_silu(t);
-                o[e] = (f16)t;
-            }
+            for (int e = 0; e < 8; ++e) o[e] = lb_gn_apply(val[e], sc[e], sh[e], silu);
             *reinterpret_cast<f16x8*>(dst + (long)px * ldy) = o;
         };
         int px = px_begin + r;
@@ -483,6 +477,65 @@ extern "C" int lb_groupnorm_from_stats(const void* x, void* y, const float* gamm
     LB_REQUIRE(groups > 0 && groups <= GN_MAX_GROUPS && C % groups == 0, "lb_groupnorm_from_stats: groups");
     LB_DISPATCH("lb_groupnorm_from_stats", groupnorm_from_stats_impl(x, y, gamma, beta, ch_stats, workspace, B, HW, C, ldx, ldy,
                                                                      groups, eps, silu, x_is_f32, stat_rows_per_sample, s));
+}
+
+// ------------------------------------------------------------------------------------------
+// The same statistics as an AFFINE TABLE for a conv that applies the GroupNorm to its own A operand (LB_GEMM_GN_A):
+// table[b][c] = (scale, shift) with y = x * scale + shift - exactly the sc / sh gn_apply_kernel folds per channel.  One launch:
+// block (group, sample) runs gn_fold_stats_kernel's fold (same rows per thread, same reduction tree), thread 0 then does what
+// gn_apply_kernel's prologue does with a one-chunk partial (its eight interleaved subsets hold the partial and seven zeros: the
+// same double), and the group's channels each write their pair through lb_gn_affine.  x is not read at all.
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) gn_affine_table_kernel(const float2* __restrict__ ch_stats, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float2* __restrict__ table, int HW, int C,
+                                                              int groups, float eps, int rows_per_sample, long total_rows) {
+    __shared__ double red_s[256], red_q[256];
+    __shared__ float stat[2];
+    const int grp = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int cpg = C / groups;
+    double s = 0, q = 0;
+    for (int c = 0; c < cpg; ++c) {
+        const float2* run = ch_stats + (long)(grp * cpg + c) * total_rows + (long)b * rows_per_sample;
+        for (int r = tid; r < rows_per_sample; r += 256) {
+            const float2 v = run[r];
+            s += (double)v.x;
+            q += (double)v.y;
+        }
+    }
+    red_s[tid] = s;
+    red_q[tid] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) { red_s[tid] += red_s[tid + w]; red_q[tid] += red_q[tid + w]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double fs = 0.0 + red_s[0], fq = 0.0 + red_q[0];     // (the apply pass starts its fold from +0)
+        const double cnt = (double)HW * cpg;
+        const double mean = fs / cnt;
+        double var = fq / cnt - mean * mean;
+        if (var < 0) var = 0;
+        stat[0] = (float)mean;
+        stat[1] = (float)(1.0 / sqrt(var + (double)eps));
+    }
+    __syncthreads();
+    for (int c = tid; c < cpg; c += 256) {
+        const int ch = grp * cpg + c;
+        float2 t;
+        lb_gn_affine(stat[1], stat[0], gamma[ch], beta[ch], t.x, t.y);
+        table[(long)b * C + ch] = t;
+    }
+}
+
+extern "C" int lb_groupnorm_affine_from_stats(const float* ch_stats, const float* gamma, const float* beta, float* table, int B,
+                                              int HW, int C, int groups, float eps, int stat_rows_per_sample, void* stream) {
+    LB_REQUIRE(B > 0 && HW > 0 && C > 0 && stat_rows_per_sample > 0 && ch_stats != nullptr && table != nullptr,
+               "lb_groupnorm_affine_from_stats: sizes");
+    LB_REQUIRE(C % 8 == 0 && C <= 4096, "lb_groupnorm_affine_from_stats: C multiple of 8, C <= 4096");
+    LB_REQUIRE(groups > 0 && groups <= GN_MAX_GROUPS && C % groups == 0, "lb_groupnorm_affine_from_stats: groups");
+    LB_DISPATCH_STMT("lb_groupnorm_affine_from_stats",
+                     hipLaunchKernelGGL(gn_affine_table_kernel, dim3(groups, B), dim3(256), 0, s, (const float2*)ch_stats, gamma, beta,
+                                        (float2*)table, HW, C, groups, eps, stat_rows_per_sample, (long)B * stat_rows_per_sample));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -33,6 +33,7 @@ class LbGemmParams(C.Structure):
         ("splitk", C.c_int), ("zero_page", C.c_void_p),
         ("scatter", C.c_int), ("sc_py", C.c_int), ("sc_px", C.c_int), ("reserved_", C.c_int),
         ("ln_colsum", C.c_void_p), ("ln_eps", C.c_float), ("reserved2_", C.c_int), ("ch_stats", C.c_void_p), ("ch_stats_rows", C.c_int),
+        ("gn_table", C.c_void_p), ("gn_silu", C.c_int),
     ]
 
 
@@ -49,6 +50,7 @@ GEMM_OUT_F32, GEMM_RES_F32, GEMM_GEGLU, GEMM_TRANS_OUT, GEMM_SILU, GEMM_RELU, GE
 GEMM_QUICK_GELU, GEMM_GELU, GEMM_CH_STATS = 128, 256, 512
 GEMM_HALO_RAGGED = 1024      # opt-in ragged tiles of the 3x3 halo conv (include/lb_hip.h)
 GEMM_HALO_KSPLIT = 4096     # opt-in K-split form of the 3x3 halo conv: partial = lb_conv_halo_ksplit_workspace_bytes (include/lb_hip.h)
+GEMM_GN_A = 8192            # A consumed through a GroupNorm affine table (gn_table / gn_silu): halo and narrow-N 3x3 convs (include/lb_hip.h)
 GEMM_C64 = 2048              # opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights: that kernel or a refusal (include/lb_hip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
@@ -148,6 +150,14 @@ HOST_SIGNATURES = {
     "lb_conv_halo_set_ksplit": (None, [_i, _i]),
 }
 
+# GroupNorm folded into the consuming 3x3 conv (LB_GEMM_GN_A, include/lb_hip_gn_a.h): the table launcher (checked like every
+# launcher; a program records it under its own name), the plan the emitter asks and the policy switch
+GN_A_SIGNATURES = {
+    "lb_groupnorm_affine_from_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
+    "lb_conv_halo_gn_a_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lb_conv_halo_set_gn_a": (None, [_i, _i]),
+}
+
 _NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
              "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan","lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
              "lb_program_destroy", "lb_program_recording", "lb_program_num_ops", "lb_program_op_name"}
@@ -191,6 +201,11 @@ for _name, (_res, _args) in HOST_SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
     setattr(api, _name, _fn)
+for _name, (_res, _args) in GN_A_SIGNATURES.items():
+    _fn = getattr(_lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+    setattr(api, _name, _wrap(_name, _fn) if _res is _i else _fn)
 for _name, (_res, _args) in STUDY_SIGNATURES.items():
     _fn = getattr(_lib, _name, None)
     if _fn is not None:

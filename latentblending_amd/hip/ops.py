@@ -390,6 +390,17 @@ def groupnorm_from_stats(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tenso
     return y
 
 
+def groupnorm_affine_from_stats(gamma: torch.Tensor, beta: torch.Tensor, groups: int, eps: float, ch_stats: torch.Tensor,
+                                rows_per_sample: int, B: int, HW: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The GroupNorm ``groupnorm_from_stats`` would apply, as a table [B, C, 2] fp32 of (scale, shift) per (sample, channel):
+    y = x * scale + shift.  The operand of a conv flagged ``lib.GEMM_GN_A`` (``gn_table``); x itself is not read."""
+    C_ = gamma.numel()
+    table = torch.empty(B, C_, 2, dtype=F32, device=gamma.device) if out is None else out
+    api.lb_groupnorm_affine_from_stats(ch_stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), table.data_ptr(), B, HW, C_, groups,
+                                       eps, rows_per_sample, stream_ptr())
+    return table
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     M, Cc = x.shape
     y = torch.empty_like(x)

@@ -127,6 +127,16 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+class GnOperand:
+    """A GroupNorm whose consumer is one 3x3 conv (``Emitter.gn_operand``): the raw tensor, the GroupNorm's arguments, and what was
+    emitted for it - the affine table of a conv that applies the GroupNorm itself, or the scratch buffer a GroupNorm launch filled."""
+
+    def __init__(self, x: torch.Tensor, args: dict):
+        self.x, self.args = x, args
+        self.table: Optional[torch.Tensor] = None
+        self.scratch: Optional[torch.Tensor] = None
+
+
 class Emitter:
     """Helpers shared by the UNet / VAE / LPIPS program builders.  All tensors are views into an
     ``Arena`` (activations) or packed weights; nothing here synchronises or allocates through
@@ -153,6 +163,10 @@ class Emitter:
         # counter area (zeroed once: every launch leaves its counters zero) in front of the slabs all launches share.
         self.halo_ksplit = True
         self.ws_ksplit: Optional[torch.Tensor] = None
+        # a GroupNorm (+ SiLU) that reads its statistics from the producing conv and feeds one 3x3 conv is folded into that conv
+        # (LB_GEMM_GN_A: ``gemm(..., gn=...)``) where the library's own plan says so (lb_conv_halo_gn_a_plan); False: no plan call,
+        # the GroupNorm launch and its output buffer as ever
+        self.gn_a = True
 
     def _ragged_flag(self, p: LbGemmParams) -> int:
         """LB_GEMM_HALO_RAGGED or 0 for the 3x3 / stride 1 conv ``p`` describes (the library's own plan, with and without the bit).
@@ -217,6 +231,18 @@ class Emitter:
         p.partial = self.ws_ksplit.data_ptr() + self._KSPLIT_COUNTER_BYTES - counters
         return True
 
+    def _gn_a_fuse(self, p: LbGemmParams, x: torch.Tensor, gn: dict) -> bool:
+        """Fold the GroupNorm ``gn`` of ``x`` into the conv ``p`` (complete but for the flag)?  Only with producer statistics, an fp16
+        stream tensor whose channels are the conv's (no padding in between), and the library's plan (route, whole tiles, unsplit,
+        measured policy: lb_conv_halo_gn_a_plan / lb_conv_halo_set_gn_a)."""
+        if not self.gn_a or gn.get("ch_stats") is None or x.dtype != F16 or not p.conv:
+            return False
+        if p.Cin != int(gn["C_"]) or p.ldx != p.Cin or gn.get("ldx") not in (None, p.Cin):
+            return False
+        fuse, kind = C.c_int(), C.c_int()
+        api.lb_conv_halo_gn_a_plan(C.byref(p), C.byref(fuse), C.byref(kind))
+        return bool(fuse.value)
+
     def _gn_ws(self, B: int, groups: int) -> torch.Tensor:
         need = api.lb_groupnorm_workspace_bytes(B, groups) // 8
         if self.ws_gn is None or self.ws_gn.numel() < need:
@@ -230,9 +256,59 @@ class Emitter:
              residual=None, rowvec=None, rows_per_batch: int = 0, flags: int = 0, alpha: float = 1.0,
              lda: Optional[int] = None, ldc: Optional[int] = None, ldr: Optional[int] = None,
              ld_rowvec: Optional[int] = None, conv: Optional[dict] = None, splitk: bool = True,
-             ln: Optional[Tuple[torch.Tensor, float]] = None, ch_stats: Optional[torch.Tensor] = None):
+             ln: Optional[Tuple[torch.Tensor, float]] = None, ch_stats: Optional[torch.Tensor] = None,
+             gn: Optional["GnOperand"] = None):
         """``ln`` = (colsum [N] fp32, eps): A is consumed through a LayerNorm folded into this GEMM (LB_GEMM_LN_A; W and
-        bias must already carry gamma / beta, see ``NativeUNet._ln_linear``); row statistics from the A fragments in the K loop."""
+        bias must already carry gamma / beta, see ``NativeUNet._ln_linear``); row statistics from the A fragments in the K loop.
+
+        ``gn`` = what ``gn_operand`` returned for this very conv (A = the raw tensor): the conv consumes GroupNorm(A), either through
+        the affine table (LB_GEMM_GN_A) or from the scratch buffer the GroupNorm launch filled; both go back to the arena here."""
+        p = self._gemm_params(A, W, out, M=M, bias=bias, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch, flags=flags,
+                              alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec, conv=conv, splitk=splitk, ln=ln,
+                              ch_stats=ch_stats)
+        N, K = W.shape
+        n_out = N // 2 if flags & lib.GEMM_GEGLU else N
+        if gn is not None:
+            if gn.table is not None:
+                if not self._gn_a_fuse(p, gn.x, gn.args):
+                    raise RuntimeError("Emitter.gemm: the conv is not the one gn_operand planned the GroupNorm fold for")
+                p.flags |= lib.GEMM_GN_A
+                p.gn_table, p.gn_silu = gn.table.data_ptr(), int(bool(gn.args["silu"]))
+            else:
+                p.A = gn.scratch.data_ptr()
+        api.lb_gemm_f16(C.byref(p), _stream())
+        if gn is not None:
+            self.arena.release(gn.scratch)
+            self.arena.release(gn.table)
+            gn.scratch = gn.table = None
+        mult = 4.0 if p.scatter == 2 else 1.0          # (four parities: four times the rows, weights and outputs)
+        self.gemm_log.append({"M": M, "N": N, "K": K, "flops": mult * 2.0 * M * N * K, "conv": conv is not None,
+                              "bytes": mult * 2.0 * (N * K + M * n_out) + (2.0 * M * K if conv is None else 0.0)})
+        return out
+
+    def gn_operand(self, x: torch.Tensor, W: torch.Tensor, *, M: int, conv: dict, flags: int = 0, has_residual: bool = False,
+                   **gn) -> "GnOperand":
+        """Emit the GroupNorm side of "3x3 conv of GroupNorm(x)" NOW and return the operand for the conv's ``gemm(x, ..., gn=...)``.
+        ``gn`` = the keyword arguments of ``groupnorm`` plus gamma / beta.  Where the library's plan fuses (``_gn_a_fuse``: producer
+        statistics, fp16 stream, route, whole tiles, unsplit, measured policy) the emitted op is the table kernel
+        (lb_groupnorm_affine_from_stats) and the conv will carry LB_GEMM_GN_A and read the raw x: no normalised buffer, no
+        lb_groupnorm_from_stats.  Everywhere else: the GroupNorm launch into a scratch buffer, exactly as ever."""
+        op = GnOperand(x, dict(gn))
+        plan = self._gemm_params(x, W, x, M=M, residual=x if has_residual else None, flags=flags, conv=conv)     # (pointers: only their nullness counts)
+        if self._gn_a_fuse(plan, x, gn):
+            B_, C_, st = int(gn["B"]), int(gn["C_"]), gn["ch_stats"]
+            op.table = self.arena.alloc((B_, C_, 2), F32)
+            api.lb_groupnorm_affine_from_stats(st[0].data_ptr(), gn["gamma"].data_ptr(), gn["beta"].data_ptr(), op.table.data_ptr(),
+                                               B_, int(gn["HW"]), C_, int(gn.get("groups", 32)), float(gn["eps"]), int(st[1]),
+                                               _stream())
+        else:
+            op.scratch = self.arena.alloc(tuple(x.shape[:-1]) + (int(gn["C_"]),))
+            self.groupnorm(x, op.scratch, gn["gamma"], gn["beta"], **{k: v for k, v in gn.items() if k not in ("gamma", "beta")})
+        return op
+
+    def _gemm_params(self, A, W, out, *, M, bias=None, residual=None, rowvec=None, rows_per_batch=0, flags=0, alpha=1.0, lda=None,
+                     ldc=None, ldr=None, ld_rowvec=None, conv=None, splitk=True, ln=None, ch_stats=None) -> LbGemmParams:
+        """The parameter block ``gemm`` launches (everything but a GroupNorm fold)."""
         p = LbGemmParams()
         N, K = W.shape
         p.A, p.W, p.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
@@ -268,11 +344,7 @@ class Emitter:
             p.flags |= self._ragged_flag(p)
         if conv is not None:
             self._halo_ksplit(p)
-        api.lb_gemm_f16(C.byref(p), _stream())
-        mult = 4.0 if p.scatter == 2 else 1.0          # (four parities: four times the rows, weights and outputs)
-        self.gemm_log.append({"M": M, "N": N, "K": K, "flops": mult * 2.0 * M * N * K, "conv": conv is not None,
-                              "bytes": mult * 2.0 * (N * K + M * n_out) + (2.0 * M * K if conv is None else 0.0)})
-        return out
+        return p
 
     def plan(self, M: int, N: int, K: int, flags: int = 0) -> Tuple[int, int]:
         """(tile, split-K) the library would choose for a plain GEMM emitted by ``gemm`` (lb_gemm_plan)."""

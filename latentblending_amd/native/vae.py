@@ -174,8 +174,25 @@ class VAEProgram:
         out._lb_chstats = (buf, rows)
         return buf
 
-    def _stream_conv(self, x, name, B, H, W, cin, cout, *, residual=None, out=None, stats=True):
-        """3x3 conv whose output goes to the residual stream (or feeds only the next GroupNorm)."""
+    def _stream_conv_args(self, name, B, H, W, cin, residual):
+        sc = self.scaled
+        cin_p = _pad(cin, 8)
+        flags = 0 if sc else (lib.GEMM_OUT_F32 | (lib.GEMM_RES_F32 if residual else 0))
+        return flags, dict(Hin=H, Win=W, Cin=cin_p, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p)
+
+    def _gn_for_conv(self, x, norm, silu, name, B, H, W, cin, *, residual=False):
+        """The GroupNorm ``norm`` of ``x`` whose only consumer is the stream conv ``name``: emitted here (see ``Emitter.gn_operand``:
+        the table kernel of a conv that applies the GroupNorm itself, or the GroupNorm launch as ever); pass the result to
+        ``_stream_conv(x, name, ..., gn=...)``."""
+        flags, conv = self._stream_conv_args(name, B, H, W, cin, residual)
+        op = self.em.gn_operand(x, self.net.w[name + ".weight"], M=B * H * W, conv=conv, flags=flags, has_residual=residual,
+                                **self._gn_args(x, norm, B, H * W, cin, silu))
+        self._gn_done(x)
+        return op
+
+    def _stream_conv(self, x, name, B, H, W, cin, cout, *, residual=None, out=None, stats=True, gn=None):
+        """3x3 conv whose output goes to the residual stream (or feeds only the next GroupNorm).  ``gn`` = what ``_gn_for_conv``
+        returned for this conv: it consumes GroupNorm(x)."""
         w, sc = self.net.w, self.scaled
         cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
         if out is None:
@@ -184,8 +201,22 @@ class VAEProgram:
         st = self._stats_for(out, B, H, W, cin_p, cout_p) if stats else None
         self.em.gemm(x, w[name + ".weight"], out, M=B * H * W, bias=w[name + (".bias_s" if sc else ".bias")],
                      residual=residual, flags=flags, alpha=STREAM_SCALE if sc else 1.0, ch_stats=st,
-                     conv=dict(Hin=H, Win=W, Cin=cin_p, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p))
+                     conv=dict(Hin=H, Win=W, Cin=cin_p, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p),
+                     gn=gn)
         return out
+
+    def _gn_args(self, x, name, B, HW, c, silu):
+        """The GroupNorm ``name`` of ``x`` as the ``gn`` argument of ``Emitter.gemm`` (same numbers as ``_gn``)."""
+        w = self.net.w
+        eps = 1e-6 * (STREAM_SCALE * STREAM_SCALE if self.scaled else 1.0)     # GroupNorm of a scaled tensor
+        return dict(gamma=w[name + ".weight"], beta=w[name + ".bias"], B=B, HW=HW, C_=c, eps=eps, silu=silu,
+                    groups=self.net.cfg.norm_groups, ch_stats=getattr(x, "_lb_chstats", None))
+
+    def _gn_done(self, x):
+        st = getattr(x, "_lb_chstats", None)
+        if st is not None:
+            self.arena.release(st[0])
+            x._lb_chstats = None
 
     def _gn(self, x, out, name, B, HW, c, silu):
         w = self.net.w
@@ -208,13 +239,9 @@ class VAEProgram:
 
     def _resnet(self, x, p, B, H, W, cin, cout):
         em, w, ar, sc = self.em, self.net.w, self.arena, self.scaled
-        n1 = ar.alloc((B, H, W, cin))
-        self._gn(x, n1, p + ".norm1", B, H * W, cin, True)
-        h = self._stream_conv(n1, p + ".conv1", B, H, W, cin, cout)
-        ar.release(n1)
-        n2 = ar.alloc((B, H, W, cout))
-        self._gn(h, n2, p + ".norm2", B, H * W, cout, True)
-        ar.release(h)
+        g1 = self._gn_for_conv(x, p + ".norm1", True, p + ".conv1", B, H, W, cin)
+        h = self._stream_conv(x, p + ".conv1", B, H, W, cin, cout, gn=g1)
+        g2 = self._gn_for_conv(h, p + ".norm2", True, p + ".conv2", B, H, W, cout, residual=True)
         if cin != cout:
             x16, owned = self._stream_as_operand(x, B, H, W, cin)
             xs = ar.alloc((B, H, W, cout), F16 if sc else F32)
@@ -226,8 +253,8 @@ class VAEProgram:
                 ar.release(x16)
         else:
             xs = x
-        out = self._stream_conv(n2, p + ".conv2", B, H, W, cout, cout, residual=xs)
-        ar.release(n2)
+        out = self._stream_conv(h, p + ".conv2", B, H, W, cout, cout, residual=xs, gn=g2)
+        ar.release(h)
         if xs is not x:
             ar.release(xs)
         return out
@@ -317,14 +344,14 @@ class VAEProgram:
                 ar.release(h)
                 h = up
                 sh, sw = 2 * sh, 2 * sw
-        n = ar.alloc((B, sh, sw, rev[-1]))
-        self._gn(h, n, "decoder.conv_norm_out", B, sh * sw, rev[-1], True)
-        ar.release(h)
         cin_p = _pad(rev[-1], 8)
-        em.gemm(n, w["decoder.conv_out.weight"], self.image_f32, M=B * sh * sw, bias=w["decoder.conv_out.bias"],
-                flags=lib.GEMM_OUT_F32,
-                conv=dict(Hin=sh, Win=sw, Cin=cin_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p))
-        ar.release(n)
+        conv_out = dict(Hin=sh, Win=sw, Cin=cin_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p)
+        g = em.gn_operand(h, w["decoder.conv_out.weight"], M=B * sh * sw, conv=conv_out, flags=lib.GEMM_OUT_F32,
+                          **self._gn_args(h, "decoder.conv_norm_out", B, sh * sw, rev[-1], True))
+        self._gn_done(h)
+        em.gemm(h, w["decoder.conv_out.weight"], self.image_f32, M=B * sh * sw, bias=w["decoder.conv_out.bias"],
+                flags=lib.GEMM_OUT_F32, conv=conv_out, gn=g)
+        ar.release(h)
         api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw,
                               _pad(cfg.out_channels, 4), 1, _stream())
 
