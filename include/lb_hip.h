@@ -193,7 +193,35 @@ void lb_gemm_pp_set_group(int gm);                /* tuning: tile order of the p
 void lb_gemm_set_depth(int depth);               /* testing: 1 = one K-tile in flight, 0 = default ring */
 int lb_gemm_plan(const LbGemmParams* p, int* tile, int* splitk, long* blocks); /* the tile (1..5) / split-K / grid lb_gemm_f16 would use; launches nothing.
                                                   * As in lb_gemm_f16, a problem flagged LB_GEMM_HALO_KSPLIT that does not route to the halo kernel
-                                                  * (tile code 6) is planned without the flag and without `partial`: that workspace is no split-K one */
+                                                  * (tile code 6) is planned without the flag and without `partial`: that workspace is no split-K one.
+                                                  * A scatter = 2 conv is answered with the GEMM tile it would get as an implicit GEMM, as ever, although
+                                                  * lb_gemm_f16 takes it to the halo upconv: the route field of lb_conv_plan is the truthful one */
+/* Everything an emitter needs to know about ONE conv (or GEMM), in one call that launches nothing: where lb_gemm_f16 would take these
+ * parameters, and what each plan export answers for them - lb_gemm_plan (tile, splitk, blocks), lb_conv_halo_plan (halo_*),
+ * lb_gemm_ch_stat_rows (stat_rows), lb_conv_halo_ksplit_plan and lb_conv_halo_ksplit_workspace_bytes (ksplit_*: the workspace is the
+ * counters, then the slabs; both sizes are 0 unless ksplit_split) and lb_conv_halo_gn_a_plan (gn_a_*).  ragged_kind / ragged_tile_w:
+ * for parameters without LB_GEMM_HALO_RAGGED whose halo_kind is 0, what lb_conv_halo_plan reports with the bit set (3 = the ragged-tile
+ * form takes the conv), else 0.  `route` is decided by the one routing function of the library; lb_gemm_plan's tile code is not a
+ * route (it answers a scatter = 2 conv with a GEMM tile).  Returns what lb_gemm_plan returns; after a refusal tile, splitk and blocks
+ * are 0 and the other fields are filled all the same. */
+enum { LB_ROUTE_GEMM = 0,         /* implicit / plain GEMM (gemm.hip and its direct-to-LDS / ping-pong forms) */
+       LB_ROUTE_C64 = 1,          /* LB_GEMM_C64: conv3_c64.hip or a refusal */
+       LB_ROUTE_UPCONV_HALO = 2,  /* scatter = 2: the 2x2 sub-pixel form of the halo kernel or a refusal */
+       LB_ROUTE_NARROW = 3,       /* N <= 16 3x3 conv: conv3_narrow.hip */
+       LB_ROUTE_HALO3 = 4 };      /* 3x3 halo-tile conv: conv3_halo.hip */
+typedef struct LbConvPlan {
+    int route;
+    int tile, splitk;
+    long blocks;
+    int halo_kind, halo_tile_w;
+    long halo_items, halo_grid;
+    int stat_rows;
+    int ksplit_split;
+    long ksplit_units, ksplit_grid, ksplit_counter_bytes, ksplit_slab_bytes;
+    int gn_a_fuse, gn_a_kind;
+    int ragged_kind, ragged_tile_w;
+} LbConvPlan;
+int lb_conv_plan(const LbGemmParams* params, LbConvPlan* plan);
 /* 3x3 / stride 1 / pad 1 conv from an LDS-resident halo tile; same parameter block as lb_gemm_f16 (conv = 1,
  * KH = KW = 3, Cin % 64 == 0, Win % 16 == 0 - or any Hin x Win with LB_GEMM_HALO_RAGGED -, zero_page set).  lb_gemm_f16 routes eligible convs here by itself
  * (lb_gemm_plan reports tile code 6); lb_gemm_set_halo: 0 = never, 1 = when the halo grid fills the chip

@@ -620,24 +620,24 @@ static void halo_grid(const LbGemmParams& p, int tw, int ks, long& items, long& 
         grid = (long)(halo_num_cus() / period) * period;
 }
 
-// LB_GEMM_CH_STATS: row blocks of the whole launch = (items / channel blocks) * 4 wave rows - the host twin of `stat_rows` in
-// the kernel's epilogue (0 = not a halo launch)
+// LB_GEMM_CH_STATS: row blocks of a whole upconv launch = (items / channel blocks) * 4 wave rows - the host twin of `stat_rows` in
+// the kernel's epilogue (0 = not eligible; the 3x3 form: the same arithmetic on LbHaloPlan.items)
 int lb_upconv_halo_eligible(const LbGemmParams& p);
 int lb_conv3x3_halo_eligible(const LbGemmParams& p);
 long lb_conv_halo_stat_rows_total(const LbGemmParams& p) {
-    int tw = 0, ks = 0;
-    if ((tw = lb_upconv_halo_eligible(p)) != 0) ks = 2;
-    else if ((tw = lb_conv3x3_halo_eligible(p)) != 0) ks = 3;
-    if (!ks) return 0;
+    const int tw = lb_upconv_halo_eligible(p);
+    if (!tw) return 0;
     long items, grid;
-    halo_grid(p, tw, ks, items, grid);
+    halo_grid(p, tw, 2, items, grid);
     return items / ((p.N + 127) / 128) * 4;
 }
 
 static int g_halo_gn_a_mode = 1, g_halo_gn_a_grid = 0;     // (lb_conv_halo_set_gn_a, below)
 
+// `nblk` work items on `grid` blocks: halo_grid's answer (lb_upconv_halo_launch), or the LbHaloPlan's (lb_conv3x3_halo_launch: the K-split form
+// walks an even share of the units on ks_grid blocks)
 template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false>
-static int launch_halo(const LbGemmParams& p, hipStream_t stream, long ksp_grid = 0) {
+static int launch_halo(const LbGemmParams& p, hipStream_t stream, long nblk, long grid) {
     constexpr int TH = 256 / TW;
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
     // (KSP: the "last arriver" word; GNA: 1 KiB of table per wave)
@@ -650,9 +650,7 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream, long ksp_grid 
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
-    long nblk, grid;
-    halo_grid(p, TW, KS, nblk, grid);          // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
-    if (KSP) grid = ksp_grid;                  // (one block per CU walks an even share of the units: halo_ksplit_plan)
+    // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
     if (GNA && g_halo_gn_a_grid > 0) {         // (tests: a multiple of the weight-slab period, at most one block per item)
         const long period = (p.N + BN - 1) / BN;
         grid = g_halo_gn_a_grid / period * period;
@@ -681,24 +679,23 @@ int lb_upconv_halo_eligible(const LbGemmParams& p) {
 
 // What a halo launch refuses, checked by every entry point (the two launchers here, the router in lb_gemm_f16) BEFORE it
 // dispatches: a recording refuses what a direct call refuses, at the call that caused it.  The launch functions trust their caller.
-static int halo_tiles_check(const LbGemmParams& p, int tw, int ks) {
-    long items, grid;
-    halo_grid(p, tw, ks, items, grid);
-    LB_REQUIRE(items < (1l << 30), "halo conv: too many tiles for one launch");
-    return 0;
-}
-
 int lb_upconv_halo_check(const LbGemmParams& p) {
     LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "halo upconv: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only");
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || (p.ch_stats != nullptr && p.ch_stats_rows == lb_conv_halo_stat_rows_total(p)),
                "halo upconv: LB_GEMM_CH_STATS needs ch_stats with ch_stats_rows = B * lb_gemm_ch_stat_rows()");
-    return halo_tiles_check(p, lb_upconv_halo_eligible(p), 2);
+    long items, grid;
+    halo_grid(p, lb_upconv_halo_eligible(p), 2, items, grid);
+    LB_REQUIRE(items < (1l << 30), "halo conv: too many tiles for one launch");
+    return 0;
 }
 
 int lb_upconv_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
-    return lb_upconv_halo_eligible(p) == 32 ? launch_halo<128, 32, 2>(p, stream) : launch_halo<128, 16, 2>(p, stream);
+    const int tw = lb_upconv_halo_eligible(p);
+    long items, grid;
+    halo_grid(p, tw, 2, items, grid);
+    return tw == 32 ? launch_halo<128, 32, 2>(p, stream, items, grid) : launch_halo<128, 16, 2>(p, stream, items, grid);
 }
 
 // nearest-2x upsample + 3x3 conv as ONE launch: W = [4][N][ldw] stacked sub-pixel kernels (parity py*2+px), C = [B][2H][2W][ldc]
@@ -729,8 +726,6 @@ int lb_conv3x3_halo_eligible(const LbGemmParams& p) {
     const long t32 = (long)((p.Win + 31) / 32) * ((p.Hin + 7) / 8), t16 = (long)((p.Win + 15) / 16) * ((p.Hin + 15) / 16);
     return t16 < t32 ? 16 : 32;
 }
-// (of an eligible problem) the image does not divide into tiles of the width lb_conv3x3_halo_eligible chose: the RAG instantiation
-static bool halo3_ragged(const LbGemmParams& p, int tw) { return p.Win % tw != 0 || p.Hin % (256 / tw) != 0; }
 
 // ---- K-split form (LB_GEMM_HALO_KSPLIT): host twins of the kernel's unit walk ------------------------------------------------------
 // mode 0 = never, 1 = the policy below (default), 2 = every flagged launch with Cin >= 128; grid > 0 overrides G (tests: a workspace
@@ -751,76 +746,61 @@ extern "C" void lb_conv_halo_set_ksplit(int mode, int grid) {
 // (profiles/halo_ksplit_ab_close.txt): +0.3 (a tie), +3.8 and +1.2 us, the last two beyond their spread.
 static constexpr long HALO_KSPLIT_FIXUP_STEPS = 20;
 static constexpr long HALO_KSPLIT_MARGIN_PCT = 5;       // split only where the estimate wins by this much
-static void halo_ksplit_plan(const LbGemmParams& p, long& units, long& grid, int& split) {
-    units = grid = 0;
-    split = 0;
+// (of a whole-tile problem whose items and unsplit grid are in `h`).  Workspace layout: one int counter per tile (channel block x
+// pixel tile), padded to 256 B, then two 256 x 128 fp32 slabs per block.
+static void halo_ksplit_plan(const LbGemmParams& p, LbHaloPlan& h) {
     if (!(p.flags & LB_GEMM_HALO_KSPLIT) || (p.flags & LB_GEMM_C64) || g_halo_ksplit_mode == 0) return;
     if (p.flags & LB_GEMM_GN_A) return;         // (refused together by lb_conv3x3_halo_check: the K-split form has no GroupNorm-on-A twin)
-    const int tw = lb_conv3x3_halo_eligible(p);
-    if (!tw || halo3_ragged(p, tw) || p.Cin < 128) return;
-    long items, ugrid;
-    halo_grid(p, tw, 3, items, ugrid);
+    if (h.ragged || p.Cin < 128) return;
     const long nchunks = p.Cin / 64;
-    if (items * nchunks >= (1l << 31)) return;
-    units = items * nchunks;
-    grid = g_halo_ksplit_grid > 0 ? g_halo_ksplit_grid : halo_num_cus();
-    if (grid > units) grid = units;
-    if (2 * grid * 256l * 128 * 4 >= (1l << 31)) {              // (the slabs sit behind ONE buffer descriptor: int byte offsets)
-        units = grid = 0;
-        return;
+    if (h.items * nchunks >= (1l << 31)) return;
+    long grid = g_halo_ksplit_grid > 0 ? g_halo_ksplit_grid : halo_num_cus();
+    if (grid > h.items * nchunks) grid = h.items * nchunks;
+    const long slab_bytes = 2 * grid * 256l * 128 * (long)sizeof(float);
+    if (slab_bytes >= (1l << 31)) return;                       // (the slabs sit behind ONE buffer descriptor: int byte offsets)
+    h.ks_units = h.items * nchunks;
+    h.ks_grid = grid;
+    if (g_halo_ksplit_mode >= 2) h.ks_split = 1;
+    else {
+        const long unsplit_steps = (h.items + h.grid - 1) / h.grid * 9 * nchunks;
+        const long split_steps = (h.ks_units + grid - 1) / grid * 9 + HALO_KSPLIT_FIXUP_STEPS;
+        h.ks_split = split_steps * (100 + HALO_KSPLIT_MARGIN_PCT) <= unsplit_steps * 100 ? 1 : 0;
     }
-    if (g_halo_ksplit_mode >= 2) {
-        split = 1;
-        return;
+    if (h.ks_split) {
+        h.ks_counter_bytes = (h.items * 4 + 255) / 256 * 256;
+        h.ks_slab_bytes = slab_bytes;
     }
-    const long unsplit_steps = (items + ugrid - 1) / ugrid * 9 * nchunks;
-    const long split_steps = (units + grid - 1) / grid * 9 + HALO_KSPLIT_FIXUP_STEPS;
-    split = split_steps * (100 + HALO_KSPLIT_MARGIN_PCT) <= unsplit_steps * 100 ? 1 : 0;
 }
-// workspace layout: one int counter per tile (channel block x pixel tile), padded to 256 B, then two 256 x 128 fp32 slabs per block
-static long halo_ksplit_counter_bytes(long items) { return (items * 4 + 255) / 256 * 256; }
+static LbHaloPlan halo_plan_guarded(const LbGemmParams* pp) {   // (the two exports below plan nothing for an empty problem)
+    return pp != nullptr && pp->M > 0 && pp->Hin > 0 && pp->Win > 0 ? lb_conv3x3_halo_plan(*pp) : LbHaloPlan{};
+}
 extern "C" void lb_conv_halo_ksplit_plan(const LbGemmParams* pp, long* units, long* grid, int* split) {
-    long u = 0, g = 0;
-    int s = 0;
-    if (pp != nullptr && pp->M > 0 && pp->Hin > 0 && pp->Win > 0) halo_ksplit_plan(*pp, u, g, s);
-    if (units) *units = u;
-    if (grid) *grid = g;
-    if (split) *split = s;
+    const LbHaloPlan h = halo_plan_guarded(pp);
+    if (units) *units = h.ks_units;
+    if (grid) *grid = h.ks_grid;
+    if (split) *split = h.ks_split;
 }
 extern "C" long lb_conv_halo_ksplit_workspace_bytes(const LbGemmParams* pp) {
-    long u = 0, g = 0;
-    int s = 0;
-    if (pp != nullptr && pp->M > 0 && pp->Hin > 0 && pp->Win > 0) halo_ksplit_plan(*pp, u, g, s);
-    if (!s) return 0;
-    return halo_ksplit_counter_bytes(u / (pp->Cin / 64)) + 2 * g * 256l * 128 * (long)sizeof(float);
-}
-
-long lb_conv3x3_halo_blocks(const LbGemmParams& p) {
-    long tiles = (long)p.M / 256;                       // 256 output pixels per block
-    if (const int tw = (p.flags & LB_GEMM_HALO_RAGGED) ? lb_conv3x3_halo_eligible(p) : 0)       // (ragged: blocks, not pixels / 256)
-        tiles = (long)(p.M / (p.Hin * p.Win)) * ((p.Hin + 256 / tw - 1) / (256 / tw)) * ((p.Win + tw - 1) / tw);
-    return tiles * ((p.N + 127) / 128);
+    const LbHaloPlan h = halo_plan_guarded(pp);
+    return h.ks_counter_bytes + h.ks_slab_bytes;
 }
 
 int lb_conv3x3_halo_check(const LbGemmParams& p) {
+    const LbHaloPlan h = lb_conv3x3_halo_plan(p);
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || (p.ch_stats != nullptr && !(p.flags & LB_GEMM_TRANS_OUT)),
                "halo conv: LB_GEMM_CH_STATS needs ch_stats and a row-major output");
-    LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || p.ch_stats_rows == lb_conv_halo_stat_rows_total(p),
+    LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS) || p.ch_stats_rows == h.items / ((p.N + 127) / 128) * 4,
                "halo conv: ch_stats_rows must be B * lb_gemm_ch_stat_rows() (the row blocks this launch writes per channel)");
-    {
-        long units, grid;
-        int split;
-        halo_ksplit_plan(p, units, grid, split);
-        LB_REQUIRE(!split || p.partial != nullptr,
-                   "halo conv: LB_GEMM_HALO_KSPLIT needs partial = a zeroed workspace of lb_conv_halo_ksplit_workspace_bytes()");
-    }
+    LB_REQUIRE(!h.ks_split || p.partial != nullptr,
+               "halo conv: LB_GEMM_HALO_KSPLIT needs partial = a zeroed workspace of lb_conv_halo_ksplit_workspace_bytes()");
     if (p.flags & LB_GEMM_GN_A) {
         LB_REQUIRE(p.gn_table != nullptr, "halo conv: LB_GEMM_GN_A needs gn_table = the [B][Cin] float2 table of lb_groupnorm_affine_from_stats");
         LB_REQUIRE(!(p.flags & LB_GEMM_HALO_KSPLIT), "halo conv: LB_GEMM_GN_A and LB_GEMM_HALO_KSPLIT exclude each other (the K-split form has no GroupNorm-on-A twin)");
-        LB_REQUIRE(!halo3_ragged(p, lb_conv3x3_halo_eligible(p)), "halo conv: LB_GEMM_GN_A needs an image that divides into whole tiles (no ragged form)");
+        LB_REQUIRE(!h.ragged, "halo conv: LB_GEMM_GN_A needs an image that divides into whole tiles (no ragged form)");
         LB_REQUIRE((reinterpret_cast<uintptr_t>(p.gn_table) & 15) == 0, "halo conv: gn_table must be 16-byte aligned");
     }
-    return halo_tiles_check(p, lb_conv3x3_halo_eligible(p), 3);
+    LB_REQUIRE(h.items < (1l << 30), "halo conv: too many tiles for one launch");
+    return 0;
 }
 
 // ---- GroupNorm on A (LB_GEMM_GN_A): policy ---------------------------------------------------------------------------------------
@@ -841,40 +821,38 @@ extern "C" void lb_conv_halo_set_gn_a(int mode, int grid) {
     g_halo_gn_a_mode = mode < 0 ? 1 : mode;
     g_halo_gn_a_grid = grid > 0 ? grid : 0;
 }
-// 1 = the policy includes this (eligible, whole-tile, unsplit) halo launch
-int lb_conv3x3_halo_gn_a_policy(const LbGemmParams& p) {
-    if (g_halo_gn_a_mode == 0) return 0;
-    if (g_halo_gn_a_mode >= 2) return 1;
-    if ((p.N + 127) / 128 > HALO_GN_A_MAX_BLOCKS) return 0;
-    long items, grid;
-    halo_grid(p, lb_conv3x3_halo_eligible(p), 3, items, grid);
-    return items >= HALO_GN_A_MIN_TILES_PER_BLOCK * grid ? 1 : 0;
-}
 int lb_conv_halo_gn_a_mode() { return g_halo_gn_a_mode; }
-// 1 = a launch of `p` (flags as it would be launched WITHOUT LB_GEMM_GN_A) on this kernel could carry the flag: the whole-tile form,
-// and the K-split plan leaves it unsplit
-int lb_conv3x3_halo_gn_a_able(const LbGemmParams& p) {
-    const int tw = lb_conv3x3_halo_eligible(p);
-    if (!tw || halo3_ragged(p, tw)) return 0;
-    long units, grid;
-    int split;
-    halo_ksplit_plan(p, units, grid, split);
-    return split ? 0 : 1;
+
+// The one host plan of a 3x3 halo launch: tile shape, work items and grid, the K-split answer with its workspace, and whether the
+// launch (flags as it would be launched WITHOUT LB_GEMM_GN_A) could carry that flag and the policy above includes it.
+LbHaloPlan lb_conv3x3_halo_plan(const LbGemmParams& p) {
+    LbHaloPlan h = {};
+    h.tw = lb_conv3x3_halo_eligible(p);
+    if (!h.tw) return h;
+    h.ragged = p.Win % h.tw != 0 || p.Hin % (256 / h.tw) != 0;
+    halo_grid(p, h.tw, 3, h.items, h.grid);
+    halo_ksplit_plan(p, h);
+    h.gn_a_able = !h.ragged && !h.ks_split;
+    h.gn_a_policy = g_halo_gn_a_mode >= 2 || (g_halo_gn_a_mode == 1 && (p.N + 127) / 128 <= HALO_GN_A_MAX_BLOCKS &&
+                                              h.items >= HALO_GN_A_MIN_TILES_PER_BLOCK * h.grid);
+    return h;
 }
 
+// (plans again when a recorded op is replayed: the switches and the device are read then, as ever)
 int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream) {
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
-    const int tw = lb_conv3x3_halo_eligible(p);
+    const LbHaloPlan h = lb_conv3x3_halo_plan(p);
+    const bool w32 = h.tw == 32;
     if (p.flags & LB_GEMM_GN_A)                     // (lb_conv3x3_halo_check passed: whole tiles, no K-split, a table)
-        return tw == 32 ? launch_halo<128, 32, 3, false, false, true>(p, stream) : launch_halo<128, 16, 3, false, false, true>(p, stream);
-    if (halo3_ragged(p, tw)) return tw == 32 ? launch_halo<128, 32, 3, true>(p, stream) : launch_halo<128, 16, 3, true>(p, stream);
-    long units, grid;
-    int split;
-    halo_ksplit_plan(p, units, grid, split);
-    if (split && p.partial != nullptr)
-        return tw == 32 ? launch_halo<128, 32, 3, false, true>(p, stream, grid) : launch_halo<128, 16, 3, false, true>(p, stream, grid);
-    return tw == 32 ? launch_halo<128, 32>(p, stream) : launch_halo<128, 16>(p, stream);
+        return w32 ? launch_halo<128, 32, 3, false, false, true>(p, stream, h.items, h.grid)
+                   : launch_halo<128, 16, 3, false, false, true>(p, stream, h.items, h.grid);
+    if (h.ragged)
+        return w32 ? launch_halo<128, 32, 3, true>(p, stream, h.items, h.grid) : launch_halo<128, 16, 3, true>(p, stream, h.items, h.grid);
+    if (h.ks_split && p.partial != nullptr)
+        return w32 ? launch_halo<128, 32, 3, false, true>(p, stream, h.items, h.ks_grid)
+                   : launch_halo<128, 16, 3, false, true>(p, stream, h.items, h.ks_grid);
+    return w32 ? launch_halo<128, 32>(p, stream, h.items, h.grid) : launch_halo<128, 16>(p, stream, h.items, h.grid);
 }
 
 extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
@@ -893,13 +871,17 @@ extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
 // Host arithmetic of a halo launch (no device work): kind = 0 (not a halo launch), 3 (3x3 form) or 2 (2x2 sub-pixel form),
 // tile width, number of (tile [, parity], channel block) work items and the grid the launcher would use.
 extern "C" void lb_conv_halo_plan(const LbGemmParams* pp, int* kind, int* tile_w, long* items, long* grid) {
-    LbGemmParams p = *pp;
+    const LbGemmParams& p = *pp;
     int k = 0, tw = 0;
-    if (p.flags & LB_GEMM_C64) tw = 0;              // (lb_gemm_f16 takes a flagged problem to conv3_c64.hip: not a halo launch)
-    else if ((tw = lb_upconv_halo_eligible(p)) != 0) k = 2;
-    else if ((tw = lb_conv3x3_halo_eligible(p)) != 0) k = 3;
     long it = 0, gr = 0;
-    if (k) halo_grid(p, tw, k, it, gr);
+    if (p.flags & LB_GEMM_C64) tw = 0;              // (lb_gemm_f16 takes a flagged problem to conv3_c64.hip: not a halo launch)
+    else if ((tw = lb_upconv_halo_eligible(p)) != 0) {
+        k = 2;
+        halo_grid(p, tw, 2, it, gr);
+    } else if (const LbHaloPlan h = lb_conv3x3_halo_plan(p); h.tw != 0) {
+        k = 3;
+        tw = h.tw, it = h.items, gr = h.grid;
+    }
     if (kind) *kind = k;
     if (tile_w) *tile_w = tw;
     if (items) *items = it;

@@ -338,8 +338,6 @@ static constexpr int g_policy_off = 0;     // (the A/B switches of the tile poli
 // 3x3 / stride 1 / pad 1 convs from an LDS-resident halo tile (conv3_halo.hip): 1.27-1.79x the implicit GEMM on
 // every conv of the benchmark's B=17 programs (profiles/r02_halo_bench.txt).  mode 0 = never, 1 = whenever the
 // halo grid has at least LB_HALO_MIN_BLOCKS blocks (default), 2 = whenever eligible (tests / A-B studies).
-int lb_conv3x3_halo_eligible(const LbGemmParams& p);
-long lb_conv3x3_halo_blocks(const LbGemmParams& p);
 int lb_conv3x3_halo_check(const LbGemmParams& p);
 int lb_conv3x3_halo_launch(LbGemmParams p, hipStream_t stream);
 int lb_conv3x3_narrow_eligible(const LbGemmParams& p);
@@ -355,9 +353,16 @@ void lb_conv3_c64_grid(const LbGemmParams& p, long& items, long& grid);
 #define LB_HALO_MIN_BLOCKS 96
 static int g_halo = 1;
 extern "C" void lb_gemm_set_halo(int mode) { g_halo = mode; }
-static bool use_halo(const LbGemmParams& p) {
-    if (g_halo == 0 || g_force_tile || !lb_conv3x3_halo_eligible(p)) return false;
-    return g_halo == 2 || lb_conv3x3_halo_blocks(p) >= LB_HALO_MIN_BLOCKS;
+// How a conv is routed: the ONLY copy of the ladder.  lb_gemm_f16, the plan exports and lb_conv_plan are switches over its result.
+// `h` is the halo plan of the launch when the route is LB_ROUTE_HALO3 (planned only if the ladder gets that far; else zero).
+static int gemm_route(const LbGemmParams& p, LbHaloPlan& h) {
+    h = LbHaloPlan{};
+    if (p.flags & LB_GEMM_C64) return LB_ROUTE_C64;                    // opt-in: that kernel or a refusal, never another route
+    if (p.scatter == 2) return LB_ROUTE_UPCONV_HALO;                   // all four sub-pixel parities in one launch: only the halo kernel implements it
+    if (g_halo == 0 || g_force_tile) return LB_ROUTE_GEMM;
+    if (lb_conv3x3_narrow_eligible(p)) return LB_ROUTE_NARROW;         // N <= 16: conv_out of the VAE / UNet (conv3_narrow.hip)
+    h = lb_conv3x3_halo_plan(p);
+    return h.tw != 0 && (g_halo == 2 || h.items >= LB_HALO_MIN_BLOCKS) ? LB_ROUTE_HALO3 : LB_ROUTE_GEMM;
 }
 
 // ping-pong 256x256 main loop (gemm_pp.hip): tile code 9
@@ -545,67 +550,90 @@ static void gemm_plan(const LbGemmParams& p, int& tile_out, int& splitk_out, lon
     nblk_out = nblk;
 }
 
-extern "C" int lb_gemm_plan(const LbGemmParams* pp, int* tile, int* splitk, long* blocks) {
-    LB_REQUIRE(pp != nullptr && pp->M > 0 && pp->N > 0 && pp->K > 0, "lb_gemm_plan: empty problem");
-    int t = 0, sk = 1;
-    long nb = 0;
-    if (pp->flags & LB_GEMM_C64) {                  // tile code 12 = 64-channel conv with resident weights; blocks = its persistent grid
-        if (const int rc = lb_conv3_c64_check(*pp)) return rc;
-        long items = 0;
-        t = 12;
-        lb_conv3_c64_grid(*pp, items, nb);
+// The GEMM route of a problem flagged LB_GEMM_HALO_KSPLIT is planned - and launched - without the flag and without `partial`: that is the
+// K-split workspace of the halo kernel, no split-K slabs.  The only place that strips them.
+static void gemm_plan_routed(LbGemmParams& p, int& tile, int& splitk, long& nblk) {
+    if (p.flags & LB_GEMM_HALO_KSPLIT) {
+        p.flags &= ~LB_GEMM_HALO_KSPLIT;
+        p.partial = nullptr;
     }
-    else if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(*pp)) { t = 8; nb = (long)pp->M / 256; }   // tile code 8 = narrow-N conv kernel
-    else if (use_halo(*pp)) { t = 6; nb = lb_conv3x3_halo_blocks(*pp); }     // tile code 6 = halo-tile conv kernel
-    else if (pp->flags & LB_GEMM_HALO_KSPLIT) {     // as lb_gemm_f16: not a halo launch, so `partial` is no split-K workspace
-        LbGemmParams q = *pp;
-        q.flags &= ~LB_GEMM_HALO_KSPLIT;
-        q.partial = nullptr;
-        gemm_plan(q, t, sk, nb);
-    }
-    else gemm_plan(*pp, t, sk, nb);
-    if (tile) *tile = t;
-    if (splitk) *splitk = sk;
-    if (blocks) *blocks = nb;
-    return 0;
+    gemm_plan(p, tile, splitk, nblk);
 }
 
-// Rows per sample of the LB_GEMM_CH_STATS buffer for the launch lb_gemm_f16 would make (same routing as below); 0 = no statistics.
+// The record of one problem (LbConvPlan, include/lb_hip.h): its route and what every plan export answers for it - they all read this.
+// Returns lb_gemm_plan's refusal, if any (tile / splitk / blocks are then zero).  Pure host arithmetic.
 long lb_conv_halo_stat_rows_total(const LbGemmParams& p);
-extern "C" int lb_gemm_ch_stat_rows(const LbGemmParams* pp) {
-    if (pp == nullptr || !pp->conv || pp->M <= 0 || pp->Hout <= 0 || pp->Wout <= 0) return 0;
-    if (pp->flags & LB_GEMM_C64) return 0;          // (not a halo-tile launch: no statistics)
-    const LbGemmParams& p = *pp;
-    bool halo;
-    if (p.scatter == 2) halo = lb_upconv_halo_eligible(p) != 0;
-    else halo = !(g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p)) && use_halo(p);
-    if (!halo) return 0;
-    const long samples = (long)p.M / ((long)p.Hout * p.Wout);
-    return samples > 0 ? (int)(lb_conv_halo_stat_rows_total(p) / samples) : 0;
-}
-
-// LB_GEMM_GN_A: what the emitter asks before it folds a GroupNorm (+ SiLU) into the 3x3 conv `pp` describes (include/lb_hip_gn_a.h) -
-// the routing of lb_gemm_f16 below, then the kernel's own conditions and the measured policy (conv3_halo.hip).  The narrow-N kernel
-// is a streaming kernel that saves a read and a write of its whole input for a map it runs once: +239 us (29.9 %) at B = 17 and
-// +32 us (28.2 %) at B = 2 for the VAE's conv_out (profiles/halo_gn_ab.txt), so it is in wherever the mode allows.
-int lb_conv3x3_halo_gn_a_able(const LbGemmParams& p);
-int lb_conv3x3_halo_gn_a_policy(const LbGemmParams& p);
 int lb_conv_halo_gn_a_mode();
-extern "C" void lb_conv_halo_gn_a_plan(const LbGemmParams* pp, int* fuse, int* kind) {
-    int f = 0, k = 0;
-    if (pp != nullptr && pp->conv && pp->M > 0 && pp->N > 0 && pp->Hin > 0 && pp->Win > 0 && pp->scatter == 0 &&
-        !(pp->flags & (LB_GEMM_C64 | LB_GEMM_GN_A))) {
-        const LbGemmParams& p = *pp;
-        if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p)) {
-            k = 8;
-            f = lb_conv_halo_gn_a_mode() != 0;
-        } else if (use_halo(p) && lb_conv3x3_halo_gn_a_able(p)) {
-            k = 3;
-            f = lb_conv3x3_halo_gn_a_policy(p);
+extern "C" void lb_conv_halo_plan(const LbGemmParams* pp, int* kind, int* tile_w, long* items, long* grid);
+static int conv_plan(const LbGemmParams& p, LbConvPlan& o) {
+    o = LbConvPlan{};
+    LbHaloPlan h;
+    int rc = 0;
+    switch (o.route = gemm_route(p, h)) {       // tile codes 12 / 8 / 6 name the kernels outside this file, blocks = their grids' work
+        case LB_ROUTE_C64:
+            if ((rc = lb_conv3_c64_check(p)) == 0) {
+                long items = 0;
+                o.tile = 12, o.splitk = 1;
+                lb_conv3_c64_grid(p, items, o.blocks);          // blocks = its persistent grid
+            }
+            break;
+        case LB_ROUTE_NARROW: o.tile = 8, o.splitk = 1, o.blocks = (long)p.M / 256; break;
+        case LB_ROUTE_HALO3: o.tile = 6, o.splitk = 1, o.blocks = h.items; break;
+        default: {      // (scatter = 2 too: lb_gemm_plan has always answered it with the tile it would get as an implicit GEMM, and tools
+            LbGemmParams q = p;                                 //  compare that answer across versions; `route` is the truthful field)
+            gemm_plan_routed(q, o.tile, o.splitk, o.blocks);
         }
     }
-    if (fuse) *fuse = f;
-    if (kind) *kind = k;
+    if (!p.conv || p.M <= 0 || p.Hin <= 0 || p.Win <= 0 || p.Hout <= 0 || p.Wout <= 0) return rc;
+    lb_conv_halo_plan(&p, &o.halo_kind, &o.halo_tile_w, &o.halo_items, &o.halo_grid);
+    // LB_GEMM_CH_STATS: rows per sample of the statistics buffer of a halo-tile launch (0: any other route)
+    long rows = 0;
+    if (o.route == LB_ROUTE_HALO3) rows = h.items / ((p.N + 127) / 128) * 4;
+    else if (o.route == LB_ROUTE_UPCONV_HALO && o.halo_kind == 2) rows = lb_conv_halo_stat_rows_total(p);
+    const long samples = (long)p.M / ((long)p.Hout * p.Wout);
+    o.stat_rows = samples > 0 ? (int)(rows / samples) : 0;
+    // LB_GEMM_HALO_KSPLIT: the answer does not depend on the route (lb_conv3x3_halo_f16 takes what the router keeps on the implicit GEMM)
+    const LbHaloPlan k = o.route == LB_ROUTE_HALO3 ? h : (o.halo_kind == 3 ? lb_conv3x3_halo_plan(p) : LbHaloPlan{});
+    o.ksplit_split = k.ks_split, o.ksplit_units = k.ks_units, o.ksplit_grid = k.ks_grid;
+    o.ksplit_counter_bytes = k.ks_counter_bytes, o.ksplit_slab_bytes = k.ks_slab_bytes;
+    // LB_GEMM_GN_A (include/lb_hip_gn_a.h): the route, then the kernel's own conditions and the measured policy (conv3_halo.hip).  The
+    // narrow-N kernel is a streaming kernel that saves a read and a write of its whole input for a map it runs once: +239 us (29.9 %) at
+    // B = 17 and +32 us (28.2 %) at B = 2 for the VAE's conv_out (profiles/halo_gn_ab.txt), so it is in wherever the mode allows.
+    if (p.N > 0 && p.scatter == 0 && !(p.flags & (LB_GEMM_C64 | LB_GEMM_GN_A))) {
+        if (o.route == LB_ROUTE_NARROW) o.gn_a_kind = 8, o.gn_a_fuse = lb_conv_halo_gn_a_mode() != 0;
+        else if (o.route == LB_ROUTE_HALO3 && h.gn_a_able) o.gn_a_kind = 3, o.gn_a_fuse = h.gn_a_policy;
+    }
+    if (o.halo_kind == 0 && !(p.flags & LB_GEMM_HALO_RAGGED)) {        // what the ragged-tile form would make of it
+        LbGemmParams q = p;
+        q.flags |= LB_GEMM_HALO_RAGGED;
+        lb_conv_halo_plan(&q, &o.ragged_kind, &o.ragged_tile_w, nullptr, nullptr);
+    }
+    return rc;
+}
+extern "C" int lb_conv_plan(const LbGemmParams* pp, LbConvPlan* out) {
+    LB_REQUIRE(pp != nullptr && out != nullptr && pp->M > 0 && pp->N > 0 && pp->K > 0, "lb_conv_plan: empty problem");
+    return conv_plan(*pp, *out);
+}
+
+extern "C" int lb_gemm_plan(const LbGemmParams* pp, int* tile, int* splitk, long* blocks) {
+    LB_REQUIRE(pp != nullptr && pp->M > 0 && pp->N > 0 && pp->K > 0, "lb_gemm_plan: empty problem");
+    LbConvPlan c;
+    if (const int rc = conv_plan(*pp, c)) return rc;
+    if (tile) *tile = c.tile;
+    if (splitk) *splitk = c.splitk;
+    if (blocks) *blocks = c.blocks;
+    return 0;
+}
+extern "C" int lb_gemm_ch_stat_rows(const LbGemmParams* pp) {
+    LbConvPlan c = {};
+    if (pp != nullptr && pp->conv && pp->M > 0 && pp->Hout > 0 && pp->Wout > 0) conv_plan(*pp, c);
+    return c.stat_rows;
+}
+extern "C" void lb_conv_halo_gn_a_plan(const LbGemmParams* pp, int* fuse, int* kind) {
+    LbConvPlan c = {};
+    if (pp != nullptr && pp->conv && pp->M > 0 && pp->N > 0 && pp->Hin > 0 && pp->Win > 0) conv_plan(*pp, c);
+    if (fuse) *fuse = c.gn_a_fuse;
+    if (kind) *kind = c.gn_a_kind;
 }
 
 extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
@@ -633,35 +661,35 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     }
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
-    if (p.flags & LB_GEMM_C64) {                    // opt-in: this kernel or a refusal, never another route
-        LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "lb_gemm_f16: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only");
-        if (const int rc = lb_conv3_c64_check(p)) return rc;
-        LB_DISPATCH("conv3x3_c64", lb_conv3_c64_launch(p, s));
-    }
-    if (p.scatter == 2) {       // all four sub-pixel parities in one launch: only the halo kernel implements it
-        LB_REQUIRE(lb_upconv_halo_eligible(p) != 0, "lb_gemm_f16: scatter = 2 needs Cin % 64 == 0, W % 16 == 0, stacked [4][N][K] weights");
-        if (const int rc = lb_upconv_halo_check(p)) return rc;
-        LB_DISPATCH("lb_upconv2x_halo_f16", lb_upconv_halo_launch(p, s));
-    }
-    if (g_halo != 0 && !g_force_tile && lb_conv3x3_narrow_eligible(p)) {    // N <= 16: conv_out of the VAE / UNet (conv3_narrow.hip)
-        if (const int rc = lb_conv3x3_narrow_check(p)) return rc;
-        LB_DISPATCH("lb_conv3x3_narrow_f16", lb_conv3x3_narrow_launch(p, s));
-    }
-    if (use_halo(p)) {
-        if (const int rc = lb_conv3x3_halo_check(p)) return rc;
-        LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
+    LbHaloPlan h;
+    switch (gemm_route(p, h)) {
+        case LB_ROUTE_C64: {
+            LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "lb_gemm_f16: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only");
+            if (const int rc = lb_conv3_c64_check(p)) return rc;
+            LB_DISPATCH("conv3x3_c64", lb_conv3_c64_launch(p, s));
+        }
+        case LB_ROUTE_UPCONV_HALO: {
+            LB_REQUIRE(lb_upconv_halo_eligible(p) != 0, "lb_gemm_f16: scatter = 2 needs Cin % 64 == 0, W % 16 == 0, stacked [4][N][K] weights");
+            if (const int rc = lb_upconv_halo_check(p)) return rc;
+            LB_DISPATCH("lb_upconv2x_halo_f16", lb_upconv_halo_launch(p, s));
+        }
+        case LB_ROUTE_NARROW: {
+            if (const int rc = lb_conv3x3_narrow_check(p)) return rc;
+            LB_DISPATCH("lb_conv3x3_narrow_f16", lb_conv3x3_narrow_launch(p, s));
+        }
+        case LB_ROUTE_HALO3: {
+            if (const int rc = lb_conv3x3_halo_check(p)) return rc;
+            LB_DISPATCH("lb_conv3x3_halo_f16", lb_conv3x3_halo_launch(p, s));
+        }
+        default: break;
     }
     LB_REQUIRE(!(p.flags & LB_GEMM_GN_A), "lb_gemm_f16: LB_GEMM_GN_A is implemented by the whole-tile 3x3 halo conv and the narrow-N conv only "
                                           "(ask lb_conv_halo_gn_a_plan before flagging a conv)");
-    if (p.flags & LB_GEMM_HALO_KSPLIT) {           // not a halo launch: `partial` is the K-split workspace of that kernel, not split-K slabs
-        p.flags &= ~LB_GEMM_HALO_KSPLIT;
-        p.partial = nullptr;
-    }
     LB_REQUIRE(!(p.flags & LB_GEMM_CH_STATS), "lb_gemm_f16: LB_GEMM_CH_STATS is implemented by the halo-tile conv kernels only "
                                               "(check lb_gemm_plan == 6 / lb_conv_halo_plan before asking for it)");
     int tile = 0, splitk = 1;
     long nblk = 0;
-    gemm_plan(p, tile, splitk, nblk);
+    gemm_plan_routed(p, tile, splitk, nblk);
     p.splitk = splitk;
     const int depth = g_depth, variant = g_variant;
     int stages = g_stages;

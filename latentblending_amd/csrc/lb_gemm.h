@@ -552,3 +552,17 @@ __device__ __forceinline__ void lb_gemm_tile_epilogue(const LbGemmParams& p, con
                                                       int row0, int col0, int gcol0) {
     lb_gemm_tile_epilogue_rows<TM, TN, GEGLU>(p, acc, [row0](int i) { return row0 + i * 16; }, col0, gcol0);
 }
+
+// Host plan of one 3x3 halo-tile launch (conv3_halo.hip: lb_conv3x3_halo_plan), computed once per call and read by the check, the
+// launch, the router (gemm.hip) and every plan export.  tw == 0: not a problem of that kernel, nothing else is set.
+struct LbHaloPlan {
+    int tw;                     // tile width, 32 or 16 (tile height = 256 / tw)
+    bool ragged;                // the image does not divide into tiles: the ragged instantiation (LB_GEMM_HALO_RAGGED)
+    long items, grid;           // (pixel tile, channel block) work items and the unsplit grid that walks them
+    long ks_units, ks_grid;     // LB_GEMM_HALO_KSPLIT: (channel block, tile, 64-channel chunk) units and the grid of the K-split form
+    int ks_split;               //   1 = a launch with these parameters takes that form
+    long ks_counter_bytes, ks_slab_bytes;   //   its workspace: the counters, then the slabs (both 0 unless ks_split)
+    bool gn_a_able;             // the launch could carry LB_GEMM_GN_A: whole tiles, unsplit
+    bool gn_a_policy;           // ... and the measured policy (lb_conv_halo_set_gn_a) says that fusing pays
+};
+LbHaloPlan lb_conv3x3_halo_plan(const LbGemmParams& p);

@@ -37,6 +37,20 @@ class LbGemmParams(C.Structure):
     ]
 
 
+class LbConvPlan(C.Structure):
+    """What lb_conv_plan answers for one conv (include/lb_hip.h); ``route`` is one of ROUTE_*."""
+    _fields_ = [
+        ("route", C.c_int), ("tile", C.c_int), ("splitk", C.c_int), ("blocks", C.c_long),
+        ("halo_kind", C.c_int), ("halo_tile_w", C.c_int), ("halo_items", C.c_long), ("halo_grid", C.c_long),
+        ("stat_rows", C.c_int), ("ksplit_split", C.c_int),
+        ("ksplit_units", C.c_long), ("ksplit_grid", C.c_long), ("ksplit_counter_bytes", C.c_long), ("ksplit_slab_bytes", C.c_long),
+        ("gn_a_fuse", C.c_int), ("gn_a_kind", C.c_int), ("ragged_kind", C.c_int), ("ragged_tile_w", C.c_int),
+    ]
+
+
+ROUTE_GEMM, ROUTE_C64, ROUTE_UPCONV_HALO, ROUTE_NARROW, ROUTE_HALO3 = range(5)
+
+
 class LbAttnParams(C.Structure):
     _fields_ = [
         ("Q", C.c_void_p), ("K", C.c_void_p), ("V", C.c_void_p), ("O", C.c_void_p),
@@ -89,6 +103,7 @@ SIGNATURES = {
     "lb_gemm_ch_stat_rows": (_i, [C.POINTER(LbGemmParams)]),
     "lb_conv_halo_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "lb_gemm_plan": (_i, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    "lb_conv_plan": (_i, [C.POINTER(LbGemmParams), C.POINTER(LbConvPlan)]),
     "lb_groupnorm_workspace_bytes": (_l, [_i, _i]),
     "lb_groupnorm_set_l3_chunk": (None, [_l]),
     "lb_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
@@ -219,3 +234,22 @@ if os.environ.get("LB_GEMM_LEAN_EPILOGUE"):     # A/B studies (tools/): 0 = the 
     api.lb_gemm_set_lean_epilogue(int(os.environ["LB_GEMM_LEAN_EPILOGUE"]))
 if os.environ.get("LB_GEMM_PP_AUTO"):           # A/B studies (tools/): 0 = the tile policy never picks the ping-pong GEMM
     api.lb_gemm_set_pp_auto(int(os.environ["LB_GEMM_PP_AUTO"]))
+
+
+def conv_plan(p: LbGemmParams) -> LbConvPlan:
+    """lb_conv_plan's record for ``p``: the route lb_gemm_f16 takes and every plan answer for it, in one call."""
+    plan = LbConvPlan()
+    api.lb_conv_plan(C.byref(p), C.byref(plan))
+    return plan
+
+
+def conv_probe(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, flags: int = 0, zero_page: int = 64) -> LbGemmParams:
+    """The parameter block of a 3x3 / stride 1 / pad 1 conv (``ks`` = 3) or a one-launch sub-pixel upsampler conv (``ks`` = 2) of
+    this geometry, for the plan calls: host arithmetic only reads whether ``zero_page`` is set."""
+    p = LbGemmParams()
+    p.flags = flags
+    p.conv, p.M, p.N, p.K = 1, B * H * W, cout, ks * ks * cin
+    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = H, W, H, W, cin, ks, ks, 1, cin
+    p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
+    p.zero_page = zero_page
+    return p

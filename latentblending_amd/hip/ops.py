@@ -350,12 +350,7 @@ def _groupnorm_workspace(wrapper: str, workspace: Optional[torch.Tensor], B: int
 def conv_halo_plan(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, flags: int = 0):
     """(kind, tile width, work items, grid) of the halo-tile kernel for this conv geometry (kind 0: not eligible).
     ``flags``: ``lib.GEMM_HALO_RAGGED`` asks for the ragged-tile plan of a 3x3 conv."""
-    p = LbGemmParams()
-    p.flags = flags
-    p.conv, p.M, p.N, p.K = 1, B * H * W, cout, ks * ks * cin
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = H, W, H, W, cin, ks, ks, 1, cin
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
-    p.zero_page = 64
+    p = lib.conv_probe(B, H, W, cin, cout, ks, flags)
     kind, tw, items, grid = C.c_int(), C.c_int(), C.c_long(), C.c_long()
     api.lb_conv_halo_plan(C.byref(p), C.byref(kind), C.byref(tw), C.byref(items), C.byref(grid))
     return kind.value, tw.value, items.value, grid.value
@@ -365,12 +360,7 @@ def conv_ch_stat_rows(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, 
     """Row blocks per sample of the LB_GEMM_CH_STATS buffer a 3x3 conv (ks = 3) / one-launch sub-pixel upsampler conv (ks = 2) of
     this geometry writes when ``gemm`` launches it (lb_gemm_ch_stat_rows: the library's own routing and tile constants); 0 = it
     does not run on a halo-tile kernel.  ``flags``: ``lib.GEMM_HALO_RAGGED`` for the ragged-tile launch."""
-    p = LbGemmParams()
-    p.flags = flags
-    p.conv, p.M, p.N, p.K = 1, B * H * W, cout, ks * ks * cin
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = H, W, H, W, cin, ks, ks, 1, cin
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
-    p.zero_page = 64
+    p = lib.conv_probe(B, H, W, cin, cout, ks, flags)
     return int(api.lb_gemm_ch_stat_rows(C.byref(p)))
 
 

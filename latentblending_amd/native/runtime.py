@@ -135,6 +135,11 @@ class GnOperand:
         self.x, self.args = x, args
         self.table: Optional[torch.Tensor] = None
         self.scratch: Optional[torch.Tensor] = None
+        self.conv: Optional[tuple] = None       # geometry of the conv the fold was planned for (``table`` set)
+
+
+def _conv_key(p: LbGemmParams) -> tuple:
+    return (p.M, p.N, p.K, p.Hin, p.Win, p.Cin, p.ldx)
 
 
 class Emitter:
@@ -156,32 +161,36 @@ class Emitter:
         self.zero_page = torch.zeros(64, dtype=torch.uint8, device=self.device)
         # set by the builder of a NON-SQUARE program (and its pipe's ``ragged_halo`` switch): 3x3 convs whose level does not divide
         # into halo tiles ask for the ragged-tile form (LB_GEMM_HALO_RAGGED) where ``geometry.use_ragged_halo`` says so.  False
-        # (every square program): no plan call, no flag - the recorded ops are those of ever.
+        # (every square program): no flag - the recorded ops are those of ever.
         self.ragged_halo = False
         # 3x3 halo-tile convs whose tiles fill the last round of CUs badly run the K-split form (LB_GEMM_HALO_KSPLIT) where the
-        # library's own plan says so (lb_conv_halo_ksplit_plan); False: no plan call, no flag.  One workspace per emitter: a fixed
+        # library's own plan says so (the K-split part of lb_conv_plan's record); False: no flag.  One workspace per emitter: a fixed
         # counter area (zeroed once: every launch leaves its counters zero) in front of the slabs all launches share.
         self.halo_ksplit = True
         self.ws_ksplit: Optional[torch.Tensor] = None
         # a GroupNorm (+ SiLU) that reads its statistics from the producing conv and feeds one 3x3 conv is folded into that conv
-        # (LB_GEMM_GN_A: ``gemm(..., gn=...)``) where the library's own plan says so (lb_conv_halo_gn_a_plan); False: no plan call,
+        # (LB_GEMM_GN_A: ``gemm(..., gn=...)``) where the library's own plan says so (the GN_A part of lb_conv_plan's record); False:
         # the GroupNorm launch and its output buffer as ever
         self.gn_a = True
 
-    def _ragged_flag(self, p: LbGemmParams) -> int:
-        """LB_GEMM_HALO_RAGGED or 0 for the 3x3 / stride 1 conv ``p`` describes (the library's own plan, with and without the bit).
-        Convs of at most 16 output channels are left alone: the narrow-N kernel's domain, 128-column halo blocks would idle."""
-        if not self.ragged_halo or not p.conv or p.KH != 3 or p.KW != 3 or p.stride != 1 or p.scatter or p.ups or p.N <= 16:
-            return 0
-        kind, tw = C.c_int(), C.c_int()
-        flags = p.flags
-        p.flags = flags & ~lib.GEMM_HALO_RAGGED
-        api.lb_conv_halo_plan(C.byref(p), C.byref(kind), None, None, None)
-        plain = kind.value
-        p.flags = flags | lib.GEMM_HALO_RAGGED
-        api.lb_conv_halo_plan(C.byref(p), C.byref(kind), C.byref(tw), None, None)
-        p.flags = flags
-        return lib.GEMM_HALO_RAGGED if use_ragged_halo(True, plain, kind.value, p.Hin, p.Win, tw.value) else 0
+    def _conv_plan(self, p: LbGemmParams) -> lib.LbConvPlan:
+        """The one planning step of a conv: ONE lb_conv_plan call says where lb_gemm_f16 takes ``p`` and in which form.  Sets the
+        emitter's two opt-in bits on ``p`` - LB_GEMM_HALO_RAGGED where ``geometry.use_ragged_halo`` says so, LB_GEMM_HALO_KSPLIT (asked
+        as a hint: it never changes the route) where the conv goes to the halo-tile kernel and the library's plan splits it - and
+        returns the record of ``p`` as flagged.  Allocates nothing: probes (``halo_stat_rows``, ``gn_operand``) plan with it too.
+        Convs of at most 16 output channels are never flagged ragged: the narrow-N kernel's domain, 128-column halo blocks would idle."""
+        if self.halo_ksplit:
+            p.flags |= lib.GEMM_HALO_KSPLIT
+        plan = lib.conv_plan(p)
+        if self.ragged_halo and p.N > 16 and use_ragged_halo(True, plan.halo_kind, plan.ragged_kind, p.Hin, p.Win, plan.ragged_tile_w):
+            p.flags |= lib.GEMM_HALO_RAGGED
+            plan = lib.conv_plan(p)          # (non-square programs only: the record of the launch as it is now flagged)
+        splits = plan.route == lib.ROUTE_HALO3 and plan.ksplit_split
+        if self.halo_ksplit and not (splits and plan.ksplit_counter_bytes <= self._KSPLIT_COUNTER_BYTES):
+            p.flags &= ~lib.GEMM_HALO_KSPLIT
+            if splits:                       # (more than 262,144 tiles: past the counter area, launched - and planned - unflagged)
+                plan = lib.conv_plan(p)
+        return plan
 
     # -- workspaces -------------------------------------------------------------------------
     def _gemm_ws(self, M: int, N: int) -> Optional[torch.Tensor]:
@@ -199,49 +208,19 @@ class Emitter:
 
     _KSPLIT_COUNTER_BYTES = 1 << 20
 
-    def _halo_ksplit(self, p: LbGemmParams) -> bool:
-        """Flag the 3x3 conv ``p`` for the K-split form of the halo-tile kernel and point ``partial`` at its workspace if
-        lb_gemm_f16 routes it to that kernel (tile code 6) and the library's plan splits it.  The launch's counters end where the
-        shared slab area begins, so no launch's slabs ever overlap another launch's counters."""
-        if not self.halo_ksplit or not p.conv or p.KH != 3 or p.KW != 3 or p.stride != 1 or p.scatter or p.ups:
+    def _halo_ksplit(self, p: LbGemmParams, plan: lib.LbConvPlan) -> bool:
+        """Apply the K-split part of ``plan`` to the 3x3 conv ``p``: where ``_conv_plan`` left it flagged, point ``partial`` at the
+        workspace, sized by the library's own numbers.  The launch's counters end where the shared slab area begins, so no launch's
+        slabs ever overlap another launch's counters."""
+        if not (self.halo_ksplit and p.flags & lib.GEMM_HALO_KSPLIT and plan.ksplit_split):
             return False
-        tile, sk, nb = C.c_int(), C.c_int(), C.c_long()
-        api.lb_gemm_plan(C.byref(p), C.byref(tile), C.byref(sk), C.byref(nb))
-        if tile.value != 6:
-            return False
-        flags = p.flags
-        p.flags = flags | lib.GEMM_HALO_KSPLIT
-        units, grid, split = C.c_long(), C.c_long(), C.c_int()
-        api.lb_conv_halo_ksplit_plan(C.byref(p), C.byref(units), C.byref(grid), C.byref(split))
-        need = int(api.lb_conv_halo_ksplit_workspace_bytes(C.byref(p)))
-        if not split.value or need <= 0:
-            p.flags = flags
-            return False
-        counters = ((units.value // (p.Cin // 64)) * 4 + 255) // 256 * 256
-        slabs = need - counters
-        assert slabs > 0 and slabs % (256 * 128 * 4) == 0, (need, counters)
-        if counters > self._KSPLIT_COUNTER_BYTES:
-            p.flags = flags
-            return False
-        total = self._KSPLIT_COUNTER_BYTES + slabs
+        total = self._KSPLIT_COUNTER_BYTES + plan.ksplit_slab_bytes
         if self.ws_ksplit is None or self.ws_ksplit.numel() < total:
             if self.ws_ksplit is not None:      # (recorded ops keep pointing into the old buffer)
                 self._retired.append(self.ws_ksplit)
             self.ws_ksplit = torch.zeros(total, dtype=torch.uint8, device=self.device)
-        p.partial = self.ws_ksplit.data_ptr() + self._KSPLIT_COUNTER_BYTES - counters
+        p.partial = self.ws_ksplit.data_ptr() + self._KSPLIT_COUNTER_BYTES - plan.ksplit_counter_bytes
         return True
-
-    def _gn_a_fuse(self, p: LbGemmParams, x: torch.Tensor, gn: dict) -> bool:
-        """Fold the GroupNorm ``gn`` of ``x`` into the conv ``p`` (complete but for the flag)?  Only with producer statistics, an fp16
-        stream tensor whose channels are the conv's (no padding in between), and the library's plan (route, whole tiles, unsplit,
-        measured policy: lb_conv_halo_gn_a_plan / lb_conv_halo_set_gn_a)."""
-        if not self.gn_a or gn.get("ch_stats") is None or x.dtype != F16 or not p.conv:
-            return False
-        if p.Cin != int(gn["C_"]) or p.ldx != p.Cin or gn.get("ldx") not in (None, p.Cin):
-            return False
-        fuse, kind = C.c_int(), C.c_int()
-        api.lb_conv_halo_gn_a_plan(C.byref(p), C.byref(fuse), C.byref(kind))
-        return bool(fuse.value)
 
     def _gn_ws(self, B: int, groups: int) -> torch.Tensor:
         need = api.lb_groupnorm_workspace_bytes(B, groups) // 8
@@ -264,18 +243,21 @@ class Emitter:
         ``gn`` = what ``gn_operand`` returned for this very conv (A = the raw tensor): the conv consumes GroupNorm(A), either through
         the affine table (LB_GEMM_GN_A) or from the scratch buffer the GroupNorm launch filled; both go back to the arena here."""
         p = self._gemm_params(A, W, out, M=M, bias=bias, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch, flags=flags,
-                              alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec, conv=conv, splitk=splitk, ln=ln,
-                              ch_stats=ch_stats)
+                              alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec, conv=conv, ln=ln, ch_stats=ch_stats)
         N, K = W.shape
         n_out = N // 2 if flags & lib.GEMM_GEGLU else N
+        if splitk and not (flags & lib.GEMM_GEGLU) and ln is None:
+            p.partial = _p(self._gemm_ws(M, N))
         if gn is not None:
-            if gn.table is not None:
-                if not self._gn_a_fuse(p, gn.x, gn.args):
+            if gn.table is not None:            # (the fold was decided by gn_operand; a flagged conv is never split along K)
+                if gn.conv != _conv_key(p):
                     raise RuntimeError("Emitter.gemm: the conv is not the one gn_operand planned the GroupNorm fold for")
                 p.flags |= lib.GEMM_GN_A
                 p.gn_table, p.gn_silu = gn.table.data_ptr(), int(bool(gn.args["silu"]))
             else:
                 p.A = gn.scratch.data_ptr()
+        if conv is not None:
+            self._halo_ksplit(p, self._conv_plan(p))
         api.lb_gemm_f16(C.byref(p), _stream())
         if gn is not None:
             self.arena.release(gn.scratch)
@@ -289,13 +271,17 @@ class Emitter:
     def gn_operand(self, x: torch.Tensor, W: torch.Tensor, *, M: int, conv: dict, flags: int = 0, has_residual: bool = False,
                    **gn) -> "GnOperand":
         """Emit the GroupNorm side of "3x3 conv of GroupNorm(x)" NOW and return the operand for the conv's ``gemm(x, ..., gn=...)``.
-        ``gn`` = the keyword arguments of ``groupnorm`` plus gamma / beta.  Where the library's plan fuses (``_gn_a_fuse``: producer
-        statistics, fp16 stream, route, whole tiles, unsplit, measured policy) the emitted op is the table kernel
+        ``gn`` = the keyword arguments of ``groupnorm`` plus gamma / beta.  Where the library's plan fuses (the GN_A part of the conv's
+        record: route, whole tiles, unsplit, measured policy) the emitted op is the table kernel
         (lb_groupnorm_affine_from_stats) and the conv will carry LB_GEMM_GN_A and read the raw x: no normalised buffer, no
         lb_groupnorm_from_stats.  Everywhere else: the GroupNorm launch into a scratch buffer, exactly as ever."""
         op = GnOperand(x, dict(gn))
-        plan = self._gemm_params(x, W, x, M=M, residual=x if has_residual else None, flags=flags, conv=conv)     # (pointers: only their nullness counts)
-        if self._gn_a_fuse(plan, x, gn):
+        p = self._gemm_params(x, W, x, M=M, residual=x if has_residual else None, flags=flags, conv=conv)     # (pointers: only their nullness counts)
+        # only with producer statistics and an fp16 stream tensor whose channels are the conv's (no padding in between)
+        able = self.gn_a and gn.get("ch_stats") is not None and x.dtype == F16 and p.Cin == int(gn["C_"]) and p.ldx == p.Cin and \
+            gn.get("ldx") in (None, p.Cin)
+        if able and self._conv_plan(p).gn_a_fuse:
+            op.conv = _conv_key(p)
             B_, C_, st = int(gn["B"]), int(gn["C_"]), gn["ch_stats"]
             op.table = self.arena.alloc((B_, C_, 2), F32)
             api.lb_groupnorm_affine_from_stats(st[0].data_ptr(), gn["gamma"].data_ptr(), gn["beta"].data_ptr(), op.table.data_ptr(),
@@ -307,8 +293,8 @@ class Emitter:
         return op
 
     def _gemm_params(self, A, W, out, *, M, bias=None, residual=None, rowvec=None, rows_per_batch=0, flags=0, alpha=1.0, lda=None,
-                     ldc=None, ldr=None, ld_rowvec=None, conv=None, splitk=True, ln=None, ch_stats=None) -> LbGemmParams:
-        """The parameter block ``gemm`` launches (everything but a GroupNorm fold)."""
+                     ldc=None, ldr=None, ld_rowvec=None, conv=None, ln=None, ch_stats=None) -> LbGemmParams:
+        """The parameter block ``gemm`` launches, before anything is planned for it: no workspace, none of the emitter's opt-in bits."""
         p = LbGemmParams()
         N, K = W.shape
         p.A, p.W, p.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
@@ -338,46 +324,22 @@ class Emitter:
             assert conv is not None and ch_stats.dtype == F32
             p.flags |= lib.GEMM_CH_STATS
             p.ch_stats, p.ch_stats_rows = ch_stats.data_ptr(), ch_stats.shape[1]    # [N][B * rows][2]: checked by the launcher
-        if splitk and not (flags & lib.GEMM_GEGLU) and ln is None:
-            p.partial = _p(self._gemm_ws(M, N))
-        if self.ragged_halo:
-            p.flags |= self._ragged_flag(p)
-        if conv is not None:
-            self._halo_ksplit(p)
         return p
-
-    def plan(self, M: int, N: int, K: int, flags: int = 0) -> Tuple[int, int]:
-        """(tile, split-K) the library would choose for a plain GEMM emitted by ``gemm`` (lb_gemm_plan)."""
-        p = LbGemmParams()
-        p.M, p.N, p.K, p.flags = M, N, K, flags
-        p.zero_page = self.zero_page.data_ptr()
-        if not (flags & lib.GEMM_GEGLU):
-            p.partial = _p(self._gemm_ws(M, N))
-        t, sk, nb = C.c_int(), C.c_int(), C.c_long()
-        api.lb_gemm_plan(C.byref(p), C.byref(t), C.byref(sk), C.byref(nb))
-        return t.value, sk.value
 
     def halo_stat_rows(self, B: int, H: int, W: int, cin: int, cout: int, ks: int = 3) -> int:
         """Rows per sample of the LB_GEMM_CH_STATS buffer ([cout][B * rows] float2, channel-major) if a 3x3 conv (ks = 3) or a one-launch
         sub-pixel upsampler conv (ks = 2) of this geometry runs on the halo-tile kernel - whose epilogue can leave the
         GroupNorm statistics of what it stores - else 0 (the consumer then runs the two-pass GroupNorm)."""
-        p = LbGemmParams()
-        p.conv, p.M, p.N, p.K = 1, B * H * W, cout, ks * ks * cin
-        p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = H, W, H, W, cin, ks, ks, 1, cin
-        p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
-        p.zero_page = self.zero_page.data_ptr()
         if ks == 2 and not self.upconv_one_launch(B, H, W, cin, cout):
             return 0
-        if self.ragged_halo:                  # (the same decision ``gemm`` makes for the launch itself)
-            p.flags |= self._ragged_flag(p)
-        return int(api.lb_gemm_ch_stat_rows(C.byref(p)))      # the library's own routing + tile constants (0: not a halo launch)
+        p = lib.conv_probe(B, H, W, cin, cout, ks, zero_page=self.zero_page.data_ptr())
+        return self._conv_plan(p).stat_rows     # the library's own routing + tile constants, with the bits ``gemm`` will set (0: not a halo launch)
 
     @staticmethod
     def upconv_one_launch(B: int, H: int, W: int, cin: int, cout: int) -> bool:
-        """The halo kernel's sub-pixel form takes this upsampler conv in one launch (else: four implicit-GEMM launches)."""
-        shape_ok = cin % 64 == 0 and ((W % 32 == 0 and H % 8 == 0) or (W % 16 == 0 and H % 16 == 0))
-        blocks = B * (H * W // 256) * 4 * ((cout + 127) // 128)
-        return shape_ok and blocks >= 96
+        """The halo kernel's sub-pixel form takes this upsampler conv in one launch (else: four implicit-GEMM launches): the library
+        says whether it can, the emitter asks for a grid of at least 96 blocks."""
+        return lib.conv_plan(lib.conv_probe(B, H, W, cin, cout, 2)).halo_kind == 2 and B * (H * W // 256) * 4 * ((cout + 127) // 128) >= 96
 
     def groupnorm(self, x: torch.Tensor, out: torch.Tensor, gamma, beta, *, B: int, HW: int, C_: int,
                   eps: float, silu: bool, groups: int = 32, ldx: Optional[int] = None,

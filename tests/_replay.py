@@ -40,7 +40,7 @@ KNOBS = {
 NOT_LAUNCHERS = {
     "lb_version", "lb_last_error_string", "lb_device_info",
     # plans and size queries
-    "lb_gemm_plan", "lb_conv_halo_plan", "lb_groupnorm_plan", "lb_gemm_ch_stat_rows", "lb_gemm_workspace_bytes",
+    "lb_gemm_plan", "lb_conv_plan", "lb_conv_halo_plan", "lb_groupnorm_plan", "lb_gemm_ch_stat_rows", "lb_gemm_workspace_bytes",
     "lb_groupnorm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
     # setters
     "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue",

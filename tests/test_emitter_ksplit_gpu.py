@@ -1,4 +1,5 @@
-"""The emitter's path to the K-split form of the 3x3 halo-tile conv (Emitter._halo_ksplit, native/runtime.py): one workspace per
+"""The emitter's path to the K-split form of the 3x3 halo-tile conv (Emitter._halo_ksplit, native/runtime.py: where the K-split
+part of lb_conv_plan's record is applied): one workspace per
 emitter, shared by every flagged launch; each launch's counters end where the slabs begin; a grown workspace retires the old one,
 which recorded ops keep using; the counter area stays zero.  Small 3x3 convs through Emitter.gemm under lb_gemm_set_halo(2) and
 lb_conv_halo_set_ksplit(2, 0) - every eligible conv routed to the halo kernel and split, on min(CUs, units) blocks -, held to a
@@ -65,8 +66,8 @@ class Chain:
         self.seen = []                                   # per emit: (flagged, a copy of the params, the emitter's workspace then)
         inner = self.em._halo_ksplit
 
-        def spy(p):
-            flagged = inner(p)
+        def spy(p, plan):
+            flagged = inner(p, plan)
             self.seen.append((flagged, type(p).from_buffer_copy(p), self.em.ws_ksplit))
             return flagged
         self.em._halo_ksplit = spy

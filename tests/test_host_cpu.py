@@ -370,13 +370,15 @@ def test_c_abi_exports_every_declared_symbol():
         with tempfile.TemporaryDirectory() as td:
             src = os.path.join(td, "t.c")
             with open(src, "w") as fh:
-                fh.write('#include <stdio.h>\n#include <stddef.h>\n#include "lb_hip.h"\nint main(){printf("%zu %zu %zu %zu\\n",'
-                         'sizeof(LbGemmParams), offsetof(LbGemmParams, splitk), sizeof(LbAttnParams), offsetof(LbAttnParams, scale));return 0;}\n')
+                fh.write('#include <stdio.h>\n#include <stddef.h>\n#include "lb_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n",'
+                         'sizeof(LbGemmParams), offsetof(LbGemmParams, splitk), sizeof(LbAttnParams), offsetof(LbAttnParams, scale), '
+                         'sizeof(LbConvPlan), offsetof(LbConvPlan, ragged_kind));return 0;}\n')
             exe = os.path.join(td, "t")
             subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
             sizes = [int(x) for x in subprocess.check_output([exe]).split()]
         assert sizes == [ctypes.sizeof(lib.LbGemmParams), lib.LbGemmParams.splitk.offset,
-                         ctypes.sizeof(lib.LbAttnParams), lib.LbAttnParams.scale.offset]
+                         ctypes.sizeof(lib.LbAttnParams), lib.LbAttnParams.scale.offset,
+                         ctypes.sizeof(lib.LbConvPlan), lib.LbConvPlan.ragged_kind.offset]
 
 
 def test_product_path_has_no_cpu_fallback():
