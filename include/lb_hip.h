@@ -99,7 +99,7 @@ enum {
     LB_GEMM_OUT_F32 = 1,     /* C is float32 (VAE residual stream) */
     LB_GEMM_RES_F32 = 2,     /* residual is float32 */
     LB_GEMM_GEGLU = 4,       /* W = [h rows | gate rows], C[M, N/2] = h * gelu(gate) */
-    LB_GEMM_TRANS_OUT = 8,   /* store C^T: C[n*ldc + m] */
+    LB_GEMM_TRANS_OUT = 8,   /* store C^T: C[n*ldc + m]; fp16 only - lb_gemm_f16 refuses the pair with LB_GEMM_OUT_F32 */
     LB_GEMM_SILU = 16,       /* SiLU after bias/residual */
     LB_GEMM_RELU = 32,       /* ReLU after bias/residual */
     LB_GEMM_QUICK_GELU = 128,/* x * sigmoid(1.702 x) after bias (CLIP-L MLP) */

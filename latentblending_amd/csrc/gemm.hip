@@ -643,6 +643,9 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     LB_REQUIRE(p.K % 8 == 0 && p.ldw % 8 == 0, "lb_gemm_f16: K and ldw must be multiples of 8");
     LB_REQUIRE(p.N % 4 == 0 && (geglu ? p.N % 8 == 0 : true), "lb_gemm_f16: N must be a multiple of 4");
     LB_REQUIRE(p.ldc % 4 == 0 || (p.flags & LB_GEMM_TRANS_OUT), "lb_gemm_f16: ldc must be a multiple of 4");
+    // (every epilogue stores the transposed form as fp16 - lb_gemm_write4, lb_gemm_store4 - while a caller of the pair sizes an fp32 buffer)
+    LB_REQUIRE(!((p.flags & LB_GEMM_TRANS_OUT) && (p.flags & LB_GEMM_OUT_F32)),
+               "lb_gemm_f16: LB_GEMM_TRANS_OUT | LB_GEMM_OUT_F32 is not implemented: the transposed store is fp16 only");
     if (p.conv) {
         LB_REQUIRE(p.Cin % 8 == 0 && p.ldx % 8 == 0, "lb_gemm_f16: conv Cin/ldx must be multiples of 8");
         LB_REQUIRE(p.K == p.KH * p.KW * p.Cin, "lb_gemm_f16: conv K != KH*KW*Cin");

@@ -20,6 +20,8 @@ pytestmark = pytest.mark.gpu
 from oracle import sdxl_ref as R  # noqa: E402  (checker only)
 from _parity import (ACT_LIPSCHITZ, ERF_APPROX, U16, U32, absdot, accumulate_bound, activation_bound, attention_bound,  # noqa: E402,F401
                      check_elementwise, contraction_bound, epilogue_bound, f64, geglu_bound, norm_bound, rnd, store_bound, ulp_diff_f16)
+from _value_kinds import (_conv_operands, _dev, _gen, _nchw64, _subpixel_ref, banded, gemm_mode, outlier_columns, outliers,  # noqa: E402,F401
+                          subnormal, tame_outlier_weights)
 
 DEV = "cuda"
 F16, F32, F64 = torch.float16, torch.float32, torch.float64
@@ -36,21 +38,6 @@ def lib():
     return l
 
 
-class gemm_mode:
-    """Variant / forced tile / forced split-K for the launches inside, the defaults afterwards."""
-
-    def __init__(self, variant=-1, tile=0, splitk=0):
-        self.v, self.t, self.s = variant, tile, splitk
-
-    def __enter__(self):
-        lib().api.lb_gemm_set_variant(self.v, 0)
-        lib().api.lb_gemm_set_tuning(self.t, self.s)
-
-    def __exit__(self, *exc):
-        lib().api.lb_gemm_set_tuning(0, 0)
-        lib().api.lb_gemm_set_variant(-1, 0)
-
-
 class attn_force:
     def __init__(self, force):
         self.f = force
@@ -62,50 +49,7 @@ class attn_force:
         lib().api.lb_attn_set_tuning(0)
 
 
-# ------------------------------------------------------------------ seeded input generators
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def outlier_columns(n):
-    """The fixed 1 % of columns (channels) that carry outliers: 7, 107, 207, ..."""
-    return torch.arange(7, n, 100)
-
-
-def outliers(shape, seed, scale=1.0):
-    """N(0, 1) * scale with the outlier columns (last axis) multiplied by 64, as fp16."""
-    x = torch.randn(*shape, generator=_gen(seed)) * scale
-    x[..., outlier_columns(shape[-1])] *= 64.0
-    return x.to(F16)
-
-
-def tame_outlier_weights(w, axis=-1):
-    """The matching weight columns divided by 8 (keeps outputs in range)."""
-    w = w.clone().float()
-    w.index_copy_(axis % w.dim(), outlier_columns(w.shape[axis]), w.index_select(axis % w.dim(), outlier_columns(w.shape[axis])) / 8.0)
-    return w.to(F16)
-
-
-def banded(shape, lo_exp, hi_exp, seed, positive=False):
-    """sign * 2^u, u uniform in [lo_exp, hi_exp): every magnitude a normal fp16 that survives an exact rescale by 2^+-6 as long as
-    lo_exp >= -8 and hi_exp <= 9."""
-    g = _gen(seed)
-    u = torch.rand(*shape, generator=g, dtype=F64) * (hi_exp - lo_exp) + lo_exp
-    s = torch.ones(shape, dtype=F64) if positive else (torch.randint(0, 2, shape, generator=g).double() * 2 - 1)
-    x = (s * torch.exp2(u)).to(F16)
-    assert bool((x.float().abs() >= 2.0 ** -14).all()) and bool(torch.isfinite(x).all())
-    return x
-
-
-def subnormal(shape, seed):
-    """Every value a non-zero fp16 subnormal (bit patterns 1 .. 1023, random sign)."""
-    g = _gen(seed)
-    bits = torch.randint(1, 1024, shape, generator=g, dtype=torch.int32) | (torch.randint(0, 2, shape, generator=g, dtype=torch.int32) << 15)
-    x = torch.from_numpy(bits.numpy().astype(np.uint16).view(np.float16).copy())
-    assert bool((x != 0).all()) and bool((x.float().abs() < 2.0 ** -14).all())
-    return x
-
-
+# ------------------------------------------------------------------ seeded input generators (the shared ones: tests/_value_kinds.py)
 def offset(shape, ratio, std, seed, blocks, axis, dtype=F32):
     """std * N(0, 1) + (+-ratio) * std with the sign alternating over ``blocks`` equal blocks of ``axis`` (groups of channels for
     GroupNorm, rows for LayerNorm: odd blocks get -ratio)."""
@@ -135,10 +79,6 @@ def gemm_case(kind, shape):
     bias, res, rv = rnd(N, seed=509, dtype=F32), rnd(M, N, seed=510), rnd(4, N, seed=511)
     A64, W64 = A.double(), W.double()
     return dict(A=A, W=W, bias=bias, res=res, rv=rv, base=A64 @ W64.t(), ad=absdot(A64, W64))
-
-
-def _dev(*ts):
-    return [None if t is None else t.to(DEV) for t in ts]
 
 
 GEMM_RUNS = [(0, 0, S1), (1, 0, S1), (3, 0, S1), (11, 0, S1), (7, 0, S2), (9, 0, S2), (10, 0, S2), (3, 2, S1), (1, 2, S1), (3, 5, S2)]
@@ -227,41 +167,6 @@ def test_gemm_epilogues_elementwise(variant, epi, kind, results_log):
             ref = full * 2.0 ** -4 + bias.double() * 1024
             bound = contraction_bound(None, None, K, ref, alpha=2.0 ** -4, bias=bias * 1024, absdot64=ad * (256 * 64))
     check_elementwise(results_log, name, got, ref, bound)
-
-
-def _nchw64(x_nhwc):
-    return x_nhwc.double().permute(0, 3, 1, 2)
-
-
-def _conv_operands(kind, xshape, cout, seed, kh=3):
-    """x [B, H, W, Cin] fp16 NHWC, w [Cout, Cin, kh, kh] fp16, of one value kind."""
-    B, H, Wd, cin = xshape
-    wshape, wscale = (cout, cin, kh, kh), (cin * kh * kh) ** -0.5
-    if kind == "normal":
-        return rnd(*xshape, seed=seed), rnd(*wshape, seed=seed + 1, scale=wscale)
-    if kind == "outliers":
-        return outliers(xshape, seed + 2), tame_outlier_weights(rnd(*wshape, seed=seed + 3, scale=wscale), axis=1)
-    if kind == "sub_a":
-        return subnormal(xshape, seed + 4), banded(wshape, 8, 12, seed + 5)
-    if kind == "sub_w":
-        return banded(xshape, 8, 12, seed + 6), subnormal(wshape, seed + 7)
-    if kind == "banded":
-        return banded(xshape, -3, 1, seed + 8), banded(wshape, -4, 0, seed + 9)
-    raise KeyError(kind)
-
-
-def _subpixel_ref(x, k4, fn=lambda t: t):
-    """fp64 result of the one-launch 2x2 sub-pixel upsampler conv from the operands the kernel reads: x [B, H, W, Cin] and the four
-    stacked kernels k4 [4][Cout][2 * 2 * Cin] (parities (0,0), (0,1), (1,0), (1,1)): output pixel (2y + py, 2x + px) sees source
-    pixels (y + a - 1 + py, x + b - 1 + px), a, b in {0, 1}.  ``fn`` = abs for the |x| . |w| term of the bound."""
-    B, H, Wd, cin = x.shape
-    cout = k4.shape[1]
-    xp = F.pad(fn(_nchw64(x)), (1, 1, 1, 1))
-    out = torch.zeros(B, 2 * H, 2 * Wd, cout, dtype=F64)
-    for i, (py, px) in enumerate([(0, 0), (0, 1), (1, 0), (1, 1)]):
-        k = fn(k4[i].double()).reshape(cout, 2, 2, cin).permute(0, 3, 1, 2)
-        out[:, py::2, px::2] = F.conv2d(xp[:, :, py:py + H + 1, px:px + Wd + 1], k).permute(0, 2, 3, 1)
-    return out
 
 
 def _run_conv(op, x, w, bias, res, f32=False, alpha=1.0, relu=False):
