@@ -91,6 +91,12 @@ int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* o
  *   (ratio 0, c0 -1, c1 0) returns m0 bit for bit in both planes. */
 int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
                      int cfg, void* stream);
+/* Counter-based sampler noise (the `noise` operand of the ancestral / LCM steps above when a pipe runs with noise="counter"):
+ * Philox4x32-10 words turned into fp16 normals in float64, each value a pure function of its row's key and counter words and of
+ * its element index - so a seed gives the same noise whatever batch, order or rank serves the draw.  The step kernels are
+ * unchanged: they receive an ordinary noise tensor.  The prototype and its contract live in lb_hip_noise.h: this header lists
+ * what hip/lib.py binds in SIGNATURES (hip/lib.py: NOISE_SIGNATURES). */
+#include "lb_hip_noise.h"
 
 /* ---- dense contractions (every nn.Linear / nn.Conv2d of the UNet at
  *      diffusers_holder.py:336, of the VAE decoder at :135 and of LPIPS-Alex at

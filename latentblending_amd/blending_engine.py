@@ -21,6 +21,7 @@ What is different underneath:
 """
 from __future__ import annotations
 
+import contextlib
 import os
 import platform
 import time
@@ -110,6 +111,9 @@ class BlendingEngine:
         #                                     exactly 1.0, the Turbo defaults) overwrites completely - bit-identical frames, fewer
         #                                     UNet forwards than the reference performs; tree_latents entries of the
         #                                     skipped steps are None
+        self.noise = None                   # per-step sampler noise of a native pipe: None = as the pipe stands, "stream" / "counter" = set
+        #                                     ``pipe.noise`` to this when a transition (or precompute_keyframes) starts.  Under "counter"
+        #                                     a seed gives the same noise on every path (native/noise.py); "stream" is the pipe's default
         self.keyframe_chunk = 16            # precompute_keyframes / batched decodes: at most this many samples per UNet / VAE batch
         self.seed1 = 0
         self.seed2 = 0
@@ -336,10 +340,16 @@ class BlendingEngine:
             self.seed1, self.seed2 = fixed_seeds[0], fixed_seeds[1]
 
         steps = self.num_inference_steps
+        self._apply_noise_setting()
         use_frontier = self.frontier_width > 1 or self.farm is not None
         if (self.anchor_image1 is not None or self.anchor_image2 is not None) and self._farm_on():
+            # (under counter-based noise there is no stream to align, but that was never the only obstacle: see the message)
             raise NotImplementedError("image anchors are not available under a farm of more than one rank "
-                                      "(the ranks' noise streams would have to be aligned around the anchors' own runs)")
+                                      + ("(the ranks' noise streams would have to be aligned around the anchors' own runs)"
+                                         if self._counter_source() is None else
+                                         "(counter-based noise needs no alignment, but every rank would compute the image anchors' "
+                                         "trajectories for itself, before the farm's consistency check - which does not cover the "
+                                         "pictures or their strengths - and they are never exchanged as rank 0's ordinary anchors are)"))
         keep1 = recycle_img1 and len(self.tree_latents[0]) == steps
         keep2 = recycle_img2 and len(self.tree_latents[-1]) == steps
         # frames handed over by preset_anchors belong to the trajectories it installed: an anchor that is denoised again
@@ -453,7 +463,8 @@ class BlendingEngine:
         cond = self.get_mixed_conditioning(0)
         t0 = time.time()
         start = self.get_noise(self.seed1)
-        traj = self.run_diffusion(cond, latents_start=start, idx_start=0)
+        with self._noise_bound(self._anchor_noise_id(self.seed1)):
+            traj = self.run_diffusion(cond, latents_start=start, idx_start=0)
         self._sync()                                     # (native launches are asynchronous)
         self.dt_unet_step = (time.time() - t0) / self.num_inference_steps
         self.tree_latents[0] = traj
@@ -464,15 +475,16 @@ class BlendingEngine:
         self._say("starting compute_latents2")
         cond = self.get_mixed_conditioning(1)
         start = self.get_noise(self.seed2)
-        if self.branch1_crossfeed_power > 0.0:
-            coeffs = planner.anchor_crossfeed_coeffs(
-                self.num_inference_steps, self.branch1_crossfeed_power,
-                self.branch1_crossfeed_range, self.branch1_crossfeed_decay)
-            traj = self.run_diffusion(cond, latents_start=start, idx_start=0,
-                                      list_latents_mixing=self.tree_latents[0],
-                                      mixing_coeffs=coeffs)
-        else:
-            traj = self.run_diffusion(cond, start)
+        with self._noise_bound(self._anchor_noise_id(self.seed2)):
+            if self.branch1_crossfeed_power > 0.0:
+                coeffs = planner.anchor_crossfeed_coeffs(
+                    self.num_inference_steps, self.branch1_crossfeed_power,
+                    self.branch1_crossfeed_range, self.branch1_crossfeed_decay)
+                traj = self.run_diffusion(cond, latents_start=start, idx_start=0,
+                                          list_latents_mixing=self.tree_latents[0],
+                                          mixing_coeffs=coeffs)
+            else:
+                traj = self.run_diffusion(cond, start)
         self.tree_latents[-1] = traj
         return self.dh.latent2image(traj[-1]) if return_image else traj
 
@@ -517,13 +529,14 @@ class BlendingEngine:
         if t_start < steps:
             cond = self.get_mixed_conditioning(0 if which == 1 else 1)
             start = traj[t_start - 1] if t_start > 0 else noised(0)
-            if which == 2 and self.branch1_crossfeed_power > 0.0:
-                coeffs = planner.anchor_crossfeed_coeffs(steps, self.branch1_crossfeed_power, self.branch1_crossfeed_range,
-                                                         self.branch1_crossfeed_decay)
-                tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start, list_latents_mixing=self.tree_latents[0],
-                                          mixing_coeffs=coeffs)
-            else:
-                tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start)
+            with self._noise_bound(self._anchor_noise_id(seed)):
+                if which == 2 and self.branch1_crossfeed_power > 0.0:
+                    coeffs = planner.anchor_crossfeed_coeffs(steps, self.branch1_crossfeed_power, self.branch1_crossfeed_range,
+                                                             self.branch1_crossfeed_decay)
+                    tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start, list_latents_mixing=self.tree_latents[0],
+                                              mixing_coeffs=coeffs)
+                else:
+                    tail = self.run_diffusion(cond, latents_start=start, idx_start=t_start)
             traj += list(tail[t_start:])
         self.tree_latents[0 if which == 1 else -1] = traj
         return traj
@@ -538,7 +551,8 @@ class BlendingEngine:
         zeros = [0.0] * self.num_inference_steps
         first, last = self.dh.pipe.native_run_diffusion_batch(
             conds, starts, 0, [None, None], [zeros, zeros], num_inference_steps=self.num_inference_steps,
-            guidance_scales=[self.guidance_scale, self.guidance_scale])
+            guidance_scales=[self.guidance_scale, self.guidance_scale],
+            noise_ids=[self._anchor_noise_id(self.seed1), self._anchor_noise_id(self.seed2)])
         # (dt_unet_step keeps its benchmark_speed() value: a batched, asynchronous run is not a per-step timing)
         self.tree_latents[0], self.tree_latents[-1] = first, last
         return first, last
@@ -561,6 +575,7 @@ class BlendingEngine:
         assert len(embeddings) == len(seeds) and len(embeddings) >= 1
         steps, n = self.num_inference_steps, len(embeddings)
         self.dh.set_num_inference_steps(steps)
+        self._apply_noise_setting()
         pipe = self.dh.pipe
         farm = self.farm if self._farm_on() else None
         ancestral = self._draws_noise(getattr(pipe, "scheduler", None))      # (any sampler that draws per-step noise)
@@ -581,7 +596,8 @@ class BlendingEngine:
                         got = pipe.native_run_diffusion_batch(
                             [embeddings[k] for k in part], [self.get_noise(int(seeds[k])) for k in part], 0, [None] * len(part),
                             [zeros] * len(part), num_inference_steps=steps, guidance_scales=[self.guidance_scale] * len(part),
-                            noise_slots=(n, part) if farm else None)
+                            noise_slots=(n, part) if farm else None,
+                            noise_ids=[self._anchor_noise_id(seeds[k]) for k in part])
                         for k, t in zip(part, got):
                             trajs[k] = t
                 elif ancestral:          # fewer key frames than ranks: a rank without one still advances a shared noise stream
@@ -589,7 +605,8 @@ class BlendingEngine:
             else:
                 for k in range(n):                       # (generic pipes: one trajectory at a time, in chain order)
                     if k in mine:
-                        trajs[k] = self.run_diffusion([embeddings[k]], latents_start=self.get_noise(int(seeds[k])), idx_start=0)
+                        with self._noise_bound(self._anchor_noise_id(seeds[k])):
+                            trajs[k] = self.run_diffusion([embeddings[k]], latents_start=self.get_noise(int(seeds[k])), idx_start=0)
                     elif ancestral:
                         self._skip_noise_draws(self._run_noise_draws(0))
             if farm:
@@ -640,9 +657,10 @@ class BlendingEngine:
         coeffs = planner.parental_crossfeed_coeffs(
             self.num_inference_steps, idx_injection, self.parental_crossfeed_power,
             self.parental_crossfeed_range, self.parental_crossfeed_decay)
-        return self.run_diffusion(cond, latents_start=mixed[idx_injection - 1],
-                                  idx_start=idx_injection, list_latents_mixing=mixed,
-                                  mixing_coeffs=coeffs)
+        with self._noise_bound(self._mid_noise_id(fract_mixing, idx_injection)):
+            return self.run_diffusion(cond, latents_start=mixed[idx_injection - 1],
+                                      idx_start=idx_injection, list_latents_mixing=mixed,
+                                      mixing_coeffs=coeffs)
 
     def get_mixing_parameters(self, idx_injection):
         """(fract, parent1, parent2) of the next branch: midpoint of the least-similar gap."""
@@ -718,7 +736,9 @@ class BlendingEngine:
             (lambda: [self.get_mixed_conditioning(gaps[k][2])[0] for k in mine]), [gaps[k][2] for k in mine],     # (built behind the first launch)
             [coeffs] * len(mine), idx_injection, steps, self.guidance_scale, [guid[k] for k in mine],
             noise_slots=(len(gaps), mine) if farm else None, elide_dead_steps=self.elide_dead_steps and not farm,
-            known_anchors=(self.tree_latents[0] if keep1 else None, self.tree_latents[-1] if keep2 else None))
+            known_anchors=(self.tree_latents[0] if keep1 else None, self.tree_latents[-1] if keep2 else None),
+            noise_ids=([self._anchor_noise_id(self.seed1), self._anchor_noise_id(self.seed2)],
+                       [self._mid_noise_id(gaps[k][2], idx_injection) for k in mine]))
         self.tree_latents[0], self.tree_latents[-1] = first, last       # (what compute_latents1 / 2 leave behind)
         given = self._anchor_frames_given
         if given[0] is not None and given[1] is not None and not farm:
@@ -948,7 +968,8 @@ class BlendingEngine:
                 idx_injection, [s["mixed"] for s in sel], [s["coeffs"] for s in sel],
                 num_inference_steps=self.num_inference_steps,
                 guidance_scales=[s["guidance"] for s in sel],
-                noise_slots=None if only is None else (len(specs), chosen))
+                noise_slots=None if only is None else (len(specs), chosen),
+                noise_ids=[self._mid_noise_id(s["fract"], idx_injection) for s in sel])
             frames = pipe.native_latent2image_batch([t[-1] for t in trajs], "pil")
             return list(zip(trajs, frames))
         out = []
@@ -957,8 +978,9 @@ class BlendingEngine:
                 self._skip_noise_draws(self._run_noise_draws(idx_injection))
                 continue
             self.guidance_scale = self.dh.guidance_scale = s["guidance"]
-            traj = self.run_diffusion([s["cond"]], latents_start=s["mixed"][idx_injection - 1], idx_start=idx_injection,
-                                      list_latents_mixing=s["mixed"], mixing_coeffs=s["coeffs"])
+            with self._noise_bound(self._mid_noise_id(s["fract"], idx_injection)):
+                traj = self.run_diffusion([s["cond"]], latents_start=s["mixed"][idx_injection - 1], idx_start=idx_injection,
+                                          list_latents_mixing=s["mixed"], mixing_coeffs=s["coeffs"])
             out.append((traj, self.dh.latent2image(traj[-1])))
         return out
 
@@ -1015,9 +1037,56 @@ class BlendingEngine:
         """Latent-shaped draws ONE denoising run from ``idx_start`` consumes (``planner.noise_draws_per_run``)."""
         return planner.noise_draws_per_run(getattr(self.dh.pipe, "scheduler", None), self.num_inference_steps, idx_start)
 
+    # counter-based sampler noise (native/noise.py): a draw is addressed by (trajectory id, step), so the engine only has to say
+    # WHICH trajectory a run denoises - ids for the native loops, a binding around a run of the generic loop
+    def _apply_noise_setting(self):
+        """``self.noise`` (a session's setting) onto the native pipe; None leaves the pipe as it stands."""
+        if self.noise is None:
+            return
+        pipe = self.dh.pipe
+        if not hasattr(type(pipe), "noise"):
+            raise ValueError("BlendingEngine.noise = ... needs the native pipe (NativeSDXLPipe); a generic pipe carries its own "
+                             "scheduler.noise_source")
+        if pipe.noise != self.noise:
+            pipe.noise = self.noise
+
+    def _counter_source(self):
+        """The scheduler's noise source if it is counter-based (``keyed`` + ``bind``: ``noise="counter"``), else None."""
+        src = getattr(getattr(self.dh.pipe, "scheduler", None), "noise_source", None)
+        return src if hasattr(src, "keyed") and hasattr(src, "bind") else None
+
+    def _anchor_noise_id(self, seed) -> Optional[int]:
+        """Trajectory id of the anchor / key frame of ``seed`` - whichever slot it fills; None under stream noise."""
+        if self._counter_source() is None:
+            return None
+        from .native.noise import anchor_id
+        return anchor_id(int(seed))
+
+    def _mid_noise_id(self, fract_mixing, idx_injection) -> Optional[int]:
+        """Trajectory id of the mid branch at ``fract_mixing`` injected at ``idx_injection``; None under stream noise."""
+        if self._counter_source() is None:
+            return None
+        from .native.noise import mid_id
+        return mid_id(int(self.seed1), int(self.seed2), float(fract_mixing), int(idx_injection))
+
+    @contextlib.contextmanager
+    def _noise_bound(self, tid):
+        """Runs of ``run_diffusion`` inside draw as trajectory ``tid`` (nothing to do under stream noise: ``tid`` is None)."""
+        src = self._counter_source()
+        if src is None or tid is None:
+            yield
+            return
+        before = src.bind(int(tid))
+        try:
+            yield
+        finally:
+            src.bind(before)
+
     def _skip_noise_draws(self, n):
         sched = getattr(self.dh.pipe, "scheduler", None)
         src = getattr(sched, "noise_source", None)
+        if self._counter_source() is not None:      # addressed draws: nothing to advance, whoever else draws
+            return
         if src is not None and self._draws_noise(sched) and n > 0:
             shape = (1, self.dh.pipe.unet.config.in_channels, self.dh.height_latent, self.dh.width_latent)
             if hasattr(src, "many"):        # the ranks that DO draw make one generator call for these n latents (native pipe,

@@ -161,9 +161,10 @@ class BlendingVariableHolder:
 
     # ---- gradio_ui.py:222-262: the chain over the edited list, one part per segment, concatenated ----
     def generate_movie(self, t_per_segment=10, fps: int = 30, movie_encoder: Optional[str] = None, movie_size=None,
-                       movie_resample: Optional[str] = None):
+                       movie_resample: Optional[str] = None, noise: Optional[str] = None):
         """``movie_encoder``: "host" / "device" for the parts' ``write_movie_transition``; ``movie_size`` / ``movie_resample``: its
-        ``size_output=(W, H)`` / ``resample=`` (None: the session's settings)."""
+        ``size_output=(W, H)`` / ``resample=`` (None: the session's settings); ``noise``: "stream" / "counter" = the native pipe's
+        sampler noise for this movie (None: the session's ``noise``, else as the pipe stands)."""
         from .replay import run_multi_transition
         if len(self.data) < 2:
             raise ValueError("generate_movie: the movie needs at least two images (add_image_to_video)")
@@ -173,7 +174,7 @@ class BlendingVariableHolder:
             run_multi_transition(be, [it["prompt"] for it in self.data], [it["seed"] for it in self.data], self.fp_movie,
                                  duration_single_trans=t_per_segment,
                                  list_negative_prompts=[it["negative_prompt"] for it in self.data], fps=fps, dp_parts=self.dp_out,
-                                 movie_encoder=movie_encoder, movie_size=movie_size, movie_resample=movie_resample)
+                                 movie_encoder=movie_encoder, movie_size=movie_size, movie_resample=movie_resample, noise=noise)
         print(f"DONE! MOVIE SAVED IN {self.fp_movie}")
         return self.fp_movie
 

@@ -173,6 +173,12 @@ GN_A_SIGNATURES = {
     "lb_conv_halo_set_gn_a": (None, [_i, _i]),
 }
 
+# counter-based sampler noise (include/lb_hip_noise.h): a launcher, checked like every launcher; a program records it under its
+# own name.  A table of its own because SIGNATURES is mirrored one to one by the replay registry of the program tests
+NOISE_SIGNATURES = {
+    "lb_counter_noise_f16": (_i, [_vp, _vp, _l, _i, _i, _vp]),
+}
+
 _NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
              "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan","lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
              "lb_program_destroy", "lb_program_recording", "lb_program_num_ops", "lb_program_op_name"}
@@ -221,6 +227,11 @@ for _name, (_res, _args) in GN_A_SIGNATURES.items():
     _fn.restype = _res
     _fn.argtypes = _args
     setattr(api, _name, _wrap(_name, _fn) if _res is _i else _fn)
+for _name, (_res, _args) in NOISE_SIGNATURES.items():
+    _fn = getattr(_lib, _name)
+    _fn.restype = _res
+    _fn.argtypes = _args
+    setattr(api, _name, _wrap(_name, _fn))
 for _name, (_res, _args) in STUDY_SIGNATURES.items():
     _fn = getattr(_lib, _name, None)
     if _fn is not None:

@@ -200,6 +200,50 @@ def dpmpp2m_step(state, eps, params, cfg=False, out: Optional[torch.Tensor] = No
     return out
 
 
+def noise_rows(rows, device) -> torch.Tensor:
+    """Host rows of ``(key0, key1, ctr1, ctr2, ctr3)`` (32-bit words) -> int32 [n, 8] on ``device``, in ONE copy: the ``rows_dev``
+    operand of ``lb_counter_noise_f16``."""
+    import numpy as np
+    host = np.zeros((len(rows), 8), dtype=np.uint32)
+    if len(rows):
+        host[:, :5] = np.asarray([[int(v) & 0xFFFFFFFF for v in r] for r in rows], dtype=np.uint64).reshape(len(rows), 5)
+    return torch.from_numpy(host.view(np.int32)).to(device)
+
+
+def counter_noise(rows, shape, raw: bool = False, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """Counter-based noise (``lb_counter_noise_f16``): ``rows`` is a host sequence of n 5-tuples ``(key0, key1, ctr1, ctr2,
+    ctr3)``, uploaded in one copy - or an int32 [n, 8] device tensor ``noise_rows`` made, which a caller that records a program
+    owns and keeps alive (the op reads it at every replay).  ``shape`` = (n, ...): the result is fp16 of that shape, or with
+    ``raw`` int32 of that shape holding the Philox words.  ``out``: caller-owned, contiguous, 16-byte aligned."""
+    shape = tuple(int(s) for s in shape)
+    n = shape[0] if shape else 0
+    per_sample = 1
+    for s in shape[1:]:
+        per_sample *= s
+    dt = torch.int32 if raw else F16
+    if out is not None:
+        device = out.device
+        if out.dtype != dt or not out.is_contiguous() or out.numel() != n * per_sample:
+            raise ValueError(f"counter_noise: out must be a contiguous {dt} tensor of {n * per_sample} elements")
+    elif device is None:
+        device = rows.device if isinstance(rows, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    if isinstance(rows, torch.Tensor):
+        if rows.dtype != torch.int32 or not rows.is_contiguous() or tuple(rows.shape) != (n, 8) or rows.device != torch.device(device):
+            raise ValueError(f"counter_noise: device rows must be a contiguous int32 [{n}, 8] tensor on {device}")
+        rows_dev = rows
+    else:
+        if len(rows) != n:
+            raise ValueError(f"counter_noise: {len(rows)} rows for a result of shape {shape}")
+        if n > 0:
+            _own_buffer("counter_noise", "device `rows` (noise_rows)")
+        rows_dev = noise_rows(rows, device)
+    if out is None:
+        out = torch.empty(shape, dtype=dt, device=device)
+    api.lb_counter_noise_f16(rows_dev.data_ptr() if n > 0 else None, out.data_ptr() if out.numel() else None, per_sample, n,
+                             int(bool(raw)), stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------------------ GEMM / conv
 def pack_linear_weight(w: torch.Tensor) -> torch.Tensor:
     """[N, K] -> fp16 [N, K] contiguous (K padded to a multiple of 8 with zeros)."""

@@ -37,6 +37,7 @@ from .frames import DeviceImage
 from .geometry import program_key
 from .lpips import NativeLPIPS
 from ..planner import noise_draws_per_run
+from .noise import CounterNoise
 from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
@@ -44,6 +45,7 @@ from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
 from .weights import SyntheticProvider
 
 F16, F32 = torch.float16, torch.float32
+NOISE_MODES = ("stream", "counter")
 
 
 def _synthetic_embedding(text: str, shape, salt: int) -> torch.Tensor:
@@ -116,8 +118,12 @@ class StableDiffusionXLPipeline:
                  text_encoder_fn=None, unet_native: Optional[NativeUNet] = None,
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
                  scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
-                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None):
-        """``decoder``: "full" (default) = the SDXL ``AutoencoderKL`` decoder; "tiny" = the TAESDXL tiny decoder (``native/tiny_vae.py``:
+                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream"):
+        """``noise``: "stream" (default) = per-step sampler noise (Euler-ancestral, LCM) drawn from a generator, as ever - the value an
+        element receives depends on the draws before it; "counter" = counter-based noise (``native/noise.py``): every value is a
+        function of (trajectory, step, element), so a seed renders the same whatever batch, order or rank serves the draw.
+        ``pipe.noise`` switches it afterwards.  The START latents stay host-seeded under both.
+        ``decoder``: "full" (default) = the SDXL ``AutoencoderKL`` decoder; "tiny" = the TAESDXL tiny decoder (``native/tiny_vae.py``:
         a speed / preview option - a distilled approximation, its LPIPS tree is computed on its own frames).  Case-insensitive,
         anything else raises ``ValueError``; ``pipe.decoder`` switches it afterwards (preview tiny, render full).  The tiny network
         is built on first use from ``tiny_vae_native`` / ``tiny_vae_provider`` (``native.from_safetensors(<dir>/taesdxl)``), else
@@ -203,6 +209,8 @@ class StableDiffusionXLPipeline:
         self._feat_scratch: Dict[int, list] = {}
         self.stats = {"unet_forwards": 0, "unet_samples": 0, "vae_decodes": 0, "slerps": 0, "lpips_pairs": 0}
         self._side_stream = None            # lazily created: conditioning programs of big batches run here beside the small anchor steps
+        self._noise = "stream"
+        self.noise = noise
 
     def _synthetic_notice(self, what: str, how: str):
         if self.allow_synthetic or what in self._warned:
@@ -210,6 +218,31 @@ class StableDiffusionXLPipeline:
         self._warned.add(what)
         warnings.warn(f"NativeSDXLPipe: using seeded SYNTHETIC {what} ({how}; allow_synthetic=True silences this)",
                       UserWarning, stacklevel=3)
+
+    # ---- sampler noise ------------------------------------------------------------------
+    @property
+    def noise(self) -> str:
+        return self._noise
+
+    @noise.setter
+    def noise(self, value):
+        name = value.strip().lower() if isinstance(value, str) else value
+        if name not in NOISE_MODES:
+            raise ValueError(f"NativeSDXLPipe: noise must be one of {NOISE_MODES} (got {value!r})")
+        if name == "counter":
+            if not isinstance(self.scheduler.noise_source, CounterNoise):
+                self.scheduler.noise_source = CounterNoise(self.device, scheduler=self.scheduler)
+        elif isinstance(self.scheduler.noise_source, CounterNoise):
+            self.scheduler.noise_source = None          # (a source the user installed is not this switch's to remove)
+        self._noise = name
+
+    @staticmethod
+    def _keyed_noise(sched, noise_ids, pairs, shape1):
+        """The counter-based draws ``pairs`` = [(index into ``noise_ids``, step), ...] in ONE launch: [len(pairs), *shape1[1:]]."""
+        if noise_ids is None:
+            raise ValueError("the scheduler's noise source is counter-based (noise='counter'): the native loops need noise_ids= "
+                             "(one trajectory id per sample, native/noise.py)")
+        return sched.noise_source.keyed([(int(noise_ids[s]), i) for s, i in pairs], (len(pairs),) + tuple(shape1[1:]))
 
     # ---- diffusers duck type ------------------------------------------------------------
     guidance_scale = property(lambda s: s._guidance_scale)
@@ -506,21 +539,30 @@ class StableDiffusionXLPipeline:
         return [side, side, 0.0, 0.0, side, side]      # native size, not render size (reference quirk)
 
     def native_run_diffusion(self, text_embeddings, latents_start, idx_start, list_latents_mixing, coeffs,
-                             num_inference_steps, guidance_scale):
+                             num_inference_steps, guidance_scale, noise_id: Optional[int] = None):
+        """One branch.  ``noise_id``: its trajectory id under counter-based noise; None = the id bound on the source (the engine
+        binds it around the holder's run), else a free one - a caller that says nothing still gets noise, merely unaddressed."""
+        src = self.scheduler.noise_source
+        if noise_id is None and hasattr(src, "keyed"):
+            noise_id = src.bound_id() if hasattr(src, "bound_id") else None
         return self.native_run_diffusion_batch([text_embeddings], [latents_start], idx_start,
                                                [list_latents_mixing], [coeffs], num_inference_steps,
-                                               [guidance_scale])[0]
+                                               [guidance_scale], noise_ids=None if noise_id is None else [noise_id])[0]
 
     @torch.no_grad()
     def native_run_diffusion_batch(self, conds: Sequence[tuple], starts: Sequence[torch.Tensor], idx_start: int,
                                    mixings: Sequence[Optional[list]], coeffs_list: Sequence[Sequence[float]],
                                    num_inference_steps: int, guidance_scales: Sequence[float],
-                                   noise_slots: Optional[Tuple[int, Sequence[int]]] = None):
+                                   noise_slots: Optional[Tuple[int, Sequence[int]]] = None,
+                                   noise_ids: Optional[Sequence[int]] = None):
         """Denoise G branches in lock-step from ``idx_start``.  Returns per branch a list with one
         entry per step (``None`` below ``idx_start``, else the [1,4,L,L] latent after that step).
         ``noise_slots`` = (n_total, my_indices): these G branches are numbers ``my_indices`` of a round of
         ``n_total`` branches evaluated by several ranks; ancestral noise is then drawn for all ``n_total`` in
-        order and only this rank's share is used, so a shared noise stream stays aligned across ranks."""
+        order and only this rank's share is used, so a shared noise stream stays aligned across ranks.
+        ``noise_ids``: one trajectory id per branch (native/noise.py), read when the scheduler's noise source is counter-based
+        (it has ``keyed``): the rows of these G branches' own steps are built and served by one launch, and ``noise_slots`` is
+        ignored - there is no stream to keep aligned."""
         G = len(conds)
         sched = self.scheduler
         if sched.num_inference_steps != num_inference_steps:
@@ -535,7 +577,8 @@ class StableDiffusionXLPipeline:
                 idx = [g for g in range(G) if wants[g] == flag]
                 part = self.native_run_diffusion_batch([conds[g] for g in idx], [starts[g] for g in idx], idx_start,
                                                        [mixings[g] for g in idx], [coeffs_list[g] for g in idx],
-                                                       num_inference_steps, [guidance_scales[g] for g in idx])
+                                                       num_inference_steps, [guidance_scales[g] for g in idx],
+                                                       noise_ids=None if noise_ids is None else [noise_ids[g] for g in idx])
                 for g, traj in zip(idx, part):
                     out[g] = traj
             return out
@@ -558,9 +601,13 @@ class StableDiffusionXLPipeline:
         nm = noise_draws_per_run(sched, num_inference_steps, idx_start)     # (ancestral: every step; LCM: every step but the last)
         if nm > 0:
             shape1 = (1,) + tuple(latents.shape[1:])
-            n_draw, keep = self._noise_slots(noise_slots, G)
-            drawn = sched.draw_noise_many(n_draw * nm, shape1, self.device).view(n_draw, nm, *shape1[1:])
-            noise_all = drawn[keep].transpose(0, 1).contiguous()                             # [steps, G, 4, L, L]
+            if hasattr(sched.noise_source, "keyed"):      # counter-based: step-major rows of this call's own samples, one launch
+                noise_all = self._keyed_noise(sched, noise_ids, [(g, i) for i in range(idx_start, idx_start + nm) for g in range(G)],
+                                              shape1).view(nm, G, *shape1[1:])
+            else:
+                n_draw, keep = self._noise_slots(noise_slots, G)
+                drawn = sched.draw_noise_many(n_draw * nm, shape1, self.device).view(n_draw, nm, *shape1[1:])
+                noise_all = drawn[keep].transpose(0, 1).contiguous()                             # [steps, G, 4, L, L]
         hist = carry = None         # (a multistep sampler's previous x0 predictions / two-plane state; every run starts without)
         for i in range(idx_start, num_inference_steps):
             mix = []
@@ -591,7 +638,8 @@ class StableDiffusionXLPipeline:
                              mid_coeffs: Sequence[Sequence[float]], idx_injection: int, num_inference_steps: int,
                              guidance_anchor: float, guidance_mids: Sequence[float],
                              noise_slots: Optional[Tuple[int, Sequence[int]]] = None, elide_dead_steps: bool = False,
-                             known_anchors: Sequence[Optional[Sequence[torch.Tensor]]] = (None, None)):
+                             known_anchors: Sequence[Optional[Sequence[torch.Tensor]]] = (None, None),
+                             noise_ids: Optional[Tuple[Sequence[int], Sequence[int]]] = None):
         """Both anchors AND a set of mid branches whose parents are the anchors, in one wavefront.
 
         A mid branch at step i only needs the anchors' latents of step i-1 (its start latent and its
@@ -613,7 +661,10 @@ class StableDiffusionXLPipeline:
         Under a MULTISTEP sampler every sample carries its previous x0 prediction from step to step: when the batch grows at
         ``idx_injection`` the anchors keep theirs and the mids enter without (first-order rows - the order is a property of the
         row, so one launch serves the mixed batch).  A skipped step would leave no x0 prediction behind for the step after it, so
-        ``elide_dead_steps`` is ignored under such a sampler (with one warning per pipe)."""
+        ``elide_dead_steps`` is ignored under such a sampler (with one warning per pipe).
+        ``noise_ids`` = (the two anchors' trajectory ids, the mids' ids), read when the scheduler's noise source is counter-based:
+        the rows of the steps this call really runs (no anchor that is known, no mid step that is dead) are served by one launch;
+        ``noise_slots`` is then ignored."""
         known = [None if t is None else list(t) for t in known_anchors]
         live = [k for k in (0, 1) if known[k] is None]          # anchors denoised here
         # ``mid_conds`` may be a CALLABLE returning the list (round 6): the mids' conditionings (two lerp launches each) are then built -
@@ -699,7 +750,20 @@ class StableDiffusionXLPipeline:
         # draws per run: an anchor's (from step 0) and a mid branch's (from idx_injection) - ancestral: one per step; LCM: one per
         # step but the schedule's last, so both kinds of run have noise at exactly the steps < nd_a
         nd_a, nm = noise_draws_per_run(sched, steps, 0), noise_draws_per_run(sched, steps, idx_injection)
-        if nd_a > 0:              # sample-major draws: anchor 1, anchor 2 (those denoised here), then every mid branch
+        if nd_a > 0 and hasattr(sched.noise_source, "keyed"):
+            # counter-based: rows (trajectory, step) of the anchors denoised here at every drawing step, then of the mids at the
+            # steps they run - step-major, so each step's share is contiguous
+            ids = None if noise_ids is None else [noise_ids[0][k] for k in live] + list(noise_ids[1])
+            mid_steps = [i for i in range(idx_injection, nd_a) if not dead[i]] if G else []
+            flat = self._keyed_noise(sched, ids, [(s, i) for i in range(nd_a) for s in range(A)]
+                                     + [(A + g, i) for i in mid_steps for g in range(G)], shape1)
+            noise_a = flat[:A * nd_a].view(nd_a, A, *shape1[1:]) if A else None
+            if mid_steps:
+                per_step = flat[A * nd_a:].view(len(mid_steps), G, *shape1[1:])
+                noise_m = [None] * nm                       # (indexed like the stream's [nm, G, ...]; a dead step has no entry)
+                for j, i in enumerate(mid_steps):
+                    noise_m[i - idx_injection] = per_step[j]
+        elif nd_a > 0:            # sample-major draws: anchor 1, anchor 2 (those denoised here), then every mid branch
             n_draw, keep = self._noise_slots(noise_slots, G)
             flat = sched.draw_noise_many(A * nd_a + n_draw * nm, shape1, self.device)      # ONE launch on the device RNG
             # (contiguous per step: the step kernels take noise[i] by pointer)

@@ -56,7 +56,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          on_segment: Optional[Callable[[int, List], None]] = None,
                          pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
                          movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
-                         list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None) -> List[List]:
+                         list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None,
+                         noise: Optional[str] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -79,12 +80,15 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     frame an image anchor (``set_anchor_image1`` / ``2``; strength ``None`` = 0.5).  The image anchors are set and cleared per
     segment; a shared image key frame is computed (and encoded) once and recycled through ``swap_forward`` like any other.  The
     engine's image anchors are cleared when the chain ends.  Together with ``pipeline_keyframes=True``: ``ValueError``.
+    ``noise``: "stream" / "counter" = the native pipe's ``noise`` for this chain (None: as the pipe stands); the previous value is
+    restored afterwards.  Under "counter" a key frame's per-step noise depends on its seed alone, so the chain renders the same
+    frames with and without ``pipeline_keyframes``, at any frontier width and under a farm of any size.
     """
     images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
     if images is not None and pipeline_keyframes:
         raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
                          "it cannot be combined with image key frames (list_images)")
-    with _decoder_as(be, decoder):
+    with _decoder_as(be, decoder), _noise_as(be, noise):
         try:
             return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
                                          keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
@@ -120,6 +124,23 @@ def _decoder_as(be, decoder: Optional[str]):
         yield
     finally:
         pipe.decoder = previous
+
+
+@contextlib.contextmanager
+def _noise_as(be, noise: Optional[str]):
+    """Run the body with the engine's native pipe on ``noise`` (None: untouched), then put the previous value back."""
+    if noise is None:
+        yield
+        return
+    pipe = be.dh.pipe
+    if not hasattr(type(pipe), "noise"):
+        raise ValueError("noise=... needs the native pipe (NativeSDXLPipe)")
+    previous = pipe.noise
+    pipe.noise = noise
+    try:
+        yield
+    finally:
+        pipe.noise = previous
 
 
 def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts, keep_parts,
@@ -199,8 +220,8 @@ def _precompute_chain(be, list_prompts, list_seeds, list_negative_prompts):
 def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_single_trans: float = 10,
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
-                   decoder: Optional[str] = None) -> List[List]:
-    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder`` as there).
+                   decoder: Optional[str] = None, noise: Optional[str] = None) -> List[List]:
+    """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder``, ``noise`` as there).
     Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames."""
     header, items = load_movie_json(fp_json)
     images = strengths = None
@@ -215,4 +236,4 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
                                 movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
-                                list_image_strengths=strengths)
+                                list_image_strengths=strengths, noise=noise)

@@ -37,7 +37,7 @@ _ENGINE_FIELDS = ("prompt1", "prompt2", "text_embedding1", "text_embedding2", "n
                   "parental_crossfeed_power", "parental_crossfeed_range", "parental_crossfeed_decay",
                   "num_inference_steps", "list_idx_injection", "list_nmb_stems", "image1_lowres", "image2_lowres",
                   "multi_transition_img_first", "multi_transition_img_last", "_preset_anchor_frames", "stats", "movie_encoder",
-                  "movie_size", "movie_resample", "anchor_image1", "anchor_image2", "anchor_image_strength1", "anchor_image_strength2")
+                  "movie_size", "movie_resample", "anchor_image1", "anchor_image2", "anchor_image_strength1", "anchor_image_strength2", "noise")
 # holder attributes that follow them
 _HOLDER_FIELDS = ("negative_prompt", "guidance_scale", "num_inference_steps", "width_img", "height_img", "width_latent",
                   "height_latent")
