@@ -26,11 +26,32 @@ F16, F32 = torch.float16, torch.float32
 
 
 class Arena:
-    def __init__(self, device):
+    """``journal=True``: every ``alloc`` / ``release`` appends ``(event, buffer id, program name, op index)`` to ``self.journal`` -
+    the buffer id is the raw buffer's index in ``self.all``, the last two come from ``self.clock`` (set by the program that is
+    recording: ``Arena.clocked``; ``(None, -1)`` outside a recording).  The journal only listens: which buffer an ``alloc`` hands
+    out, and so every recorded pointer, is the same with it on or off."""
+
+    def __init__(self, device, journal: bool = False):
         self.device = device
         self.free: Dict[int, List[torch.Tensor]] = {}
         self.all: List[torch.Tensor] = []
         self.bytes_allocated = 0
+        self.journal: Optional[List[Tuple[str, int, Optional[str], int]]] = [] if journal else None
+        self.clock = None                   # () -> (program name, number of ops recorded so far)
+        self._ids: Dict[int, int] = {}      # id(raw) -> index in self.all (journal only)
+
+    @contextlib.contextmanager
+    def clocked(self, prog: "Program"):
+        """While ``prog`` records: journal entries carry its name and the index of the op that will be recorded next."""
+        self.clock = lambda: (prog.name, prog.num_ops)
+        try:
+            yield
+        finally:
+            self.clock = None
+
+    def _log(self, event: str, raw: torch.Tensor) -> None:
+        name, op = self.clock() if self.clock is not None else (None, -1)
+        self.journal.append((event, self._ids[id(raw)], name, op))
 
     @staticmethod
     def _cls(nbytes: int) -> int:
@@ -49,6 +70,10 @@ class Arena:
             raw = torch.empty(cls, dtype=torch.uint8, device=self.device)
             self.all.append(raw)
             self.bytes_allocated += cls
+            if self.journal is not None:
+                self._ids[id(raw)] = len(self.all) - 1
+        if self.journal is not None:
+            self._log("alloc", raw)
         t = raw[: n * esz].view(dtype).view(*shape)
         t._lb_raw = raw
         return t
@@ -64,6 +89,8 @@ class Arena:
         if raw is None:
             return
         t._lb_raw = None
+        if self.journal is not None:
+            self._log("release", raw)
         self.free.setdefault(raw.numel(), []).append(raw)
 
 

@@ -20,7 +20,7 @@ MI355X-specific here:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -59,6 +59,37 @@ class UNetConfig:
 
 def _pad(n: int, m: int) -> int:
     return (n + m - 1) // m * m
+
+
+class Mark(NamedTuple):
+    """End of one emission unit of a recorded program (``UNetProgram.marks`` / ``VAEProgram.marks``): the unit's ops are those from
+    the previous mark of the same program up to ``op_end`` (exclusive), ``out`` is the view its result is read through - valid right
+    after op ``op_end - 1``, the arena may hand the buffer on later - and ``inputs`` names the units (or program inputs) it read."""
+    name: str
+    kind: str
+    program: str
+    op_end: int
+    out: torch.Tensor
+    inputs: Tuple[str, ...]
+
+
+def capture_marks(progs: Dict[str, Program], marks: List[Mark], convert=None) -> Dict[str, torch.Tensor]:
+    """Replay ``progs`` (in order) from mark to mark with ``run_range`` and clone every unit's output right after its last op.
+    ``convert(mark, clone)`` may turn the clone into what the caller wants to see."""
+    taps: Dict[str, torch.Tensor] = {}
+    for pname, prog in progs.items():
+        at = 0
+        for m in marks:
+            if m.program != pname:
+                continue
+            if m.op_end > at:
+                prog.run_range(at, m.op_end)
+                at = m.op_end
+            t = m.out.clone()
+            taps[m.name] = convert(m, t) if convert is not None else t
+        if at < prog.num_ops:
+            prog.run_range(at, prog.num_ops)
+    return taps
 
 
 class NativeUNet:
@@ -256,9 +287,10 @@ class NativeUNet:
         return sum(t.numel() * t.element_size() for t in self.w.values())
 
     # ------------------------------------------------------------------ program -----------
-    def build(self, B: int, L, ragged_halo: bool = True) -> "UNetProgram":
-        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``)."""
-        return UNetProgram(self, B, L, ragged_halo=ragged_halo)
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "UNetProgram":
+        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
+        keeps its alloc / release journal (``Arena``); the recorded ops are the same."""
+        return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
 
 
 class UNetProgram:
@@ -266,9 +298,12 @@ class UNetProgram:
     caller fills (torch copies on the launch stream); ``run`` replays the launches.
     ``L``: latent side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for square programs (else None).  ``ragged_halo``: a
     non-square program may send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo
-    kernel (``geometry.use_ragged_halo``); a square program records what it always recorded."""
+    kernel (``geometry.use_ragged_halo``); a square program records what it always recorded.
+    ``marks``: one ``Mark`` per emission unit (``aug`` and ``ctx_kv`` of the conditioning program; ``temb_all``, ``conv_in``, every
+    resnet / transformer / downsampler / upsampler by its weight prefix, and ``eps``); ``tap_names`` maps the block taps of the
+    oracle (``conv_in``, ``down0`` .., ``mid``, ``up0`` ..) to the unit whose output they are.  ``capture()`` fills ``taps``."""
 
-    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True):
+    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False):
         cfg = net.cfg
         H, W = latent_hw(L)
         check_unet_latent_size(H, W, len(cfg.block_channels))
@@ -277,9 +312,12 @@ class UNetProgram:
         # LayerNorm handling of THIS program ("auto": fold into the consumers only where the program is launch-bound)
         self.ln_mode = net.fuse_layernorm if net.fuse_layernorm != "auto" else (B * max(H // 4, 1) * max(W // 4, 1) <= 1024)
         dev = net.device
-        self.arena = Arena(dev)
+        self.arena = Arena(dev, journal=journal)
         self.em = Emitter(self.arena)
         self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
+        self.marks: List[Mark] = []
+        self.tap_names: Dict[str, str] = {}
+        self.persistent: List[torch.Tensor] = []       # arena tensors that stay live after emission
         T = cfg.time_embed_dim
         # ---- inputs / outputs (persistent) ----
         self.x_in = torch.zeros(B, cfg.in_channels, H, W, dtype=F16, device=dev)
@@ -295,11 +333,28 @@ class UNetProgram:
         self.ctx_kv = torch.zeros(B * CTX_PAD, 2 * net.n_ctx, dtype=F16, device=dev)   # [K of all blocks | V of all blocks]
         self.prog_cond = Program("unet-cond")
         self.prog_step = Program("unet-step")
-        with self.prog_cond.record():
+        with self.prog_cond.record(), self.arena.clocked(self.prog_cond):
+            self._rec = self.prog_cond
             self._emit_cond()
-        with self.prog_step.record():
+        with self.prog_step.record(), self.arena.clocked(self.prog_step):
+            self._rec = self.prog_step
             self._emit_step()
+        self._rec = None
         self.taps: Dict[str, torch.Tensor] = {}
+
+    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
+        self.marks.append(Mark(name, kind, self._rec.name, self._rec.num_ops, out, tuple(inputs)))
+        return name
+
+    def capture(self) -> Dict[str, torch.Tensor]:
+        """Replay both programs on the inputs the buffers hold now (``set_conditioning`` / ``forward`` filled them), unit by unit,
+        and keep a clone of every unit's output in ``taps`` (fp16, NHWC for feature maps), also under the block-tap names of
+        ``tap_names``.  Leaves ``eps`` as a ``forward`` would."""
+        taps = capture_marks({p.name: p for p in (self.prog_cond, self.prog_step)}, self.marks)
+        for tap, unit in self.tap_names.items():
+            taps[tap] = taps[unit]
+        self.taps = taps
+        return taps
 
     # ---- helpers ------------------------------------------------------------------------
     def _conv(self, x, name, B, H, W, cin, cout, *, stride=1, ups=0, rowvec=None, ld_rowvec=None,
@@ -434,8 +489,10 @@ class UNetProgram:
         em.gemm(a1, w["add_embedding.linear_2.weight"], self.aug, M=B, bias=w["add_embedding.linear_2.bias"])
         ar.release(add_in)
         ar.release(a1)
+        self._mark("aug", "aug", self.aug, "text_embeds", "time_ids")
         ctx2d = self.ctx.view(B * CTX_PAD, cfg.cross_dim)
         em.gemm(ctx2d, w["ctx_kv.weight"], self.ctx_kv, M=B * CTX_PAD)
+        self._mark("ctx_kv", "ctx_kv", self.ctx_kv, "ctx")
 
     # ---- step program: depends on the latent and the timestep
     def _emit_step(self):
@@ -460,43 +517,55 @@ class UNetProgram:
         ar.release(tsin)
         ar.release(t1)
         ar.release(emb)
+        self.persistent.append(self.temb_all)
+        self._mark("temb_all", "temb_all", self.temb_all, "tvals", "aug", *(("timestep_cond",) if self.timestep_cond is not None else ()))
         # input: NCHW latent -> NHWC (channels padded to 8)
         cin_p = _pad(cfg.in_channels, 8)
         x8 = ar.alloc((B, self.H, self.W, cin_p))
         api.lb_nchw_to_nhwc_f16(self.x_in.data_ptr(), x8.data_ptr(), B, cfg.in_channels, self.H * self.W, cin_p, 1.0, _stream())
         h, _, _ = self._conv(x8, "conv_in", B, self.H, self.W, cfg.in_channels, ch[0])
         ar.release(x8)
-        skips = [(h, ch[0])]
+        at = self.tap_names["conv_in"] = self._mark("conv_in", "conv_in", h, "x_in")     # ``at``: the unit whose output h is
+        skips = [(h, ch[0], at)]
         sh, sw, prev = self.H, self.W, ch[0]                    # the current level's map is sh x sw
         for bi, c in enumerate(ch):
             for li in range(cfg.layers_per_block):
-                nxt = self._resnet(h, f"down_blocks.{bi}.resnets.{li}", B, sh, sw, prev, c)
-                if not any(h is s for s, _ in skips):
+                p = f"down_blocks.{bi}.resnets.{li}"
+                nxt = self._resnet(h, p, B, sh, sw, prev, c)
+                if not any(h is s for s, _, _ in skips):
                     ar.release(h)
                 h = nxt
+                at = self._mark(p, "resnet", h, at, "temb_all")
                 if cfg.transformer_depth[bi]:
-                    nxt = self._transformer(h, f"down_blocks.{bi}.attentions.{li}", B, sh, sw, c,
-                                            cfg.transformer_depth[bi])
+                    p = f"down_blocks.{bi}.attentions.{li}"
+                    nxt = self._transformer(h, p, B, sh, sw, c, cfg.transformer_depth[bi])
                     ar.release(h)
                     h = nxt
-                skips.append((h, c))
+                    at = self._mark(p, "transformer", h, at, "ctx_kv")
+                skips.append((h, c, at))
                 prev = c
             if bi < len(ch) - 1:
-                h, sh, sw = self._conv(h, f"down_blocks.{bi}.downsamplers.0.conv", B, sh, sw, c, c, stride=2)
-                skips.append((h, c))
+                p = f"down_blocks.{bi}.downsamplers.0.conv"
+                h, sh, sw = self._conv(h, p, B, sh, sw, c, c, stride=2)
+                at = self._mark(p, "downsample", h, at)
+                skips.append((h, c, at))
+            self.tap_names[f"down{bi}"] = at
         c = ch[-1]
         nxt = self._resnet(h, "mid_block.resnets.0", B, sh, sw, c, c)     # h is a skip: not released
         h = nxt
+        at = self._mark("mid_block.resnets.0", "resnet", h, at, "temb_all")
         nxt = self._transformer(h, "mid_block.attentions.0", B, sh, sw, c, cfg.transformer_depth[-1])
         ar.release(h)
         h = nxt
+        at = self._mark("mid_block.attentions.0", "transformer", h, at, "ctx_kv")
         nxt = self._resnet(h, "mid_block.resnets.1", B, sh, sw, c, c)
         ar.release(h)
         h = nxt
+        at = self.tap_names["mid"] = self._mark("mid_block.resnets.1", "resnet", h, at, "temb_all")
         depths = list(reversed(cfg.transformer_depth))
         for ui, (c, cins) in enumerate(net.up_plan()):
             for li, (hid, sc) in enumerate(cins):
-                skip, sch = skips.pop()
+                skip, sch, skip_at = skips.pop()
                 assert sch == sc
                 M = B * sh * sw
                 cat = ar.alloc((B, sh, sw, hid + sc))
@@ -504,16 +573,23 @@ class UNetProgram:
                 em.copy_cols(skip, cat, rows=M, cols=sc, ld_src=sc, ld_dst=hid + sc, dst_off=hid)
                 ar.release(h)
                 ar.release(skip)
-                h = self._resnet(cat, f"up_blocks.{ui}.resnets.{li}", B, sh, sw, hid + sc, c)
+                p = f"up_blocks.{ui}.resnets.{li}"
+                h = self._resnet(cat, p, B, sh, sw, hid + sc, c)
                 ar.release(cat)
+                at = self._mark(p, "resnet", h, at, skip_at, "temb_all")      # (reads the concatenation [h | skip])
                 if depths[ui]:
-                    nxt = self._transformer(h, f"up_blocks.{ui}.attentions.{li}", B, sh, sw, c, depths[ui])
+                    p = f"up_blocks.{ui}.attentions.{li}"
+                    nxt = self._transformer(h, p, B, sh, sw, c, depths[ui])
                     ar.release(h)
                     h = nxt
+                    at = self._mark(p, "transformer", h, at, "ctx_kv")
             if ui < len(ch) - 1:
-                nxt, sh, sw = self._upconv(h, f"up_blocks.{ui}.upsamplers.0.conv", B, sh, sw, c)
+                p = f"up_blocks.{ui}.upsamplers.0.conv"
+                nxt, sh, sw = self._upconv(h, p, B, sh, sw, c)
                 ar.release(h)
                 h = nxt
+                at = self._mark(p, "upsample", h, at)
+            self.tap_names[f"up{ui}"] = at
         n = ar.alloc((B, sh, sw, ch[0]))
         em.groupnorm(h, n, w["conv_norm_out.weight"], w["conv_norm_out.bias"], B=B, HW=sh * sw, C_=ch[0],
                      eps=1e-5, silu=True, groups=cfg.norm_groups)
@@ -523,6 +599,7 @@ class UNetProgram:
         api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.eps.data_ptr(), B, cfg.out_channels, self.H * self.W,
                                 _pad(cfg.out_channels, 4), _stream())
         ar.release(o)
+        self._mark("eps", "out", self.eps, at)
 
     # ---- execution ------------------------------------------------------------------------
     def set_conditioning(self, ctx: torch.Tensor, text_embeds: torch.Tensor, time_ids: torch.Tensor,

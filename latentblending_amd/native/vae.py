@@ -21,7 +21,7 @@ Output is quantised on device to uint8 NHWC frames.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, List, Tuple
 
 import torch
 
@@ -29,7 +29,7 @@ from ..hip import lib
 from ..hip.lib import api
 from .geometry import latent_hw
 from .runtime import Arena, Emitter, Program, F16, F32, _stream
-from .unet import _pad
+from .unet import Mark, _pad, capture_marks
 
 STREAM_SCALE = 1.0 / 16.0
 
@@ -131,16 +131,20 @@ class NativeVAEDecoder:
         for key in [k for k in self.w if k.endswith(".bias")]:          # biases in stream units (x 2^-4, exact)
             self.w[key + "_s"] = self.w[key] * STREAM_SCALE
 
-    def build(self, B: int, L, ragged_halo: bool = True) -> "VAEProgram":
-        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``)."""
-        return VAEProgram(self, B, L, ragged_halo=ragged_halo)
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "VAEProgram":
+        """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
+        keeps its alloc / release journal (``Arena``); the recorded ops are the same."""
+        return VAEProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
 
 
 class VAEProgram:
     """One recorded decode for a fixed (batch, latent size): ``L`` = a side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for
-    square programs (else None).  ``ragged_halo`` as in ``UNetProgram``."""
+    square programs (else None).  ``ragged_halo`` as in ``UNetProgram``.
+    ``marks``: one ``Mark`` per emission unit (``conv_in`` = post_quant_conv + conv_in, every resnet and upsampler by its weight
+    prefix, ``mid_attention``, ``image_f32``); ``tap_names`` maps the oracle's block taps (``mid``, ``up0`` ..) to units;
+    ``capture()`` fills ``taps``."""
 
-    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True):
+    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
         cfg = net.cfg
         H, W = latent_hw(L)
         self.net, self.B, self.H, self.W = net, B, H, W
@@ -149,17 +153,37 @@ class VAEProgram:
         self.fuse_gn_stats = bool(getattr(cfg, "fuse_gn_stats", True))
         self.fused_mid_attention = bool(getattr(cfg, "fused_mid_attention", True))
         dev = net.device
-        self.arena = Arena(dev)
+        self.arena = Arena(dev, journal=journal)
         self.em = Emitter(self.arena)
         self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
+        self.marks: List[Mark] = []
+        self.tap_names: Dict[str, str] = {}
+        self.persistent: List[torch.Tensor] = []       # arena tensors that stay live after emission: none
+        self.taps: Dict[str, torch.Tensor] = {}
         SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
         self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
         self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
         self.image_f32 = torch.zeros(B, SH, SW, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
         self._pq = torch.zeros(B, H, W, _pad(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
         self.prog = Program("vae-decode")
-        with self.prog.record():
+        with self.prog.record(), self.arena.clocked(self.prog):
             self._emit()
+
+    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
+        self.marks.append(Mark(name, kind, self.prog.name, self.prog.num_ops, out, tuple(inputs)))
+        return name
+
+    def capture(self) -> Dict[str, torch.Tensor]:
+        """Replay the program on the latent ``z_in`` holds now, unit by unit, and keep a clone of every unit's output in ``taps``
+        (NHWC), also under the block-tap names of ``tap_names``.  Stream tensors come back in real units as fp32: the 2^-4 of the
+        scaled fp16 stream is undone (exactly).  Leaves ``frames`` / ``image_f32`` as a ``decode`` would."""
+        def real(m, t):
+            return t.float() / STREAM_SCALE if (self.scaled and m.kind != "out") else t
+        taps = capture_marks({self.prog.name: self.prog}, self.marks, real)
+        for tap, unit in self.tap_names.items():
+            taps[tap] = taps[unit]
+        self.taps = taps
+        return taps
 
     # ---- residual-stream format --------------------------------------------------------------
     # scaled (default): stream tensors hold value * 2^-4 in fp16;  f32: plain fp32 (see module docstring)
@@ -311,14 +335,20 @@ class VAEProgram:
         em.gemm(z8, w["post_quant_conv.weight"], self._pq, M=B * LH * LW, bias=w["post_quant_conv.bias"], ldc=lc_p)
         ar.release(z8)
         h = self._stream_conv(self._pq, "decoder.conv_in", B, LH, LW, lc, top)
+        at = self._mark("conv_in", "conv_in", h, "z_in")        # ``at``: the unit whose output h is
         nxt = self._resnet(h, "decoder.mid_block.resnets.0", B, LH, LW, top, top); ar.release(h); h = nxt
+        at = self._mark("decoder.mid_block.resnets.0", "resnet", h, at)
         h = self._mid_attention(h, B, LH, LW, top)
+        at = self._mark("mid_attention", "mid_attention", h, at)
         nxt = self._resnet(h, "decoder.mid_block.resnets.1", B, LH, LW, top, top); ar.release(h); h = nxt
+        at = self.tap_names["mid"] = self._mark("decoder.mid_block.resnets.1", "resnet", h, at)
         sh, sw, prev = LH, LW, top                              # the current level's map is sh x sw
         for ui, c in enumerate(rev):
             for li in range(cfg.layers_per_block + 1):
-                nxt = self._resnet(h, f"decoder.up_blocks.{ui}.resnets.{li}", B, sh, sw, prev, c)
+                p = f"decoder.up_blocks.{ui}.resnets.{li}"
+                nxt = self._resnet(h, p, B, sh, sw, prev, c)
                 ar.release(h); h = nxt
+                at = self._mark(p, "resnet", h, at)
                 prev = c
             if ui < len(rev) - 1:
                 h16, owned = self._stream_as_operand(h, B, sh, sw, c)
@@ -344,6 +374,8 @@ class VAEProgram:
                 ar.release(h)
                 h = up
                 sh, sw = 2 * sh, 2 * sw
+                at = self._mark(name, "upsample", h, at)
+            self.tap_names[f"up{ui}"] = at
         cin_p = _pad(rev[-1], 8)
         conv_out = dict(Hin=sh, Win=sw, Cin=cin_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p)
         g = em.gn_operand(h, w["decoder.conv_out.weight"], M=B * sh * sw, conv=conv_out, flags=lib.GEMM_OUT_F32,
@@ -352,6 +384,7 @@ class VAEProgram:
         em.gemm(h, w["decoder.conv_out.weight"], self.image_f32, M=B * sh * sw, bias=w["decoder.conv_out.bias"],
                 flags=lib.GEMM_OUT_F32, conv=conv_out, gn=g)
         ar.release(h)
+        self._mark("image_f32", "out", self.image_f32, at)
         api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw,
                               _pad(cfg.out_channels, 4), 1, _stream())
 

@@ -461,11 +461,11 @@ def ancestral_sigmas(s_from: float, s_to: float) -> Tuple[float, float]:
 # =============================================================================================
 # UNet
 # =============================================================================================
-def sinusoid(values: Tensor, dim: int) -> Tensor:
+def sinusoid(values: Tensor, dim: int, dtype=torch.float32) -> Tensor:
     """diffusers ``Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)``: [cos | sin]."""
     half = dim // 2
-    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32, device=values.device) / half)
-    ang = values.float()[:, None] * freqs[None]
+    freqs = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=dtype, device=values.device) / half)
+    ang = values.to(dtype)[:, None] * freqs[None]
     return torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1)
 
 
@@ -526,25 +526,26 @@ def transformer_2d(x, ctx, w, p, depth, heads, groups):
     return h + x
 
 
-def unet_embedding(cfg: UNetCfg, w, t: Tensor, text_embeds: Tensor, time_ids: Tensor) -> Tensor:
+def unet_embedding(cfg: UNetCfg, w, t: Tensor, text_embeds: Tensor, time_ids: Tensor, dtype=torch.float32) -> Tensor:
     B = text_embeds.shape[0]
-    t = t.reshape(-1).float().expand(B)
-    temb = _lin(F.silu(_lin(sinusoid(t, cfg.block_channels[0]), w, "time_embedding.linear_1")),
+    t = t.reshape(-1).to(dtype).expand(B)
+    temb = _lin(F.silu(_lin(sinusoid(t, cfg.block_channels[0], dtype), w, "time_embedding.linear_1")),
                 w, "time_embedding.linear_2")
-    ids = sinusoid(time_ids.reshape(-1), cfg.add_time_dim).reshape(B, -1)
-    add_in = torch.cat([text_embeds.float(), ids], dim=-1)
+    ids = sinusoid(time_ids.reshape(-1), cfg.add_time_dim, dtype).reshape(B, -1)
+    add_in = torch.cat([text_embeds.to(dtype), ids], dim=-1)
     aug = _lin(F.silu(_lin(add_in, w, "add_embedding.linear_1")), w, "add_embedding.linear_2")
     return temb + aug
 
 
 def unet_forward(cfg: UNetCfg, w: Dict[str, Tensor], sample: Tensor, t, ctx: Tensor,
-                 text_embeds: Tensor, time_ids: Tensor, taps: Optional[dict] = None) -> Tensor:
-    """sample [B,4,L,L] -> eps [B,4,L,L]; all arithmetic fp32.  ``taps`` collects intermediates."""
+                 text_embeds: Tensor, time_ids: Tensor, taps: Optional[dict] = None, dtype=torch.float32) -> Tensor:
+    """sample [B,4,L,L] -> eps [B,4,L,L]; all arithmetic fp32.  ``taps`` collects intermediates.  ``dtype``: the arithmetic's
+    type - torch.float64 (with weights ``w`` of that type) for the tests that hold single units to a float64 reference."""
     g = cfg.norm_groups
-    x = sample.float()
-    ctx = ctx.float()
+    x = sample.to(dtype)
+    ctx = ctx.to(dtype)
     t = torch.as_tensor(t)
-    emb = unet_embedding(cfg, w, t, text_embeds, time_ids)
+    emb = unet_embedding(cfg, w, t, text_embeds, time_ids, dtype)
     ch = cfg.block_channels
     h = _conv(x, w, "conv_in")
     skips = [h]
@@ -590,10 +591,10 @@ def unet_forward(cfg: UNetCfg, w: Dict[str, Tensor], sample: Tensor, t, ctx: Ten
 # =============================================================================================
 # VAE decoder + postprocess
 # =============================================================================================
-def vae_decode(cfg: VAECfg, w: Dict[str, Tensor], z: Tensor, taps: Optional[dict] = None) -> Tensor:
-    """z (already divided by the scaling factor) [B,4,L,L] -> image [B,3,8L,8L] in ~[-1,1]."""
+def vae_decode(cfg: VAECfg, w: Dict[str, Tensor], z: Tensor, taps: Optional[dict] = None, dtype=torch.float32) -> Tensor:
+    """z (already divided by the scaling factor) [B,4,L,L] -> image [B,3,8L,8L] in ~[-1,1].  ``dtype`` as in ``unet_forward``."""
     g, eps = cfg.norm_groups, 1e-6
-    h = _conv(z.float(), w, "post_quant_conv", pad=0)
+    h = _conv(z.to(dtype), w, "post_quant_conv", pad=0)
     h = _conv(h, w, "decoder.conv_in")
     h = resnet_block(h, None, w, "decoder.mid_block.resnets.0", g, eps)
     a = "decoder.mid_block.attentions.0"
