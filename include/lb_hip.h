@@ -94,9 +94,21 @@ int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* par
 /* Counter-based sampler noise (the `noise` operand of the ancestral / LCM steps above when a pipe runs with noise="counter"):
  * Philox4x32-10 words turned into fp16 normals in float64, each value a pure function of its row's key and counter words and of
  * its element index - so a seed gives the same noise whatever batch, order or rank serves the draw.  The step kernels are
- * unchanged: they receive an ordinary noise tensor.  The prototype and its contract live in lb_hip_noise.h: this header lists
- * what hip/lib.py binds in SIGNATURES (hip/lib.py: NOISE_SIGNATURES). */
-#include "lb_hip_noise.h"
+ * unchanged: they receive an ordinary noise tensor.
+ * rows_dev: uint32[n][8] = {key0, key1, ctr1, ctr2, ctr3, 0, 0, 0} (32-byte rows); out: fp16 [n][per_sample].
+ * Element e of row j is word e % 4 of Philox4x32-10(ctr = {e / 4, ctr1, ctr2, ctr3}, key = {key0, key1}) (Random123:
+ * multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds), turned into normals in pairs -
+ * words (w0, w1) give elements 0 and 1, (w2, w3) elements 2 and 3:
+ *   u1 = ((wa >> 8) + 0.5) 2^-24;  t = ((wb >> 8) + 0.5) 2^-23;  r = sqrt(-2 ln u1);  z_even = r cospi(t);  z_odd = r sinpi(t)
+ * evaluated in float64 and rounded once to fp16 (nearest even); |z| <= 5.89.  A value depends on its row's five words and its
+ * index e alone: not on n, on the row's position j, on `out`, on the stream or on any launch before it.
+ * raw = 1 (tests, tools): out is uint32 [n][per_sample] holding the Philox words themselves, same indexing.
+ * Refused before anything is launched or recorded: n <= 0; per_sample <= 0 or not a multiple of 8; null or 16-byte-misaligned
+ * rows_dev / out; per_sample / 4 >= 2^32.  Reads nothing but rows_dev[0 : 8 n], writes nothing outside out[0 : n per_sample].
+ * rows_dev is read when the kernel RUNS: a recorded op reads it at every replay, like every operand a launcher records, so the
+ * rows must stay allocated for as long as the program lives - and rewriting them between replays is how a program draws other
+ * noise. */
+int lb_counter_noise_f16(const void* rows_dev, void* out, long per_sample, int n, int raw, void* stream);
 
 /* ---- dense contractions (every nn.Linear / nn.Conv2d of the UNet at
  *      diffusers_holder.py:336, of the VAE decoder at :135 and of LPIPS-Alex at
@@ -142,7 +154,7 @@ enum {
                               * routes there: A is consumed through a GroupNorm given as an affine table - the kernel multiplies
                               * f16(silu(fma(A[b, y, x, c], gn_table[b][c].scale, gn_table[b][c].shift))) (SiLU when gn_silu), the very
                               * fp16 value lb_groupnorm_from_stats would have stored, transformed in LDS after staging; zero padding stays
-                              * zero.  gn_table = [B][Cin] float2 from lb_groupnorm_affine_from_stats (lb_hip_gn_a.h).  A flagged problem
+                              * zero.  gn_table = [B][Cin] float2 from lb_groupnorm_affine_from_stats (below).  A flagged problem
                               * runs on one of the two kernels or is refused: no table, a ragged (LB_GEMM_HALO_RAGGED shape that does not
                               * divide into tiles) or K-split (LB_GEMM_HALO_KSPLIT) launch, a sub-pixel upconv, LB_GEMM_C64, or a route to
                               * any other kernel.  Whether fusing pays is lb_conv_halo_gn_a_plan's answer (lb_conv_halo_set_gn_a). */
@@ -246,17 +258,22 @@ void lb_conv_halo_plan(const LbGemmParams* params, int* kind, int* tile_w, long*
  * (one block per CU, each walking units [b * units / grid, (b + 1) * units / grid)) and split = 1 if a launch with these
  * parameters takes the K-split form, 0 = it stays unsplit even if flagged (then units = grid = 0 unless the shape is eligible).
  * lb_conv_halo_plan keeps reporting the tile items and the unsplit grid. */
+void lb_conv_halo_ksplit_plan(const LbGemmParams* params, long* units, long* grid, int* split);
 /* Bytes of the workspace (`partial`) a launch with these parameters needs: one int counter per (channel block, tile), padded to
  * 256 B, then two 256 x 128 fp32 slabs per block of the grid; 0 = the launch does not split.  Zero the counters once. */
+long lb_conv_halo_ksplit_workspace_bytes(const LbGemmParams* params);
 /* Tuning: mode 0 = never split, 1 = the step-count policy (default), 2 = every flagged whole-tile launch with Cin >= 128;
  * grid > 0 overrides the grid (tests only: size the workspace under the same override), 0 = one block per CU. */
-/* The three prototypes (lb_conv_halo_ksplit_plan, lb_conv_halo_ksplit_workspace_bytes, lb_conv_halo_set_ksplit) live in
- * lb_hip_ksplit.h: this header lists what hip/lib.py binds in SIGNATURES - the table of what a program can record, one replay case
- * per entry - and these three launch nothing and take no stream (hip/lib.py: HOST_SIGNATURES). */
-#include "lb_hip_ksplit.h"
-/* LB_GEMM_GN_A: the table launcher (lb_groupnorm_affine_from_stats), the plan the emitter asks (lb_conv_halo_gn_a_plan) and the
- * policy switch (lb_conv_halo_set_gn_a) live in lb_hip_gn_a.h for the same reason (hip/lib.py: GN_A_SIGNATURES). */
-#include "lb_hip_gn_a.h"
+void lb_conv_halo_set_ksplit(int mode, int grid);
+/* LB_GEMM_GN_A, host arithmetic only (launches nothing): whether the emitter should fuse a GroupNorm (+ SiLU) into the 3x3 conv
+ * `params` describes (flags WITHOUT LB_GEMM_GN_A, as it would be launched otherwise): fuse = 1 if lb_gemm_f16 would run the
+ * flagged problem on a kernel that implements the flag AND the policy includes the shape (lb_conv_halo_set_gn_a); kind = 0
+ * (cannot), 3 (whole-tile 3x3 halo conv) or 8 (narrow-N conv). */
+void lb_conv_halo_gn_a_plan(const LbGemmParams* params, int* fuse, int* kind);
+/* mode 0 = the plan never fuses, 1 = the measured policy (default), 2 = the plan fuses every eligible launch; grid > 0
+ * overrides the persistent grid of FLAGGED halo launches (tests: several tiles per block on small shapes), 0 = default.
+ * A flagged launch always applies the table, whatever the mode: the mode only changes the plan's answer. */
+void lb_conv_halo_set_gn_a(int mode, int grid);
 /* LB_GEMM_CH_STATS: row blocks PER SAMPLE of the statistics buffer ([N][B * rows] float2) the launch lb_gemm_f16 would make
  * for these parameters writes - from the same routing and the same tile constants as the launch itself; 0 = this problem does
  * not run on a halo-tile kernel (no statistics: the consumer runs the two-pass GroupNorm).  Launches nothing. */
@@ -283,6 +300,12 @@ void lb_groupnorm_set_l3_chunk(long bytes);
 int lb_groupnorm_from_stats(const void* x, void* y, const float* gamma, const float* beta, const float* ch_stats,
                             void* workspace, int B, int HW, int C, int ldx, int ldy, int groups, float eps, int silu,
                             int x_is_f32, int stat_rows_per_sample, void* stream);
+/* GroupNorm (+ SiLU) applied by the consuming 3x3 conv to its own A operand (LB_GEMM_GN_A): the table that conv reads.
+ * ch_stats as for lb_groupnorm_from_stats ([C][B * stat_rows_per_sample] float2 left by the producing conv under
+ * LB_GEMM_CH_STATS) -> table[B][C] float2 (scale, shift): y = x * scale + shift is the GroupNorm of sample b, channel c -
+ * the very pair lb_groupnorm_from_stats folds per channel (same float64 fold, same expressions).  One launch; x is not read. */
+int lb_groupnorm_affine_from_stats(const float* ch_stats, const float* gamma, const float* beta, float* table, int B, int HW,
+                                   int C, int groups, float eps, int stat_rows_per_sample, void* stream);
 long lb_groupnorm_workspace_bytes(int B, int groups);
 int lb_groupnorm_nhwc(const void* x, void* y, const float* gamma, const float* beta, void* workspace,
                       int B, int HW, int C, int ldx, int ldy, int groups, float eps, int silu,

@@ -596,7 +596,7 @@ static int conv_plan(const LbGemmParams& p, LbConvPlan& o) {
     const LbHaloPlan k = o.route == LB_ROUTE_HALO3 ? h : (o.halo_kind == 3 ? lb_conv3x3_halo_plan(p) : LbHaloPlan{});
     o.ksplit_split = k.ks_split, o.ksplit_units = k.ks_units, o.ksplit_grid = k.ks_grid;
     o.ksplit_counter_bytes = k.ks_counter_bytes, o.ksplit_slab_bytes = k.ks_slab_bytes;
-    // LB_GEMM_GN_A (include/lb_hip_gn_a.h): the route, then the kernel's own conditions and the measured policy (conv3_halo.hip).  The
+    // LB_GEMM_GN_A (include/lb_hip.h): the route, then the kernel's own conditions and the measured policy (conv3_halo.hip).  The
     // narrow-N kernel is a streaming kernel that saves a read and a write of its whole input for a map it runs once: +239 us (29.9 %) at
     // B = 17 and +32 us (28.2 %) at B = 2 for the VAE's conv_out (profiles/halo_gn_ab.txt), so it is in wherever the mode allows.
     if (p.N > 0 && p.scatter == 0 && !(p.flags & (LB_GEMM_C64 | LB_GEMM_GN_A))) {

@@ -1,4 +1,4 @@
-// Counter-based sampler noise (include/lb_hip_noise.h): every value is a pure function of (row key, row counter words, element
+// Counter-based sampler noise (include/lb_hip.h): every value is a pure function of (row key, row counter words, element
 // index), so a draw does not depend on how many draws came before it or on the shape of the launch that serves it.
 //   Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11 - the Random123
 //   construction): multipliers 0xD2511F53 / 0xCD9E8D57, Weyl key increments 0x9E3779B9 / 0xBB67AE85, ten rounds.

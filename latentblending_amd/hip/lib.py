@@ -68,120 +68,110 @@ GEMM_GN_A = 8192            # A consumed through a GroupNorm affine table (gn_ta
 GEMM_C64 = 2048              # opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights: that kernel or a refusal (include/lb_hip.h)
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
+_pp, _pi, _pl = C.POINTER(LbGemmParams), C.POINTER(_i), C.POINTER(_l)
 
-# name -> (restype, argtypes); launchers (restype int) are wrapped with error checking
+# What an entry point is to a caller, and with it how it is bound:
+#   _L "launcher": takes the stream as its last void*, returns an int status and can be recorded into a program (tests/_replay.py
+#                  holds one replay case per launcher); bound through the checking wrapper
+#   _S "status":   returns an int status but is nothing a program records; bound through the checking wrapper
+#   _V "value":    returns a value or nothing (sizes, plans that answer through out-pointers, setters); bound raw
+_L, _S, _V = "launcher", "status", "value"
+
+# every symbol include/lb_hip.h declares outside its study block: name -> (restype, argtypes, role)
 SIGNATURES = {
-    "lb_version": (_i, []),
-    "lb_last_error_string": (C.c_char_p, []),
-    "lb_device_info": (_i, [_i, C.POINTER(_i), C.POINTER(_l), C.c_char_p, _i]),
-    "lb_slerp_pairs_f16": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp]),
-    "lb_slerp_pairs_f32": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp]),
-    "lb_slerp_pairs_f64": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp]),
-    "lb_slerp_batched_f16": (_i, [_vp, _vp, _vp, _vp, _l, _l, _vp]),
-    "lb_slerp_strided_f16": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _l, _vp]),
-    "lb_lerp_f16": (_i, [_vp, _vp, _vp, _l, _d, _vp]),
-    "lb_lerp_f32": (_i, [_vp, _vp, _vp, _l, _d, _vp]),
-    "lb_scale_model_input_f16": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
-    "lb_euler_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp]),
-    "lb_ddim_step_f16": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp]),
-    "lb_gemm_f16": (_i, [C.POINTER(LbGemmParams), _vp]),
-    "lb_gemm_workspace_bytes": (_l, [_i, _i]),
-    "lb_gemm_set_tuning": (None, [_i, _i]),
-    "lb_gemm_set_depth": (None, [_i]),
-    "lb_gemm_set_variant": (None, [_i, _i]),
-    "lb_gemm_set_wide_store": (None, [_i]),
-    "lb_gemm_set_lean_epilogue": (None, [_i]),
-    "lb_gemm_set_t192_waves8": (None, [_i]),
-    "lb_gemm_set_kgroups": (None, [_i]),
-    "lb_gemm_pp_set_group": (None, [_i]),
-    "lb_gemm_set_pp_auto": (None, [_i]),
-    "lb_gemm_set_halo": (None, [_i]),
-    "lb_conv3x3_halo_f16": (_i, [C.POINTER(LbGemmParams), _vp]),
-    "lb_conv3x3_narrow_f16": (_i, [C.POINTER(LbGemmParams), _vp]),
-    "lb_upconv2x_halo_f16": (_i, [C.POINTER(LbGemmParams), _vp]),
-    "lb_conv_halo_set_persistent": (None, [_i]),
-    "lb_gemm_ch_stat_rows": (_i, [C.POINTER(LbGemmParams)]),
-    "lb_conv_halo_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
-    "lb_gemm_plan": (_i, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
-    "lb_conv_plan": (_i, [C.POINTER(LbGemmParams), C.POINTER(LbConvPlan)]),
-    "lb_groupnorm_workspace_bytes": (_l, [_i, _i]),
-    "lb_groupnorm_set_l3_chunk": (None, [_l]),
-    "lb_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    "lb_groupnorm_from_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp]),
-    "lb_layernorm_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "lb_attn_fwd_d64": (_i, [C.POINTER(LbAttnParams), _vp]),
-    "lb_attn_fwd_d512": (_i, [C.POINTER(LbAttnParams), _vp]),
-    "lb_attn_set_tuning": (None, [_i]),
-    "lb_layernorm_set_form": (None, [_i]),
-    "lb_groupnorm_set_fused": (None, [_i]),
-    "lb_groupnorm_plan": (_i, [_i, _i, _i, _i]),
-    "lb_softmax_rows_f16": (_i, [_vp, _i, _i, _i, _f, _vp]),
-    "lb_sinusoid_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
-    "lb_copy_cols_f16": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _vp]),
-    "lb_cast_f16_to_f32": (_i, [_vp, _vp, _l, _vp]),
-    "lb_cast_f32_to_f16": (_i, [_vp, _vp, _l, _f, _vp]),
-    "lb_nchw_to_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "lb_nhwc_to_nchw_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "lb_postprocess_u8": (_i, [_vp, _vp, _l, _i, _i, _vp]),
-    "lb_lpips_prep_u8": (_i, [_vp, _vp, _l, _vp]),
-    "lb_maxpool3s2_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "lb_lpips_tap": (_i, [c_void_pp, c_void_pp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "lb_fill_f32": (_i, [_vp, _l, _f, _vp]),
-    "lb_embed_tokens_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "lb_frames_lerp_u8": (_i, [_vp, _vp, _vp, _vp, _l, _l, _vp]),
-    "lb_gather_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "lb_copy_d2d": (_i, [_vp, _vp, _l, _vp]),
-    "lb_jpeg_dct_quant_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "lb_jpeg_coefficient_count": (_l, [_i, _i, _i, _i]),
-    "lb_jpeg_entropy": (_i, [_vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _vp]),
-    "lb_jpeg_workspace_bytes": (_l, [_i, _i, _i, _i]),
-    "lb_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
-    "lb_program_create": (_vp, []),
-    "lb_program_destroy": (None, [_vp]),
-    "lb_program_begin_record": (_i, [_vp]),
-    "lb_program_end_record": (_i, [_vp]),
-    "lb_program_recording": (_i, []),
-    "lb_program_num_ops": (_i, [_vp]),
-    "lb_program_op_name": (C.c_char_p, [_vp, _i]),
-    "lb_program_run": (_i, [_vp, _vp]),
-    "lb_program_run_range": (_i, [_vp, _i, _i, _vp]),
-    "lb_program_instantiate": (_i, [_vp]),
-    "lb_program_launch": (_i, [_vp, _vp]),
-    "lb_program_time_ops": (_i, [_vp, _vp, C.POINTER(C.c_float)]),
+    "lb_version": (_i, [], _V),
+    "lb_last_error_string": (C.c_char_p, [], _V),
+    "lb_device_info": (_i, [_i, _pi, _pl, C.c_char_p, _i], _S),
+    "lb_slerp_pairs_f16": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp], _L),
+    "lb_slerp_pairs_f32": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp], _L),
+    "lb_slerp_pairs_f64": (_i, [c_void_pp, c_void_pp, c_void_pp, C.POINTER(_d), _i, _l, _vp], _L),
+    "lb_slerp_batched_f16": (_i, [_vp, _vp, _vp, _vp, _l, _l, _vp], _L),
+    "lb_slerp_strided_f16": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _l, _vp], _L),
+    "lb_lerp_f16": (_i, [_vp, _vp, _vp, _l, _d, _vp], _L),
+    "lb_lerp_f32": (_i, [_vp, _vp, _vp, _l, _d, _vp], _L),
+    "lb_scale_model_input_f16": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp], _L),
+    "lb_euler_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp], _L),
+    "lb_ddim_step_f16": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp], _L),
+    "lb_counter_noise_f16": (_i, [_vp, _vp, _l, _i, _i, _vp], _L),
+    "lb_gemm_f16": (_i, [_pp, _vp], _L),
+    "lb_gemm_workspace_bytes": (_l, [_i, _i], _V),
+    "lb_gemm_set_tuning": (None, [_i, _i], _V),
+    "lb_gemm_set_depth": (None, [_i], _V),
+    "lb_gemm_set_variant": (None, [_i, _i], _V),
+    "lb_gemm_set_wide_store": (None, [_i], _V),
+    "lb_gemm_set_lean_epilogue": (None, [_i], _V),
+    "lb_gemm_set_t192_waves8": (None, [_i], _V),
+    "lb_gemm_set_kgroups": (None, [_i], _V),
+    "lb_gemm_pp_set_group": (None, [_i], _V),
+    "lb_gemm_set_pp_auto": (None, [_i], _V),
+    "lb_gemm_set_halo": (None, [_i], _V),
+    "lb_conv3x3_halo_f16": (_i, [_pp, _vp], _L),
+    "lb_conv3x3_narrow_f16": (_i, [_pp, _vp], _L),
+    "lb_upconv2x_halo_f16": (_i, [_pp, _vp], _L),
+    "lb_conv_halo_set_persistent": (None, [_i], _V),
+    "lb_gemm_ch_stat_rows": (_i, [_pp], _V),
+    "lb_conv_halo_plan": (None, [_pp, _pi, _pi, _pl, _pl], _V),
+    "lb_conv_halo_ksplit_plan": (None, [_pp, _pl, _pl, _pi], _V),
+    "lb_conv_halo_ksplit_workspace_bytes": (_l, [_pp], _V),
+    "lb_conv_halo_set_ksplit": (None, [_i, _i], _V),
+    "lb_conv_halo_gn_a_plan": (None, [_pp, _pi, _pi], _V),
+    "lb_conv_halo_set_gn_a": (None, [_i, _i], _V),
+    "lb_gemm_plan": (_i, [_pp, _pi, _pi, _pl], _S),
+    "lb_conv_plan": (_i, [_pp, C.POINTER(LbConvPlan)], _S),
+    "lb_groupnorm_workspace_bytes": (_l, [_i, _i], _V),
+    "lb_groupnorm_set_l3_chunk": (None, [_l], _V),
+    "lb_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp], _L),
+    "lb_groupnorm_from_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _vp], _L),
+    "lb_groupnorm_affine_from_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp], _L),
+    "lb_layernorm_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp], _L),
+    "lb_attn_fwd_d64": (_i, [C.POINTER(LbAttnParams), _vp], _L),
+    "lb_attn_fwd_d512": (_i, [C.POINTER(LbAttnParams), _vp], _L),
+    "lb_attn_set_tuning": (None, [_i], _V),
+    "lb_layernorm_set_form": (None, [_i], _V),
+    "lb_groupnorm_set_fused": (None, [_i], _V),
+    "lb_groupnorm_plan": (_i, [_i, _i, _i, _i], _V),
+    "lb_softmax_rows_f16": (_i, [_vp, _i, _i, _i, _f, _vp], _L),
+    "lb_sinusoid_f16": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp], _L),
+    "lb_copy_cols_f16": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _vp], _L),
+    "lb_cast_f16_to_f32": (_i, [_vp, _vp, _l, _vp], _L),
+    "lb_cast_f32_to_f16": (_i, [_vp, _vp, _l, _f, _vp], _L),
+    "lb_nchw_to_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp], _L),
+    "lb_nhwc_to_nchw_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp], _L),
+    "lb_postprocess_u8": (_i, [_vp, _vp, _l, _i, _i, _vp], _L),
+    "lb_lpips_prep_u8": (_i, [_vp, _vp, _l, _vp], _L),
+    "lb_maxpool3s2_nhwc_f16": (_i, [_vp, _vp, _i, _i, _i, _i, _vp], _L),
+    "lb_lpips_tap": (_i, [c_void_pp, c_void_pp, _vp, _vp, _vp, _i, _i, _i, _vp], _L),
+    "lb_fill_f32": (_i, [_vp, _l, _f, _vp], _L),
+    "lb_embed_tokens_f16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp], _L),
+    "lb_frames_lerp_u8": (_i, [_vp, _vp, _vp, _vp, _l, _l, _vp], _L),
+    "lb_gather_rows_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp], _L),
+    "lb_copy_d2d": (_i, [_vp, _vp, _l, _vp], _L),
+    "lb_jpeg_dct_quant_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp], _L),
+    "lb_jpeg_coefficient_count": (_l, [_i, _i, _i, _i], _V),
+    "lb_jpeg_entropy": (_i, [_vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _vp], _L),
+    "lb_jpeg_workspace_bytes": (_l, [_i, _i, _i, _i], _V),
+    "lb_resample_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp], _L),
+    "lb_program_create": (_vp, [], _V),
+    "lb_program_destroy": (None, [_vp], _V),
+    "lb_program_begin_record": (_i, [_vp], _S),
+    "lb_program_end_record": (_i, [_vp], _S),
+    "lb_program_recording": (_i, [], _V),
+    "lb_program_num_ops": (_i, [_vp], _V),
+    "lb_program_op_name": (C.c_char_p, [_vp, _i], _V),
+    "lb_program_run": (_i, [_vp, _vp], _S),
+    "lb_program_run_range": (_i, [_vp, _i, _i, _vp], _S),
+    "lb_program_instantiate": (_i, [_vp], _S),
+    "lb_program_launch": (_i, [_vp, _vp], _S),
+    "lb_program_time_ops": (_i, [_vp, _vp, C.POINTER(_f)], _S),
 }
 
-# exported only by study builds (-DLB_STUDY_BUILD, liblbhip_study.so): switches that change the arithmetic / the tile policy
+# exported only by study builds (-DLB_STUDY_BUILD, liblbhip_study.so): switches that change the arithmetic / the tile policy;
+# absent from the product library, so bound only where the loaded library has them
 STUDY_SIGNATURES = {
-    "lb_slerp_set_study": (None, [_i]),
-    "lb_gemm_set_policy": (None, [_i]),
-    "lb_conv_halo_set_study": (None, [_i]),
+    "lb_slerp_set_study": (None, [_i], _V),
+    "lb_gemm_set_policy": (None, [_i], _V),
+    "lb_conv_halo_set_study": (None, [_i], _V),
 }
-
-# host arithmetic and tuning switch of the K-split halo conv (LB_GEMM_HALO_KSPLIT): they launch nothing and take no stream, so they are
-# bound beside SIGNATURES - the table of what a program can record (tests/_replay.py holds one replay case per entry)
-HOST_SIGNATURES = {
-    "lb_conv_halo_ksplit_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
-    "lb_conv_halo_ksplit_workspace_bytes": (_l, [C.POINTER(LbGemmParams)]),
-    "lb_conv_halo_set_ksplit": (None, [_i, _i]),
-}
-
-# GroupNorm folded into the consuming 3x3 conv (LB_GEMM_GN_A, include/lb_hip_gn_a.h): the table launcher (checked like every
-# launcher; a program records it under its own name), the plan the emitter asks and the policy switch
-GN_A_SIGNATURES = {
-    "lb_groupnorm_affine_from_stats": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
-    "lb_conv_halo_gn_a_plan": (None, [C.POINTER(LbGemmParams), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "lb_conv_halo_set_gn_a": (None, [_i, _i]),
-}
-
-# counter-based sampler noise (include/lb_hip_noise.h): a launcher, checked like every launcher; a program records it under its
-# own name.  A table of its own because SIGNATURES is mirrored one to one by the replay registry of the program tests
-NOISE_SIGNATURES = {
-    "lb_counter_noise_f16": (_i, [_vp, _vp, _l, _i, _i, _vp]),
-}
-
-_NO_CHECK = {"lb_version", "lb_last_error_string", "lb_gemm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
-             "lb_groupnorm_workspace_bytes", "lb_groupnorm_set_l3_chunk", "lb_conv_halo_set_persistent", "lb_conv_halo_plan","lb_gemm_ch_stat_rows", "lb_conv_halo_set_study", "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue", "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_policy", "lb_gemm_set_halo", "lb_attn_set_tuning", "lb_layernorm_set_form", "lb_groupnorm_set_fused", "lb_groupnorm_plan", "lb_slerp_set_study", "lb_program_create",
-             "lb_program_destroy", "lb_program_recording", "lb_program_num_ops", "lb_program_op_name"}
 
 
 def _load():
@@ -212,32 +202,13 @@ def _wrap(name, fn):
 
 
 api = _Api()
-for _name, (_res, _args) in SIGNATURES.items():
+for _name, (_res, _args, _role) in {**SIGNATURES, **STUDY_SIGNATURES}.items():
+    if _name in STUDY_SIGNATURES and not hasattr(_lib, _name):
+        continue
     _fn = getattr(_lib, _name)          # AttributeError here == header/library mismatch
     _fn.restype = _res
     _fn.argtypes = _args
-    setattr(api, _name, _fn if _name in _NO_CHECK else _wrap(_name, _fn))
-for _name, (_res, _args) in HOST_SIGNATURES.items():
-    _fn = getattr(_lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-    setattr(api, _name, _fn)
-for _name, (_res, _args) in GN_A_SIGNATURES.items():
-    _fn = getattr(_lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-    setattr(api, _name, _wrap(_name, _fn) if _res is _i else _fn)
-for _name, (_res, _args) in NOISE_SIGNATURES.items():
-    _fn = getattr(_lib, _name)
-    _fn.restype = _res
-    _fn.argtypes = _args
-    setattr(api, _name, _wrap(_name, _fn))
-for _name, (_res, _args) in STUDY_SIGNATURES.items():
-    _fn = getattr(_lib, _name, None)
-    if _fn is not None:
-        _fn.restype = _res
-        _fn.argtypes = _args
-        setattr(api, _name, _fn)
+    setattr(api, _name, _fn if _role == _V else _wrap(_name, _fn))
 
 if os.environ.get("LB_GEMM_WIDE_STORE"):        # tuning experiments (tools/): 16-byte epilogue stores
     api.lb_gemm_set_wide_store(int(os.environ["LB_GEMM_WIDE_STORE"]))

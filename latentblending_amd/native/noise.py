@@ -1,7 +1,7 @@
 """Counter-based sampler noise: every value is a pure function of (which trajectory, which step, which element).
 
 This module is the DEFINITION of the stream - ``philox4x32_10`` and ``counter_normal_f16`` restate in numpy float64 what
-``lb_counter_noise_f16`` (csrc/noise.hip, contract: include/lb_hip_noise.h) evaluates on the device - and its CPU implementation.
+``lb_counter_noise_f16`` (csrc/noise.hip, contract: include/lb_hip.h) evaluates on the device - and its CPU implementation.
 
 Stream.  Element ``e`` of a draw takes word ``e % 4`` of Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2,
 3", SC'11; the Random123 construction) at counter ``{e // 4, ctr1, ctr2, ctr3}`` under key ``{key0, key1}``.  Words become normals in

@@ -1,6 +1,6 @@
 """An independent restatement of the counter-based noise stream for the tests (it imports nothing from latentblending_amd):
 Philox4x32-10 in plain Python integers (the Random123 construction: Salmon et al., SC'11), the pair-wise Box-Muller transform of
-include/lb_hip_noise.h in float64 with ``cos(pi t)`` / ``sin(pi t)`` written the plain way, and the SplitMix64 fold of the
+include/lb_hip.h in float64 with ``cos(pi t)`` / ``sin(pi t)`` written the plain way, and the SplitMix64 fold of the
 trajectory ids.  Scalar and slow on purpose where it defines something; ``words`` has a vectorised twin for the larger shapes,
 checked against the scalar form by the CPU tests."""
 import math

@@ -36,22 +36,14 @@ KNOBS = {
     "lb_attn_set_tuning": (0, 128),          # bit 7: 8-byte output stores
 }
 
-# exported symbols that are no stream launchers (nothing to record): the completeness test subtracts exactly these
-NOT_LAUNCHERS = {
-    "lb_version", "lb_last_error_string", "lb_device_info",
-    # plans and size queries
-    "lb_gemm_plan", "lb_conv_plan", "lb_conv_halo_plan", "lb_groupnorm_plan", "lb_gemm_ch_stat_rows", "lb_gemm_workspace_bytes",
-    "lb_groupnorm_workspace_bytes", "lb_jpeg_coefficient_count", "lb_jpeg_workspace_bytes",
-    # setters
-    "lb_gemm_set_tuning", "lb_gemm_set_depth", "lb_gemm_set_variant", "lb_gemm_set_wide_store", "lb_gemm_set_lean_epilogue",
-    "lb_gemm_set_t192_waves8", "lb_gemm_set_kgroups", "lb_gemm_pp_set_group", "lb_gemm_set_pp_auto", "lb_gemm_set_halo",
-    "lb_conv_halo_set_persistent", "lb_groupnorm_set_l3_chunk", "lb_attn_set_tuning", "lb_layernorm_set_form",
-    "lb_groupnorm_set_fused",
-}
-
 
 def is_program_api(name):
     return name.startswith("lb_program_")
+
+
+def table_launchers():
+    """What a program can record: the entries of lib.SIGNATURES whose role is ``launcher`` (one replay case each, at least)."""
+    return {name for name, sig in _lib().SIGNATURES.items() if sig[2] == "launcher"}
 
 
 # ====================================================================== cases ==================
@@ -574,6 +566,36 @@ def _halo_stats():
     return c.freeze()
 
 
+@case("halo_ch_stats_groupnorm_affine_from_stats", "lb_gemm_f16", "lb_groupnorm_affine_from_stats")
+def _halo_stats_affine():
+    """The same producer, and lb_groupnorm_affine_from_stats turning its statistics into the [B][C] (scale, shift) table of a conv
+    flagged LB_GEMM_GN_A.  Two samples: the smallest batch at which the per-sample indexing of the table can go wrong."""
+    o, l = _ops(), _lib()
+    c = Case("halo_ch_stats_groupnorm_affine_from_stats", ["lb_conv3x3_halo_f16", "lb_groupnorm_affine_from_stats"])
+    B, H, Wd, Cin, Cout = 2, 8, 96, 64, 64
+    x_d, w_d, b_d = _halo_operands(c, B, H, Wd, Cin, Cout, seed=221)
+    l.api.lb_gemm_set_halo(2)
+    try:
+        rows = o.conv_ch_stat_rows(B, H, Wd, Cin, Cout)
+    finally:
+        l.api.lb_gemm_set_halo(1)
+    assert rows > 0
+    st = c.guarded("ch_stats", Cout, B * rows * 2, B * rows * 2, F32).view(Cout, B * rows, 2)
+    y = c.guarded("conv_out", B * H * Wd, Cout, Cout + 8, F16).unflatten(0, (B, H, Wd))
+    table = c.guarded("table", B, Cout * 2, Cout * 2, F32, back_rows=2)
+    gamma, beta = c.dev(1 + 0.1 * _rnd(Cout, seed=225, dtype=F32)), c.dev(0.1 * _rnd(Cout, seed=226, dtype=F32))
+
+    def thunk():
+        l.api.lb_gemm_set_halo(2)
+        try:
+            o.gemm(x_d, w_d, bias=b_d, alpha=0.5, out=y, conv=dict(KH=3, KW=3, stride=1, pad=1), ch_stats=st, splitk_ws=False)
+        finally:
+            l.api.lb_gemm_set_halo(1)
+        o.groupnorm_affine_from_stats(gamma, beta, 32, 1e-6, st, rows, B, H * Wd, out=table)
+    c.thunk = thunk
+    return c.freeze()
+
+
 # ---------------------------------------------------------------------- norms -------------------
 def _groupnorm_case(name, B, HW, Cc, f32_in, fused):
     def build():
@@ -781,6 +803,29 @@ def _scheduler():
         params.copy_(o.step_params([(2.9, 1.8, 0.0, 5.0, -1.1)] * B, DEV))
         params_anc.copy_(o.step_params([(2.9, 1.3, 1.2, 5.0, -1.6)] * B, DEV))
         params_ddim.copy_(o.step_params([nd.step_row(7, 5.0)] * B, DEV))
+    c.mutate = mutate
+    return c.freeze()
+
+
+@case("counter_noise", "lb_counter_noise_f16")
+def _counter_noise():
+    """fp16 normals and the raw Philox words of the same rows.  3 x 2056 values are 771 sixteen-byte work items (1542 raw): no
+    multiple of a wave or a block.  The key / counter rows are read when the kernel RUNS (include/lb_hip.h): the protocol rewrites
+    them after the recording and requires every replay to draw the other noise."""
+    o = _ops()
+    n, per = 3, 2056
+    c = Case("counter_noise", ["lb_counter_noise_f16", "lb_counter_noise_f16"])
+    rows = c.inp(o.noise_rows([(0x243F6A88, 0x85A308D3, 7, 0, 0), (0x13198A2E, 0x03707344, 7, 0, 0), (0xA4093822, 0x299F31D0, 0, 1, 5)], DEV))
+    z = c.guarded("normals", n, per, per, F16, back_rows=2)
+    words = c.guarded("words", n, per, per, F32, back_rows=2)        # 32-bit words: compared as bits, never read as floats
+
+    def thunk():
+        o.counter_noise(rows, (n, per), out=z)
+        o.counter_noise(rows, (n, per), raw=True, out=words.view(I32))
+    c.thunk = thunk
+
+    def mutate():
+        rows.copy_(o.noise_rows([(0x243F6A88, 0x85A308D3, 8, 0, 0), (0x082EFA98, 0xEC4E6C89, 7, 0, 0), (0xA4093822, 0x299F31D0, 0, 1, 6)], DEV))
     c.mutate = mutate
     return c.freeze()
 

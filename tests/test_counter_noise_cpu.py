@@ -302,7 +302,7 @@ def test_launcher_refusals_and_recorded_name():
     import contextlib
     from latentblending_amd.hip import lib, ops
     api = lib.api
-    assert "lb_counter_noise_f16" in lib.NOISE_SIGNATURES and "lb_counter_noise_f16" not in lib.SIGNATURES
+    assert lib.SIGNATURES["lb_counter_noise_f16"][2] == "launcher"
     P0, P1 = 0x100000, 0x200000                                 # fake, 16-byte aligned device pointers: a recording never launches
 
     @contextlib.contextmanager

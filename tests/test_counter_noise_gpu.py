@@ -1,4 +1,4 @@
-"""``lb_counter_noise_f16`` on the device (csrc/noise.hip; contract: include/lb_hip_noise.h) and counter-based noise through the
+"""``lb_counter_noise_f16`` on the device (csrc/noise.hip; contract: include/lb_hip.h) and counter-based noise through the
 native loops.  The reference is tests/_counter_noise_ref.py - an independent restatement in Python integers and float64 - never
 native/noise.py.  Words must match exactly; values must equal ``fp16(float64 restatement)``, with the one allowance the float64
 evaluation leaves (device and host libm each within an ulp of float64: a value that close to an fp16 rounding boundary): at most

@@ -359,8 +359,10 @@ def test_c_abi_exports_every_declared_symbol():
     cdll = ctypes.CDLL(lib.LIB_PATH)
     missing = [n for n in declared if not hasattr(cdll, n)]
     assert not missing, f"declared in include/lb_hip.h but not exported: {missing}"
-    unbound = [n for n in declared if n not in lib.SIGNATURES]
+    unbound = sorted(declared - set(lib.SIGNATURES))
     assert not unbound, f"declared but not bound in hip/lib.py: {unbound}"
+    undeclared = sorted(set(lib.SIGNATURES) - declared)
+    assert not undeclared, f"bound in hip/lib.py but not declared in include/lb_hip.h: {undeclared}"
     assert lib.api.lb_version() >= 10000
     # struct layout guard: ctypes mirror == what a C compiler makes of the header
     import shutil

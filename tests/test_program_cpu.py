@@ -34,17 +34,21 @@ def names(h):
 
 # ---------------------------------------------------------------- registry completeness
 def test_every_stream_launcher_has_a_replay_case():
-    """A new launcher in lib.SIGNATURES without a case in tests/_replay.py fails here (so does a stale exclusion)."""
-    launchers = {n for n in lib.SIGNATURES if n not in RP.NOT_LAUNCHERS and not RP.is_program_api(n)}
-    assert RP.NOT_LAUNCHERS <= set(lib.SIGNATURES), sorted(RP.NOT_LAUNCHERS - set(lib.SIGNATURES))
+    """A new launcher in lib.SIGNATURES without a case in tests/_replay.py fails here, and so does a role that the signature's
+    shape contradicts."""
+    launchers = RP.table_launchers()
     missing = sorted(launchers - RP.registered_launchers())
     assert not missing, f"launchers without a replay case: {missing}"
     assert not RP.registered_launchers() - launchers, sorted(RP.registered_launchers() - launchers)
-    # the exclusions are what they claim to be: no stream argument last, or a setter / plan / query by name
-    for n in launchers:
-        assert lib.SIGNATURES[n][1][-1] is C.c_void_p and lib.SIGNATURES[n][0] is C.c_int, n
+    # a role is what the signature says: outside the program API, "int status, stream last" is a launcher and nothing else is
+    for n, (res, args, role) in lib.SIGNATURES.items():
+        assert role in ("launcher", "status", "value"), (n, role)
+        if not RP.is_program_api(n):
+            assert (role == "launcher") == (res is C.c_int and bool(args) and args[-1] is C.c_void_p), (n, role)
+    assert not any(RP.is_program_api(n) for n in launchers)
     assert len(RP.case_ids()) == len(set(RP.case_ids()))
-    assert set(RP.KNOBS) <= RP.NOT_LAUNCHERS
+    for n in RP.KNOBS:
+        assert lib.SIGNATURES[n][2] == "value" and lib.SIGNATURES[n][0] is None, n
 
 
 # ---------------------------------------------------------------- fake calls of every launcher
@@ -104,6 +108,7 @@ FAKE_CALLS = {
     "lb_scale_model_input_f16": lambda: api.lb_scale_model_input_f16(P[0], P[1], P[2], 64, 2, 0, None),
     "lb_euler_step_f16": lambda: api.lb_euler_step_f16(P[0], P[1], None, P[2], P[3], 64, 2, 0, 0, None),
     "lb_ddim_step_f16": lambda: api.lb_ddim_step_f16(P[0], P[1], P[2], P[3], 64, 2, 0, None),
+    "lb_counter_noise_f16": lambda: api.lb_counter_noise_f16(P[0], P[1], 64, 2, 0, None),
     "lb_gemm_f16": lambda: api.lb_gemm_f16(C.byref(gemm_params()), None),
     "lb_conv3x3_halo_f16": lambda: api.lb_conv3x3_halo_f16(C.byref(conv_params()), None),
     "lb_conv3x3_narrow_f16": lambda: api.lb_conv3x3_narrow_f16(C.byref(conv_params(N=8)), None),
@@ -111,6 +116,7 @@ FAKE_CALLS = {
     "lb_groupnorm_nhwc": lambda: api.lb_groupnorm_nhwc(P[0], P[1], P[2], P[3], P[4], 1, 64, 64, 64, 64, 32, 1e-5, 0, 0, None),
     "lb_groupnorm_from_stats": lambda: api.lb_groupnorm_from_stats(P[0], P[1], P[2], P[3], P[4], P[5], 1, 64, 64, 64, 64, 32, 1e-5, 0, 0,
                                                                    4, None),
+    "lb_groupnorm_affine_from_stats": lambda: api.lb_groupnorm_affine_from_stats(P[0], P[1], P[2], P[3], 2, 64, 64, 32, 1e-5, 4, None),
     "lb_layernorm_f16": lambda: api.lb_layernorm_f16(P[0], P[1], P[2], P[3], 4, 64, 64, 64, 1e-5, None),
     "lb_attn_fwd_d64": lambda: api.lb_attn_fwd_d64(C.byref(attn_params()), None),
     "lb_attn_fwd_d512": lambda: api.lb_attn_fwd_d512(C.byref(attn_params(D=512)), None),
