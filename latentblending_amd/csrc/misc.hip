@@ -212,6 +212,9 @@ __global__ void __launch_bounds__(256) lpips_tap_kernel(LpipsPairs pp, const flo
         const float ia = 1.f / (sqrtf(sa) + 1e-10f), ib = 1.f / (sqrtf(sb) + 1e-10f);
         float d = 0.f;
         for (int c = lane; c < C; c += 64) {
+            // both products rounded, then subtracted: contracted into fma(a, ia, -(b * ib)) the difference is not antisymmetric in
+            // (a, b) and not 0 for a == b, so d(a, b) != d(b, a) in the last bits and d(a, a) = 1e-17 instead of 0
+#pragma clang fp contract(off)
             const float t = (float)fa[(long)px * C + c] * ia - (float)fb[(long)px * C + c] * ib;
             d += lin[c] * t * t;
         }

@@ -30,6 +30,7 @@ import torch
 from ..hip import lib
 from ..hip.lib import api
 from .runtime import Arena, Emitter, Program, F16, F32, _stream
+from .unet import Mark, capture_marks
 
 MAX_TOKENS = 77
 
@@ -107,24 +108,47 @@ class NativeCLIPText:
         assert S == self.cfg.max_position_embeddings, f"expected {self.cfg.max_position_embeddings} tokens, got {S}"
         prog = self._programs.get(B)
         if prog is None:
-            prog = self._programs[B] = _CLIPProgram(self, B)
+            prog = self._programs[B] = self.build(B)
         return prog.run(ids)
+
+    def build(self, B: int, journal: bool = False) -> "_CLIPProgram":
+        """A program of its own for ``B`` prompts (``forward`` keeps one per batch size).  ``journal``: the program's arena keeps its
+        alloc / release journal (``Arena``); the recorded ops are the same."""
+        return _CLIPProgram(self, B, journal=journal)
 
 
 class _CLIPProgram:
-    def __init__(self, net: NativeCLIPText, B: int):
+    """One recorded tower forward for ``B`` prompts.  ``marks``: one ``Mark`` per emission unit - ``embed``; per layer ``L{i}.qkv``
+    (LayerNorm 1 + projection), ``L{i}.attn``, ``L{i}.out`` (+ residual), ``L{i}.fc1`` (LayerNorm 2 + projection + activation),
+    ``L{i}.fc2`` (+ residual); ``penultimate`` (the copy of the last layer's input, where it is emitted); ``pooled`` (EOS gather +
+    final LayerNorm + projection, towers with a projection only).  ``capture()`` fills ``taps``."""
+
+    def __init__(self, net: NativeCLIPText, B: int, journal: bool = False):
         cfg, dev = net.cfg, net.device
         self.net, self.B = net, B
         c, S, M = cfg.hidden_size, cfg.max_position_embeddings, B * cfg.max_position_embeddings
-        self.arena = Arena(dev)
+        self.arena = Arena(dev, journal=journal)
         self.em = Emitter(self.arena)
+        self.marks: List[Mark] = []
+        self.taps: Dict[str, torch.Tensor] = {}
         self.ids = torch.zeros(M, dtype=torch.int32, device=dev)
         self.eos_rows = torch.zeros(B, dtype=torch.int32, device=dev)
         self.penultimate = torch.zeros(B, S, c, dtype=F16, device=dev)
         self.pooled = torch.zeros(B, cfg.projection_dim, dtype=F16, device=dev) if cfg.projection_dim else None
         self.prog = Program("clip-text")
-        with self.prog.record():
+        with self.prog.record(), self.arena.clocked(self.prog):
             self._emit()
+
+    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
+        self.marks.append(Mark(name, kind, self.prog.name, self.prog.num_ops, out, tuple(inputs)))
+        return name
+
+    def capture(self) -> Dict[str, torch.Tensor]:
+        """Replay the program on the ids the buffers hold now (``run`` filled them), unit by unit, and keep a clone of every unit's
+        output in ``taps`` (fp16; the residual stream is updated in place, so a clone is the only way to see it).  Leaves
+        ``penultimate`` and ``pooled`` as a ``run`` would."""
+        self.taps = capture_marks({self.prog.name: self.prog}, self.marks)
+        return self.taps
 
     def _emit(self):
         net, cfg, em, ar, w = self.net, self.net.cfg, self.em, self.arena, self.net.w
@@ -134,27 +158,34 @@ class _CLIPProgram:
         h = ar.alloc((M, c))
         api.lb_embed_tokens_f16(self.ids.data_ptr(), w["tok"].data_ptr(), w["pos"].data_ptr(), h.data_ptr(), M, S, c,
                                 cfg.vocab_size, _stream())
+        at = self._mark("embed", "embed", h, "ids")
         for i in range(cfg.num_hidden_layers):
             if i == cfg.num_hidden_layers - 1:          # hidden_states[-2]: the input of the last layer
                 em.copy(self.penultimate, h)
+                self._mark("penultimate", "penultimate", self.penultimate, at)
             ln = ar.alloc((M, c))
             em.layernorm(h, ln, w[f"{i}.layer_norm1.w"], w[f"{i}.layer_norm1.b"], M=M, C_=c, eps=cfg.layer_norm_eps)
             qkv = ar.alloc((M, 3 * c))
             em.gemm(ln, w[f"{i}.qkv.w"], qkv, M=M, bias=w[f"{i}.qkv.b"])
             ar.release(ln)
+            self._mark(f"L{i}.qkv", "qkv", qkv, at)
             a = ar.alloc((M, c))
             em.attention(qkv.data_ptr(), qkv.data_ptr() + c * 2, qkv.data_ptr() + 2 * c * 2, a, B=B, H=H, Sq=S, Skv=S,
                          valid=S, ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, causal=True)
             ar.release(qkv)
+            self._mark(f"L{i}.attn", "attn", a, f"L{i}.qkv")
             em.gemm(a, w[f"{i}.out.w"], h, M=M, bias=w[f"{i}.out.b"], residual=h)
             ar.release(a)
+            at = self._mark(f"L{i}.out", "out", h, f"L{i}.attn", at)
             ln = ar.alloc((M, c))
             em.layernorm(h, ln, w[f"{i}.layer_norm2.w"], w[f"{i}.layer_norm2.b"], M=M, C_=c, eps=cfg.layer_norm_eps)
             ff = ar.alloc((M, cfg.intermediate_size))
             em.gemm(ln, w[f"{i}.fc1.w"], ff, M=M, bias=w[f"{i}.fc1.b"], flags=act)
             ar.release(ln)
+            self._mark(f"L{i}.fc1", "fc1", ff, at)
             em.gemm(ff, w[f"{i}.fc2.w"], h, M=M, bias=w[f"{i}.fc2.b"], residual=h)
             ar.release(ff)
+            at = self._mark(f"L{i}.fc2", "fc2", h, f"L{i}.fc1", at)
         if self.pooled is not None:                     # text_projection(final_layer_norm(last_hidden)[EOS row])
             eos = ar.alloc((B, c))
             api.lb_gather_rows_f16(h.data_ptr(), self.eos_rows.data_ptr(), eos.data_ptr(), B, c, c, _stream())
@@ -163,6 +194,7 @@ class _CLIPProgram:
             em.gemm(fin, w["proj"], self.pooled, M=B)
             ar.release(eos)
             ar.release(fin)
+            self._mark("pooled", "pooled", self.pooled, at, "ids")
         ar.release(h)
 
     def run(self, ids: torch.Tensor):
