@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch  # noqa: F401  (must be imported first: shares libamdhip64 with the extension)
 
@@ -66,6 +67,93 @@ GEMM_HALO_RAGGED = 1024      # opt-in ragged tiles of the 3x3 halo conv (include
 GEMM_HALO_KSPLIT = 4096     # opt-in K-split form of the 3x3 halo conv: partial = lb_conv_halo_ksplit_workspace_bytes (include/lb_hip.h)
 GEMM_GN_A = 8192            # A consumed through a GroupNorm affine table (gn_table / gn_silu): halo and narrow-N 3x3 convs (include/lb_hip.h)
 GEMM_C64 = 2048              # opt-in 64 -> 64 channel 3x3 conv with LDS-resident weights: that kernel or a refusal (include/lb_hip.h)
+
+
+class _ConvGeomFields(NamedTuple):
+    Hin: int
+    Win: int
+    Cin: int
+    KH: int
+    KW: int
+    stride: int
+    pad: int
+    ups: int
+    ldx: int
+    parity: Union[None, str, Tuple[int, int]]
+    Hout: int
+    Wout: int
+
+
+class ConvGeom(_ConvGeomFields):
+    """The geometry of one implicit-GEMM convolution over an NHWC input whose pixels are ``ldx`` elements apart (None: ``Cin``): a
+    frozen value.  ``ups``: the conv reads the nearest-2^ups upsampled input.  ``parity``: a sub-pixel upsampler conv on the low-res
+    grid that scatters into the 2H x 2W output - ``(py, px)`` one of the four, ``"all"`` the four in one launch (W stacked
+    [4][N][K]).  ``Hout`` / ``Wout`` are derived here and nowhere else: the rows and columns the launch computes per sample - of the
+    output, or of the low-res grid for a sub-pixel conv.  (A tuple underneath: the emitters build one per launch.)"""
+    __slots__ = ()
+
+    def __new__(cls, Hin: int, Win: int, Cin: int, KH: int, KW: int, stride: int = 1, pad: int = 0, ups: int = 0,
+                ldx: Optional[int] = None, parity=None):
+        if parity is None:
+            Hout, Wout = ((Hin << ups) + 2 * pad - KH) // stride + 1, ((Win << ups) + 2 * pad - KW) // stride + 1
+        else:
+            Hout, Wout = Hin, Win
+        return tuple.__new__(cls, (Hin, Win, Cin, KH, KW, stride, pad, ups, Cin if ldx is None else ldx, parity, Hout, Wout))
+
+    @classmethod
+    def conv3x3(cls, H: int, W: int, cin: int, stride: int = 1, ups: int = 0, ldx: Optional[int] = None) -> "ConvGeom":
+        return cls(H, W, cin, 3, 3, stride, 1, ups, ldx)
+
+    @classmethod
+    def subpixel(cls, H: int, W: int, cin: int, parity, ldx: Optional[int] = None) -> "ConvGeom":
+        return cls(H, W, cin, 2, 2, ldx=ldx, parity=parity)
+
+    @property
+    def scatter(self) -> int:
+        return 0 if self.parity is None else 2 if self.parity == "all" else 1
+
+    @property
+    def K(self) -> int:
+        return self.KH * self.KW * self.Cin
+
+    def M(self, B: int) -> int:
+        return B * self.Hout * self.Wout
+
+
+def gemm_params(*, M: int, N: int, K: int, ldw: int, ldc: int, lda: int = 0, A: Optional[int] = None, W: Optional[int] = None,
+                C: Optional[int] = None, conv: Optional[ConvGeom] = None, bias: Optional[int] = None, residual: Optional[int] = None,
+                ldr: int = 0, rowvec: Optional[int] = None, ld_rowvec: int = 0, rows_per_batch: int = 0, alpha: float = 1.0,
+                flags: int = 0, zero_page: Optional[int] = None, partial: Optional[int] = None, ln=None, ch_stats=None,
+                gn=None, make=LbGemmParams) -> LbGemmParams:
+    """THE constructor of the block lb_gemm_f16 and the plan calls read: integers in, block out - no tensor, no allocation, no
+    launch, no plan.  Pointers are addresses or None.  ``lda`` counts for a plain GEMM, ``conv`` for a convolution; ``ld_rowvec`` /
+    ``rows_per_batch`` only with a ``rowvec``.  ``ln`` = (colsum pointer, eps), ``ch_stats`` = (pointer, rows), ``gn`` = (table
+    pointer, silu) each set their flag bit (LB_GEMM_LN_A / LB_GEMM_CH_STATS / LB_GEMM_GN_A).  ``splitk`` and the reserved words stay
+    zero.  ``make``: what creates the empty block - ``ops.gemm`` passes its module's own ``LbGemmParams``, the name the replay tests
+    wrap to find (and later destroy) every block a wrapper built."""
+    p = make()
+    p.A, p.W, p.C, p.bias, p.residual, p.rowvec, p.partial = A, W, C, bias, residual, rowvec, partial
+    p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.ldr = M, N, K, lda, ldw, ldc, ldr
+    if rowvec is not None:
+        p.ld_rowvec, p.rows_per_batch = ld_rowvec, rows_per_batch
+    p.alpha, p.flags, p.zero_page = alpha, flags, zero_page
+    if conv is not None:
+        p.conv = 1
+        p.Hin, p.Win, p.Cin, p.KH, p.KW, p.stride, p.pad, p.ups, p.ldx, parity, p.Hout, p.Wout = conv
+        if parity is not None:
+            p.scatter = conv.scatter
+            if parity != "all":
+                p.sc_py, p.sc_px = int(parity[0]), int(parity[1])
+    if ln is not None:
+        p.flags |= GEMM_LN_A
+        p.ln_colsum, p.ln_eps = ln[0], float(ln[1])
+    if ch_stats is not None:
+        p.flags |= GEMM_CH_STATS
+        p.ch_stats, p.ch_stats_rows = ch_stats
+    if gn is not None:
+        p.flags |= GEMM_GN_A
+        p.gn_table, p.gn_silu = gn[0], int(bool(gn[1]))
+    return p
 
 _vp, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double
 _pp, _pi, _pl = C.POINTER(LbGemmParams), C.POINTER(_i), C.POINTER(_l)
@@ -228,10 +316,5 @@ def conv_plan(p: LbGemmParams) -> LbConvPlan:
 def conv_probe(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, flags: int = 0, zero_page: int = 64) -> LbGemmParams:
     """The parameter block of a 3x3 / stride 1 / pad 1 conv (``ks`` = 3) or a one-launch sub-pixel upsampler conv (``ks`` = 2) of
     this geometry, for the plan calls: host arithmetic only reads whether ``zero_page`` is set."""
-    p = LbGemmParams()
-    p.flags = flags
-    p.conv, p.M, p.N, p.K = 1, B * H * W, cout, ks * ks * cin
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = H, W, H, W, cin, ks, ks, 1, cin
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
-    p.zero_page = zero_page
-    return p
+    g = ConvGeom.conv3x3(H, W, cin) if ks == 3 else ConvGeom(H, W, cin, ks, ks, parity="all")
+    return gemm_params(M=g.M(B), N=cout, K=g.K, ldw=0, ldc=0, conv=g, alpha=0.0, flags=flags, zero_page=zero_page)

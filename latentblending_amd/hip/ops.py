@@ -292,30 +292,19 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias=None, residual=None, rowvec=None
     ``workspace``: caller-owned fp32 split-K slabs (>= lb_gemm_workspace_bytes(M, N) bytes) instead of a temporary one.
     ``conv``: dict(KH, KW, stride, pad, ups) for an implicit-GEMM convolution.
     ``ln`` = (colsum [N] fp32, eps): LayerNorm over A's columns folded into the GEMM (see ``fold_layernorm``)."""
-    p = LbGemmParams()
     N, K = W.shape
     dev = A.device
+    geom = None
     if conv is not None:
         B, H, Wd, Cin = A.shape
-        ups = int(conv.get("ups", 0))
-        kh, kw, st, pad = conv["KH"], conv["KW"], conv.get("stride", 1), conv.get("pad", 0)
-        hout = ((H << ups) + 2 * pad - kh) // st + 1
-        wout = ((Wd << ups) + 2 * pad - kw) // st + 1
-        Mv = B * hout * wout
-        p.conv, p.Hin, p.Win, p.Cin, p.Hout, p.Wout = 1, H, Wd, Cin, hout, wout
-        p.KH, p.KW, p.stride, p.pad, p.ups, p.ldx = kh, kw, st, pad, ups, A.stride(2)
-        out_shape = (B, hout, wout)
-        if "parity" in conv:                          # sub-pixel upsampling conv: caller supplies `out`
-            if conv["parity"] == "all":
-                p.scatter = 2                         # W = parity 0 of a stacked [4][N][K] tensor
-            else:
-                p.scatter, p.sc_py, p.sc_px = 1, int(conv["parity"][0]), int(conv["parity"][1])
-            hout, wout = H, Wd
-            Mv = B * H * Wd
-            p.Hout, p.Wout = H, Wd
+        geom = lib.ConvGeom(H, Wd, Cin, conv["KH"], conv["KW"], stride=conv.get("stride", 1), pad=conv.get("pad", 0),
+                            ups=int(conv.get("ups", 0)), ldx=A.stride(2), parity=conv.get("parity"))
+        if geom.parity is not None and out is None:
+            raise ValueError("gemm: a sub-pixel upsampling conv scatters into a [B, 2H, 2W, N] `out` the caller supplies")
+        Mv = geom.M(B)
+        out_shape = (B, geom.Hout, geom.Wout)
     else:
         Mv = M if M is not None else A.shape[0]
-        p.lda = A.stride(0)
         out_shape = (Mv,)
     n_out = N // 2 if flags & lib.GEMM_GEGLU else N
     if out is None:
@@ -324,23 +313,6 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias=None, residual=None, rowvec=None
             out = torch.empty(n_out, Mv, dtype=odt, device=dev)
         else:
             out = torch.empty(out_shape + (n_out,), dtype=odt, device=dev)
-    p.A, p.W, p.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
-    p.bias, p.residual, p.rowvec = _ptr(bias), _ptr(residual), _ptr(rowvec)
-    p.M, p.N, p.K, p.ldw = Mv, N, K, W.stride(0)
-    p.ldc = out.stride(0) if (flags & lib.GEMM_TRANS_OUT) else out.stride(-2)
-    if residual is not None:
-        p.ldr = residual.stride(-2)
-    if rowvec is not None:
-        p.ld_rowvec, p.rows_per_batch = rowvec.stride(0), rows_per_batch
-    p.alpha, p.flags = alpha, flags
-    zp = zero_page(dev)
-    p.zero_page = zp.data_ptr()
-    if ln is not None:
-        p.flags |= lib.GEMM_LN_A
-        p.ln_colsum, p.ln_eps = ln[0].data_ptr(), float(ln[1])
-    if ch_stats is not None:                          # halo-tile convs only: GroupNorm statistics of the stored output
-        p.flags |= lib.GEMM_CH_STATS
-        p.ch_stats, p.ch_stats_rows = ch_stats.data_ptr(), ch_stats.shape[1]      # [N][B * rows][2] fp32
     ws = None
     if splitk_ws and not (flags & lib.GEMM_GEGLU) and ln is None:
         ws = workspace
@@ -348,7 +320,14 @@ def gemm(A: torch.Tensor, W: torch.Tensor, bias=None, residual=None, rowvec=None
             _own_buffer("gemm", "split-K `workspace` (or splitk_ws=False)")
             ws = torch.empty(api.lb_gemm_workspace_bytes(Mv, N) // 4, dtype=F32, device=dev)
         assert ws.numel() * ws.element_size() >= api.lb_gemm_workspace_bytes(Mv, N), "gemm: split-K workspace too small"
-        p.partial = ws.data_ptr()
+    p = lib.gemm_params(
+        A=A.data_ptr(), W=W.data_ptr(), C=out.data_ptr(), M=Mv, N=N, K=K, lda=A.stride(0) if conv is None else 0, ldw=W.stride(0),
+        ldc=out.stride(0) if (flags & lib.GEMM_TRANS_OUT) else out.stride(-2), conv=geom, bias=_ptr(bias), residual=_ptr(residual),
+        ldr=residual.stride(-2) if residual is not None else 0, rowvec=_ptr(rowvec),
+        ld_rowvec=rowvec.stride(0) if rowvec is not None else 0, rows_per_batch=rows_per_batch, alpha=alpha, flags=flags,
+        zero_page=zero_page(dev).data_ptr(), partial=_ptr(ws), ln=None if ln is None else (ln[0].data_ptr(), ln[1]),
+        # ch_stats: halo-tile convs only, the GroupNorm statistics of the stored output, [N][B * rows][2] fp32
+        ch_stats=None if ch_stats is None else (ch_stats.data_ptr(), ch_stats.shape[1]), make=LbGemmParams)
     if conv is not None and conv.get("halo"):         # experimental halo-tile 3x3 kernel (csrc/conv3_halo.hip)
         api.lb_conv3x3_halo_f16(C.byref(p), stream_ptr())
     else:

@@ -56,13 +56,11 @@ class NativeLPIPS:
                 pooled = torch.empty(N, ho, wo, cin, dtype=F16, device=self.device)
                 api.lb_maxpool3s2_nhwc_f16(h.data_ptr(), pooled.data_ptr(), N, hh, ww, cin, _stream())
                 h, hh, ww = pooled, ho, wo
-            ho, wo = (hh + 2 * pad - k) // stride + 1, (ww + 2 * pad - k) // stride + 1
+            g = lib.ConvGeom(hh, ww, _pad(cin, 8), k, k, stride=stride, pad=pad)
+            ho, wo = g.Hout, g.Wout
             out = torch.empty(N, ho, wo, cout, dtype=F16, device=self.device)
-            cin_p = _pad(cin, 8)
-            self.em.gemm(h, self.w[f"net.conv{i + 1}.weight"], out, M=N * ho * wo, bias=self.w[f"net.conv{i + 1}.bias"],
-                         flags=lib.GEMM_RELU,
-                         conv=dict(Hin=hh, Win=ww, Cin=cin_p, Hout=ho, Wout=wo, KH=k, KW=k, stride=stride, pad=pad,
-                                   ups=0, ldx=cin_p))
+            self.em.gemm(h, self.w[f"net.conv{i + 1}.weight"], out, M=g.M(N), bias=self.w[f"net.conv{i + 1}.bias"],
+                         flags=lib.GEMM_RELU, conv=g)
             taps.append(out.view(N, ho * wo, cout))
             h, hh, ww, cin = out, ho, wo, cout
         return taps

@@ -261,7 +261,7 @@ class Emitter:
     def gemm(self, A: torch.Tensor, W: torch.Tensor, out: torch.Tensor, *, M: int, bias=None,
              residual=None, rowvec=None, rows_per_batch: int = 0, flags: int = 0, alpha: float = 1.0,
              lda: Optional[int] = None, ldc: Optional[int] = None, ldr: Optional[int] = None,
-             ld_rowvec: Optional[int] = None, conv: Optional[dict] = None, splitk: bool = True,
+             ld_rowvec: Optional[int] = None, conv: Optional[lib.ConvGeom] = None, splitk: bool = True,
              ln: Optional[Tuple[torch.Tensor, float]] = None, ch_stats: Optional[torch.Tensor] = None,
              gn: Optional["GnOperand"] = None):
         """``ln`` = (colsum [N] fp32, eps): A is consumed through a LayerNorm folded into this GEMM (LB_GEMM_LN_A; W and
@@ -269,20 +269,16 @@ class Emitter:
 
         ``gn`` = what ``gn_operand`` returned for this very conv (A = the raw tensor): the conv consumes GroupNorm(A), either through
         the affine table (LB_GEMM_GN_A) or from the scratch buffer the GroupNorm launch filled; both go back to the arena here."""
-        p = self._gemm_params(A, W, out, M=M, bias=bias, residual=residual, rowvec=rowvec, rows_per_batch=rows_per_batch, flags=flags,
-                              alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec, conv=conv, ln=ln, ch_stats=ch_stats)
+        fold = gn is not None and gn.table is not None      # (the fold was decided by gn_operand; a flagged conv is never split along K)
+        p = self._gemm_params(A if gn is None or fold else gn.scratch, W, out, M=M, bias=bias, residual=residual, rowvec=rowvec,
+                              rows_per_batch=rows_per_batch, flags=flags, alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec,
+                              conv=conv, ln=ln, ch_stats=ch_stats, gn=(gn.table, gn.args["silu"]) if fold else None)
         N, K = W.shape
         n_out = N // 2 if flags & lib.GEMM_GEGLU else N
         if splitk and not (flags & lib.GEMM_GEGLU) and ln is None:
             p.partial = _p(self._gemm_ws(M, N))
-        if gn is not None:
-            if gn.table is not None:            # (the fold was decided by gn_operand; a flagged conv is never split along K)
-                if gn.conv != _conv_key(p):
-                    raise RuntimeError("Emitter.gemm: the conv is not the one gn_operand planned the GroupNorm fold for")
-                p.flags |= lib.GEMM_GN_A
-                p.gn_table, p.gn_silu = gn.table.data_ptr(), int(bool(gn.args["silu"]))
-            else:
-                p.A = gn.scratch.data_ptr()
+        if fold and gn.conv != _conv_key(p):
+            raise RuntimeError("Emitter.gemm: the conv is not the one gn_operand planned the GroupNorm fold for")
         if conv is not None:
             self._halo_ksplit(p, self._conv_plan(p))
         api.lb_gemm_f16(C.byref(p), _stream())
@@ -295,7 +291,7 @@ class Emitter:
                               "bytes": mult * 2.0 * (N * K + M * n_out) + (2.0 * M * K if conv is None else 0.0)})
         return out
 
-    def gn_operand(self, x: torch.Tensor, W: torch.Tensor, *, M: int, conv: dict, flags: int = 0, has_residual: bool = False,
+    def gn_operand(self, x: torch.Tensor, W: torch.Tensor, *, M: int, conv: lib.ConvGeom, flags: int = 0, has_residual: bool = False,
                    **gn) -> "GnOperand":
         """Emit the GroupNorm side of "3x3 conv of GroupNorm(x)" NOW and return the operand for the conv's ``gemm(x, ..., gn=...)``.
         ``gn`` = the keyword arguments of ``groupnorm`` plus gamma / beta.  Where the library's plan fuses (the GN_A part of the conv's
@@ -320,38 +316,22 @@ class Emitter:
         return op
 
     def _gemm_params(self, A, W, out, *, M, bias=None, residual=None, rowvec=None, rows_per_batch=0, flags=0, alpha=1.0, lda=None,
-                     ldc=None, ldr=None, ld_rowvec=None, conv=None, ln=None, ch_stats=None) -> LbGemmParams:
-        """The parameter block ``gemm`` launches, before anything is planned for it: no workspace, none of the emitter's opt-in bits."""
-        p = LbGemmParams()
+                     ldc=None, ldr=None, ld_rowvec=None, conv=None, ln=None, ch_stats=None, gn=None) -> LbGemmParams:
+        """The parameter block ``gemm`` launches, before anything is planned for it: no workspace, none of the emitter's opt-in bits.
+        Leading dimensions default to dense; ``gn`` = (affine table, silu): LB_GEMM_GN_A."""
         N, K = W.shape
-        p.A, p.W, p.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
-        p.bias, p.residual, p.rowvec = _p(bias), _p(residual), _p(rowvec)
-        p.M, p.N, p.K, p.ldw = M, N, K, W.stride(0)
         n_out = N // 2 if flags & lib.GEMM_GEGLU else N
-        if conv is not None:
-            p.conv = 1
-            for k in ("Hin", "Win", "Cin", "Hout", "Wout", "KH", "KW", "stride", "pad", "ups", "ldx"):
-                setattr(p, k, int(conv[k]))
-            if conv.get("parity") == "all":            # all four sub-pixel convs in ONE halo-kernel launch (W stacked [4][N][K])
-                p.scatter = 2
-            elif "parity" in conv:                     # one sub-pixel upsampling conv
-                p.scatter, p.sc_py, p.sc_px = 1, int(conv["parity"][0]), int(conv["parity"][1])
-        else:
-            p.lda = lda if lda is not None else K
-        p.ldc = ldc if ldc is not None else (M if flags & lib.GEMM_TRANS_OUT else n_out)
-        p.ldr = ldr if ldr is not None else n_out
-        if rowvec is not None:
-            p.ld_rowvec, p.rows_per_batch = ld_rowvec if ld_rowvec is not None else N, rows_per_batch
-        p.alpha, p.flags = alpha, flags
-        p.zero_page = self.zero_page.data_ptr()
-        if ln is not None:
-            p.flags |= lib.GEMM_LN_A
-            p.ln_colsum, p.ln_eps = ln[0].data_ptr(), float(ln[1])
         if ch_stats is not None:       # halo-tile convs only (see halo_stat_rows): GroupNorm statistics of the stored output
             assert conv is not None and ch_stats.dtype == F32
-            p.flags |= lib.GEMM_CH_STATS
-            p.ch_stats, p.ch_stats_rows = ch_stats.data_ptr(), ch_stats.shape[1]    # [N][B * rows][2]: checked by the launcher
-        return p
+        return lib.gemm_params(
+            A=A.data_ptr(), W=W.data_ptr(), C=out.data_ptr(), M=M, N=N, K=K, ldw=W.stride(0), conv=conv,
+            lda=0 if conv is not None else lda if lda is not None else K,
+            ldc=ldc if ldc is not None else (M if flags & lib.GEMM_TRANS_OUT else n_out), bias=_p(bias), residual=_p(residual),
+            ldr=ldr if ldr is not None else n_out, rowvec=_p(rowvec), ld_rowvec=ld_rowvec if ld_rowvec is not None else N,
+            rows_per_batch=rows_per_batch, alpha=alpha, flags=flags, zero_page=self.zero_page.data_ptr(),
+            ln=None if ln is None else (ln[0].data_ptr(), ln[1]),
+            ch_stats=None if ch_stats is None else (ch_stats.data_ptr(), ch_stats.shape[1]),      # [N][B * rows][2]: checked by the launcher
+            gn=None if gn is None else (gn[0].data_ptr(), gn[1]))
 
     def halo_stat_rows(self, B: int, H: int, W: int, cin: int, cout: int, ks: int = 3) -> int:
         """Rows per sample of the LB_GEMM_CH_STATS buffer ([cout][B * rows] float2, channel-major) if a 3x3 conv (ks = 3) or a one-launch
@@ -367,6 +347,21 @@ class Emitter:
         """The halo kernel's sub-pixel form takes this upsampler conv in one launch (else: four implicit-GEMM launches): the library
         says whether it can, the emitter asks for a grid of at least 96 blocks."""
         return lib.conv_plan(lib.conv_probe(B, H, W, cin, cout, 2)).halo_kind == 2 and B * (H * W // 256) * 4 * ((cout + 127) // 128) >= 96
+
+    def upconv(self, x: torch.Tensor, weights: dict, stem: str, out: torch.Tensor, *, B: int, H: int, W: int, c: int, bias,
+               flags: int = 0, alpha: float = 1.0, ch_stats: Optional[torch.Tensor] = None):
+        """nearest-2x upsample + 3x3 conv (c -> c) of x [B, H, W, c] into out [B, 2H, 2W, c], as sub-pixel 2x2 convs on the low-res
+        grid: ONE halo-kernel launch of the four stacked kernels ``weights[stem + ".sub4"]`` where ``upconv_one_launch`` says so, else
+        four implicit-GEMM launches of ``weights[stem + ".sub{py}{px}"]``.  ``ch_stats``: what ``halo_stat_rows(..., ks=2)`` sized -
+        only the one-launch form leaves statistics."""
+        one = self.upconv_one_launch(B, H, W, c, c)
+        assert one or ch_stats is None
+        forms = [("all", weights[f"{stem}.sub4"][0])] if one else \
+            [((py, px), weights[f"{stem}.sub{py}{px}"]) for py in (0, 1) for px in (0, 1)]
+        for parity, wt in forms:
+            self.gemm(x, wt, out, M=B * H * W, bias=bias, ldc=c, flags=flags, alpha=alpha, ch_stats=ch_stats,
+                      conv=lib.ConvGeom.subpixel(H, W, c, parity))
+        return out
 
     def groupnorm(self, x: torch.Tensor, out: torch.Tensor, gamma, beta, *, B: int, HW: int, C_: int,
                   eps: float, silu: bool, groups: int = 32, ldx: Optional[int] = None,

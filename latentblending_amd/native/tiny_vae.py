@@ -193,14 +193,14 @@ class TinyVAEProgram:
     def _conv64(self, x, name, B, hin, win, *, ups=0, relu=True, residual=None):
         """One 64 -> 64 conv (on the nearest-2x upsampled map when ``ups``): flagged where the rule says so."""
         w = self.net.w
-        ho, wo = hin << ups, win << ups
+        g = lib.ConvGeom.conv3x3(hin, win, 64, ups=ups)
+        ho, wo = g.Hout, g.Wout
         out = self.arena.alloc((B, ho, wo, 64))
         flags = lib.GEMM_RELU if relu else 0
         if self.c64 and use_c64(B, ho, wo):
             flags |= lib.GEMM_C64
             self.c64_launches += 1
-        self.em.gemm(x, w[name + ".weight"], out, M=B * ho * wo, bias=w[name + ".bias"], residual=residual, flags=flags, splitk=False,
-                     conv=dict(Hin=hin, Win=win, Cin=64, Hout=ho, Wout=wo, KH=3, KW=3, stride=1, pad=1, ups=ups, ldx=64))
+        self.em.gemm(x, w[name + ".weight"], out, M=g.M(B), bias=w[name + ".bias"], residual=residual, flags=flags, splitk=False, conv=g)
         return out
 
     def _emit(self):
@@ -215,7 +215,7 @@ class TinyVAEProgram:
             if kind == "in":
                 h = ar.alloc((B, sh, sw, 64))
                 em.gemm(z8, w[p + ".weight"], h, M=B * sh * sw, bias=w[p + ".bias"], flags=lib.GEMM_RELU, splitk=False,
-                        conv=dict(Hin=sh, Win=sw, Cin=lc_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=lc_p))
+                        conv=lib.ConvGeom.conv3x3(sh, sw, lc_p))
                 ar.release(z8)
             elif kind == "block":
                 a = self._conv64(h, p + ".conv.0", B, sh, sw)
@@ -232,7 +232,7 @@ class TinyVAEProgram:
                 sh, sw = 2 * sh, 2 * sw
             else:
                 em.gemm(h, w[p + ".weight"], self.image_f32, M=B * sh * sw, bias=w[p + ".bias"], flags=lib.GEMM_OUT_F32, splitk=False,
-                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+                        conv=lib.ConvGeom.conv3x3(sh, sw, 64))
                 ar.release(h)
         api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw, _pad(cfg.out_channels, 4), 1, _stream())
 
@@ -346,7 +346,7 @@ class TinyEncoderProgram:
             flags |= lib.GEMM_C64
             self.c64_launches += 1
         self.em.gemm(x, wt[name + ".weight"], out, M=B * h * w, bias=wt[name + ".bias"], residual=residual, flags=flags, splitk=False,
-                     conv=dict(Hin=h, Win=w, Cin=64, Hout=h, Wout=w, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+                     conv=lib.ConvGeom.conv3x3(h, w, 64))
         return out
 
     def _emit(self):
@@ -359,7 +359,7 @@ class TinyEncoderProgram:
             if kind == "in":
                 h = ar.alloc((B, sh, sw, 64))
                 em.gemm(self.x_in, w[p + ".weight"], h, M=B * sh * sw, bias=w[p + ".bias"], flags=0, splitk=False,
-                        conv=dict(Hin=sh, Win=sw, Cin=self.pc_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=self.pc_p))
+                        conv=lib.ConvGeom.conv3x3(sh, sw, self.pc_p))
             elif kind == "block":
                 a = self._conv64(h, p + ".conv.0", B, sh, sw)
                 b = self._conv64(a, p + ".conv.2", B, sh, sw)
@@ -369,16 +369,16 @@ class TinyEncoderProgram:
                 ar.release(h)
                 h = o
             elif kind == "down":
-                ho, wo = sh // 2, sw // 2
+                g = lib.ConvGeom.conv3x3(sh, sw, 64, stride=2)
+                ho, wo = g.Hout, g.Wout
                 o = ar.alloc((B, ho, wo, 64))
-                em.gemm(h, w[p + ".weight"], o, M=B * ho * wo, flags=0, splitk=False,
-                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=ho, Wout=wo, KH=3, KW=3, stride=2, pad=1, ups=0, ldx=64))
+                em.gemm(h, w[p + ".weight"], o, M=g.M(B), flags=0, splitk=False, conv=g)
                 ar.release(h)
                 h, sh, sw = o, ho, wo
             else:
                 o = ar.alloc((B, sh, sw, lc_p))
                 em.gemm(h, w[p + ".weight"], o, M=B * sh * sw, bias=w[p + ".bias"], flags=0, splitk=False,
-                        conv=dict(Hin=sh, Win=sw, Cin=64, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=64))
+                        conv=lib.ConvGeom.conv3x3(sh, sw, 64))
                 ar.release(h)
                 api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.latents.data_ptr(), B, cfg.latent_channels, sh * sw, lc_p, _stream())
                 ar.release(o)

@@ -360,30 +360,20 @@ class UNetProgram:
     def _conv(self, x, name, B, H, W, cin, cout, *, stride=1, ups=0, rowvec=None, ld_rowvec=None,
               residual=None, out=None, flags=0, k=3, pad=1):
         em, w = self.em, self.net.w
-        he, we = H << ups, W << ups
-        ho, wo = (he + 2 * pad - k) // stride + 1, (we + 2 * pad - k) // stride + 1
         cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
+        g = lib.ConvGeom(H, W, cin_p, k, k, stride=stride, pad=pad, ups=ups)
+        ho, wo = g.Hout, g.Wout
         if out is None:
             out = self.arena.alloc((B, ho, wo, cout_p), F32 if flags & lib.GEMM_OUT_F32 else F16)
-        em.gemm(x, w[name + ".weight"], out, M=B * ho * wo, bias=w[name + ".bias"], residual=residual,
-                rowvec=rowvec, rows_per_batch=ho * wo, ld_rowvec=ld_rowvec, flags=flags,
-                conv=dict(Hin=H, Win=W, Cin=cin_p, Hout=ho, Wout=wo, KH=k, KW=k, stride=stride, pad=pad,
-                          ups=ups, ldx=cin_p))
+        em.gemm(x, w[name + ".weight"], out, M=g.M(B), bias=w[name + ".bias"], residual=residual,
+                rowvec=rowvec, rows_per_batch=ho * wo, ld_rowvec=ld_rowvec, flags=flags, conv=g)
         return out, ho, wo
 
     def _upconv(self, x, name, B, H, W, c):
-        """nearest-2x upsample + 3x3 conv as four sub-pixel 2x2 convs scattered into the 2H x 2W output."""
-        em, w = self.em, self.net.w
+        """nearest-2x upsample + 3x3 conv as sub-pixel 2x2 convs scattered into the 2H x 2W output (``Emitter.upconv``)."""
+        w = self.net.w
         out = self.arena.alloc((B, 2 * H, 2 * W, c))
-        if em.upconv_one_launch(B, H, W, c, c):
-            em.gemm(x, w[f"{name}.weight.sub4"][0], out, M=B * H * W, bias=w[name + ".bias"], ldc=c,
-                    conv=dict(Hin=H, Win=W, Cin=c, Hout=H, Wout=W, KH=2, KW=2, stride=1, pad=0, ups=0, ldx=c, parity="all"))
-            return out, 2 * H, 2 * W
-        for py in (0, 1):
-            for px in (0, 1):
-                em.gemm(x, w[f"{name}.weight.sub{py}{px}"], out, M=B * H * W, bias=w[name + ".bias"], ldc=c,
-                        conv=dict(Hin=H, Win=W, Cin=c, Hout=H, Wout=W, KH=2, KW=2, stride=1, pad=0, ups=0, ldx=c,
-                                  parity=(py, px)))
+        self.em.upconv(x, w, name + ".weight", out, B=B, H=H, W=W, c=c, bias=w[name + ".bias"])
         return out, 2 * H, 2 * W
 
     def _resnet(self, x, p, B, H, W, cin, cout):

@@ -198,17 +198,16 @@ class VAEProgram:
         out._lb_chstats = (buf, rows)
         return buf
 
-    def _stream_conv_args(self, name, B, H, W, cin, residual):
-        sc = self.scaled
-        cin_p = _pad(cin, 8)
-        flags = 0 if sc else (lib.GEMM_OUT_F32 | (lib.GEMM_RES_F32 if residual else 0))
-        return flags, dict(Hin=H, Win=W, Cin=cin_p, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p)
+    def _stream_conv_args(self, H, W, cin, residual):
+        """(flags, geometry) of a stream conv: the one copy ``_gn_for_conv`` plans with and ``_stream_conv`` launches."""
+        flags = 0 if self.scaled else (lib.GEMM_OUT_F32 | (lib.GEMM_RES_F32 if residual else 0))
+        return flags, lib.ConvGeom.conv3x3(H, W, _pad(cin, 8))
 
     def _gn_for_conv(self, x, norm, silu, name, B, H, W, cin, *, residual=False):
         """The GroupNorm ``norm`` of ``x`` whose only consumer is the stream conv ``name``: emitted here (see ``Emitter.gn_operand``:
         the table kernel of a conv that applies the GroupNorm itself, or the GroupNorm launch as ever); pass the result to
         ``_stream_conv(x, name, ..., gn=...)``."""
-        flags, conv = self._stream_conv_args(name, B, H, W, cin, residual)
+        flags, conv = self._stream_conv_args(H, W, cin, residual)
         op = self.em.gn_operand(x, self.net.w[name + ".weight"], M=B * H * W, conv=conv, flags=flags, has_residual=residual,
                                 **self._gn_args(x, norm, B, H * W, cin, silu))
         self._gn_done(x)
@@ -221,12 +220,10 @@ class VAEProgram:
         cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
         if out is None:
             out = self.arena.alloc((B, H, W, cout_p), F16 if sc else F32)
-        flags = 0 if sc else (lib.GEMM_OUT_F32 | (lib.GEMM_RES_F32 if residual is not None else 0))
+        flags, conv = self._stream_conv_args(H, W, cin, residual is not None)
         st = self._stats_for(out, B, H, W, cin_p, cout_p) if stats else None
         self.em.gemm(x, w[name + ".weight"], out, M=B * H * W, bias=w[name + (".bias_s" if sc else ".bias")],
-                     residual=residual, flags=flags, alpha=STREAM_SCALE if sc else 1.0, ch_stats=st,
-                     conv=dict(Hin=H, Win=W, Cin=cin_p, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p),
-                     gn=gn)
+                     residual=residual, flags=flags, alpha=STREAM_SCALE if sc else 1.0, ch_stats=st, conv=conv, gn=gn)
         return out
 
     def _gn_args(self, x, name, B, HW, c, silu):
@@ -354,21 +351,10 @@ class VAEProgram:
                 h16, owned = self._stream_as_operand(h, B, sh, sw, c)
                 name = f"decoder.up_blocks.{ui}.upsamplers.0.conv"
                 up = ar.alloc((B, 2 * sh, 2 * sw, c), F16 if sc else F32)
-                one = em.upconv_one_launch(B, sh, sw, c, c)
-                if one:                     # all four sub-pixel convs in ONE launch of the halo kernel
-                    em.gemm(h16, w[f"{name}.weight.sub4"][0], up, M=B * sh * sw,
-                            bias=w[name + (".bias_s" if sc else ".bias")], ldc=c,
-                            flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE,
-                            ch_stats=self._stats_for(up, B, sh, sw, c, c, ks=2),
-                            conv=dict(Hin=sh, Win=sw, Cin=c, Hout=sh, Wout=sw, KH=2, KW=2, stride=1, pad=0,
-                                      ups=0, ldx=c, parity="all"))
-                for py in (() if one else (0, 1)):           # else: four 2x2 convs on the low-res grid
-                    for px in (0, 1):
-                        em.gemm(h16, w[f"{name}.weight.sub{py}{px}"], up, M=B * sh * sw,
-                                bias=w[name + (".bias_s" if sc else ".bias")], ldc=c,
-                                flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE,
-                                conv=dict(Hin=sh, Win=sw, Cin=c, Hout=sh, Wout=sw, KH=2, KW=2, stride=1, pad=0,
-                                          ups=0, ldx=c, parity=(py, px)))
+                # (statistics only where the four sub-pixel convs run as ONE launch of the halo kernel: else _stats_for gives None)
+                em.upconv(h16, w, name + ".weight", up, B=B, H=sh, W=sw, c=c, bias=w[name + (".bias_s" if sc else ".bias")],
+                          flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE,
+                          ch_stats=self._stats_for(up, B, sh, sw, c, c, ks=2))
                 if owned:
                     ar.release(h16)
                 ar.release(h)
@@ -376,8 +362,7 @@ class VAEProgram:
                 sh, sw = 2 * sh, 2 * sw
                 at = self._mark(name, "upsample", h, at)
             self.tap_names[f"up{ui}"] = at
-        cin_p = _pad(rev[-1], 8)
-        conv_out = dict(Hin=sh, Win=sw, Cin=cin_p, Hout=sh, Wout=sw, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin_p)
+        conv_out = lib.ConvGeom.conv3x3(sh, sw, _pad(rev[-1], 8))
         g = em.gn_operand(h, w["decoder.conv_out.weight"], M=B * sh * sw, conv=conv_out, flags=lib.GEMM_OUT_F32,
                           **self._gn_args(h, "decoder.conv_norm_out", B, sh * sw, rev[-1], True))
         self._gn_done(h)

@@ -84,10 +84,5 @@ def gn_a_plan(p):
 def host_conv_params(B, H, W, Cin, N, flags=0, ks=3):
     """Parameter block of a 3x3 (ks = 3) or one-launch sub-pixel (ks = 2) conv for the host-side plan / refusal checks: every
     pointer a launch needs is a non-null dummy (nothing is launched with them)."""
-    p = lib().LbGemmParams()
-    p.A = p.W = p.C = p.zero_page = 4096
-    p.M, p.N, p.K, p.ldw, p.ldc = B * H * W, N, ks * ks * Cin, ks * ks * Cin, N
-    p.conv, p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.ldx = 1, H, W, H, W, Cin, ks, ks, 1, Cin
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, 2)
-    p.alpha, p.flags = 1.0, flags
-    return p
+    g = lib().ConvGeom.conv3x3(H, W, Cin) if ks == 3 else lib().ConvGeom.subpixel(H, W, Cin, "all")
+    return lib().gemm_params(A=4096, W=4096, C=4096, zero_page=4096, M=g.M(B), N=N, K=g.K, ldw=g.K, ldc=N, conv=g, flags=flags)

@@ -58,25 +58,14 @@ def conv_params(x, w, out, *, bias=None, residual=None, rowvec=None, alpha=1.0, 
     l = lib()
     B, H, W, Cin = x.shape
     N = w.shape[0]
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    p = l.LbGemmParams()
-    p.A, p.W, p.C = x.data_ptr(), w.data_ptr(), out.data_ptr()
-    p.bias = None if bias is None else bias.data_ptr()
-    p.M, p.N, p.K, p.ldw, p.ldc, p.ldr = B * Ho * Wo, N, 9 * Cin, w.stride(0), out.stride(0), N
-    p.conv, p.Hin, p.Hout, p.Win, p.Wout = 1, H, Ho, W, Wo
-    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = Cin, 3, 3, stride, 1, x.stride(2)
-    p.alpha, p.zero_page, p.flags = alpha, (o.zero_page(DEV) if zero is None else zero).data_ptr(), flags
-    if residual is not None:
-        p.residual, p.ldr = residual.data_ptr(), residual.stride(0)
-    if rowvec is not None:
-        p.rowvec, p.ld_rowvec, p.rows_per_batch = rowvec.data_ptr(), rowvec.stride(0), Ho * Wo
-    if stats is not None:
-        p.flags |= l.GEMM_CH_STATS
-        p.ch_stats, p.ch_stats_rows = stats.data_ptr(), stats.shape[1]
-    if ksplit:
-        p.flags |= l.GEMM_HALO_KSPLIT
-        p.partial = ws.data_ptr() if ws is not None else None
-    return p
+    g = l.ConvGeom.conv3x3(H, W, Cin, stride=stride, ldx=x.stride(2))
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    return l.gemm_params(
+        A=x.data_ptr(), W=w.data_ptr(), C=out.data_ptr(), M=g.M(B), N=N, K=g.K, ldw=w.stride(0), ldc=out.stride(0), conv=g,
+        bias=ptr(bias), residual=ptr(residual), ldr=N if residual is None else residual.stride(0), rowvec=ptr(rowvec),
+        ld_rowvec=0 if rowvec is None else rowvec.stride(0), rows_per_batch=g.Hout * g.Wout, alpha=alpha,
+        flags=flags | (l.GEMM_HALO_KSPLIT if ksplit else 0), zero_page=(o.zero_page(DEV) if zero is None else zero).data_ptr(),
+        partial=ptr(ws) if ksplit else None, ch_stats=None if stats is None else (stats.data_ptr(), stats.shape[1]))
 
 
 @functools.lru_cache(maxsize=None)

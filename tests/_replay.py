@@ -428,14 +428,10 @@ for _cfg in GEMM_REPLAY_CONFIGS:
 # ---------------------------------------------------------------------- convolutions ------------
 def _conv_params(x, w, bias, out, B, H, Wd, Cin, N, ks, ldc, ldx, zero_page, flags=0, scatter=0):
     """LbGemmParams of a 3x3 / pad 1 (ks = 3) or one-launch sub-pixel 2x2 (ks = 2, scatter = 2) conv on NHWC x."""
-    p = _lib().LbGemmParams()
-    p.A, p.W, p.C, p.bias = x.data_ptr(), w.data_ptr(), out.data_ptr(), bias.data_ptr()
-    p.conv, p.M, p.N, p.K = 1, B * H * Wd, N, ks * ks * Cin
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride = H, Wd, H, Wd, Cin, ks, ks, 1
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, scatter)
-    p.ldx, p.ldw, p.ldc, p.alpha, p.flags = ldx, w.stride(0), ldc, 1.0, flags
-    p.zero_page = zero_page.data_ptr()
-    return p
+    l = _lib()
+    g = l.ConvGeom.conv3x3(H, Wd, Cin, ldx=ldx) if ks == 3 else l.ConvGeom(H, Wd, Cin, ks, ks, ldx=ldx, parity="all" if scatter else None)
+    return l.gemm_params(A=x.data_ptr(), W=w.data_ptr(), C=out.data_ptr(), bias=bias.data_ptr(), M=B * H * Wd, N=N, K=g.K, ldw=w.stride(0),
+                         ldc=ldc, conv=g, flags=flags, zero_page=zero_page.data_ptr())
 
 
 def _halo_operands(c, B, H, Wd, Cin, Cout, ldx_pad=8, seed=90):

@@ -23,27 +23,21 @@ SLAB_BYTES = 256 * 128 * 4
 
 def build_params(row, flags):
     kind, B, H, W, cin, cout, opt = row
-    p = lib.LbGemmParams()
-    p.flags = flags | opt.get("flags", 0)
-    p.A = p.W = p.C = 4096                              # (host arithmetic only: never dereferenced)
+    flags |= opt.get("flags", 0)
     if kind in ("gemm", "geglu"):
-        p.M, p.N, p.K, p.lda, p.ldw = B, cout, cin, cin, cin
-        if kind == "geglu":
-            p.flags |= G.GEGLU
-        p.ldc = p.ldr = cout // 2 if kind == "geglu" else cout
+        n_out = cout // 2 if kind == "geglu" else cout
+        flags |= G.GEGLU if kind == "geglu" else 0
+        shape = dict(M=B, N=cout, K=cin, lda=cin, ldw=cin, ldc=n_out, ldr=n_out)
     else:
         ks, stride, pad, ups, scatter = G.KINDS[kind]
-        ho, wo = (((H << ups) + 2 * pad - ks) // stride + 1, ((W << ups) + 2 * pad - ks) // stride + 1) if scatter == 0 else (H, W)
-        p.conv, p.M, p.N, p.K = 1, B * ho * wo, cout, ks * ks * cin
-        p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW = H, W, ho, wo, cin, ks, ks
-        p.stride, p.pad, p.ups, p.scatter, p.ldx, p.ldw, p.ldc, p.ldr = stride, pad, ups, scatter, cin, ks * ks * cin, cout, cout
-    p.residual = 4096 if opt.get("residual") else None
-    if opt.get("rowvec"):
-        p.rowvec, p.ld_rowvec, p.rows_per_batch = 4096, cout, p.M // B
-    small = ((p.M + 63) // 64) * ((p.N + 63) // 64) <= 640 and kind != "geglu"
-    p.partial = 4096 if opt.get("partial", small) else None
-    p.zero_page = 64 if opt.get("zero_page", True) else None
-    return p
+        g = lib.ConvGeom(H, W, cin, ks, ks, stride=stride, pad=pad, ups=ups, parity=[None, (0, 0), "all"][scatter])
+        shape = dict(M=g.M(B), N=cout, K=g.K, ldw=g.K, ldc=cout, ldr=cout, conv=g)
+    M = shape["M"]
+    small = ((M + 63) // 64) * ((cout + 63) // 64) <= 640 and kind != "geglu"
+    fake = lambda on: 4096 if on else None      # noqa: E731  (host arithmetic only: never dereferenced)
+    return lib.gemm_params(A=4096, W=4096, C=4096, residual=fake(opt.get("residual")), rowvec=fake(opt.get("rowvec")), ld_rowvec=cout,
+                           rows_per_batch=M // B, partial=fake(opt.get("partial", small)), flags=flags,
+                           zero_page=64 if opt.get("zero_page", True) else None, **shape)
 
 
 def old_exports(api, p):
@@ -170,7 +164,7 @@ def test_probes_plan_without_allocating(monkeypatch):
     B, H, Cin, N = 17, 64, 320, 320                       # a conv the default policy splits along K: no fold, a GroupNorm launch
     x, w = torch.empty(B, H, H, Cin, dtype=torch.float16), torch.empty(N, 9 * Cin, dtype=torch.float16)
     gamma, st = torch.ones(Cin), (torch.zeros(Cin, B * 4, 2), 4)
-    conv = dict(Hin=H, Win=H, Cin=Cin, Hout=H, Wout=H, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=Cin)
+    conv = lib.ConvGeom.conv3x3(H, H, Cin)
     prog = rt.Program("t")
     with prog.record():
         g = em.gn_operand(x, w, M=B * H * H, conv=conv, gamma=gamma, beta=gamma, B=B, HW=H * H, C_=Cin, eps=1e-6, silu=True, groups=32,

@@ -89,7 +89,7 @@ class Chain:
         _, wd, _, bd = weights()[i]
         src, dst = self.io(i)
         self.em.gemm(src, wd, dst, M=B * H * W, bias=bd, ch_stats=self.stats if with_stats else None,
-                     conv=dict(Hin=H, Win=W, Cin=cin, Hout=H, Wout=W, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=cin))
+                     conv=lib().ConvGeom.conv3x3(H, W, cin))
 
     def emit_all(self):
         for i in range(len(CONVS)):

@@ -34,10 +34,7 @@ def test_shape_has_the_edges_it_claims():
 def _plan(k, flags):
     """lb_gemm_plan's (tile, splitk) for the matrix shape with K = ``k`` (host arithmetic: the pointers are never dereferenced)."""
     from latentblending_amd.hip import lib
-    p = lib.LbGemmParams()
-    p.A = p.W = p.C = p.partial = 4096
-    p.zero_page = 64
-    p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.flags = E.M, E.N, k, k, k, E.N, flags
+    p = lib.gemm_params(A=4096, W=4096, C=4096, partial=4096, zero_page=64, M=E.M, N=E.N, K=k, lda=k, ldw=k, ldc=E.N, flags=flags)
     tile, sk = C.c_int(), C.c_int()
     lib.api.lb_gemm_plan(C.byref(p), C.byref(tile), C.byref(sk), None)
     return tile.value, sk.value
@@ -104,11 +101,9 @@ def test_trans_out_with_out_f32_is_refused():
     M, N, K = 64, 64, 64
     a, w = (C.c_uint16 * (M * K))(), (C.c_uint16 * (N * K))()
     out = (C.c_uint8 * (M * N * 4))(*([0xA5] * (M * N * 4)))
-    p = lib.LbGemmParams()
-    p.A, p.W, p.C = C.addressof(a), C.addressof(w), C.addressof(out)
-    p.M, p.N, p.K, p.lda, p.ldw, p.ldc = M, N, K, K, K, M
     for extra in (0, lib.GEMM_RES_F32, lib.GEMM_RELU):
-        p.flags = lib.GEMM_TRANS_OUT | lib.GEMM_OUT_F32 | extra
+        p = lib.gemm_params(A=C.addressof(a), W=C.addressof(w), C=C.addressof(out), M=M, N=N, K=K, lda=K, ldw=K, ldc=M,
+                            flags=lib.GEMM_TRANS_OUT | lib.GEMM_OUT_F32 | extra)
         with pytest.raises(RuntimeError) as ei:
             lib.api.lb_gemm_f16(C.byref(p), None)
         assert "LB_GEMM_TRANS_OUT" in str(ei.value) and "LB_GEMM_OUT_F32" in str(ei.value)

@@ -51,24 +51,11 @@ def _launch(expect, A, W, out, m, n, k, ldc, flags=0, alpha=1.0, bias=None, rowv
     ``expect`` = (tile, splitk) - tile None: whatever the automatic policy picks - and the implicit-GEMM route, then launch that very
     block.  Returns the tile code."""
     l = lib()
-    p = l.LbGemmParams()
-    p.A, p.W, p.C = A.data_ptr(), W.data_ptr(), out.data_ptr()
-    p.M, p.N, p.K, p.ldw, p.ldc = m, n, k, W.stride(0), ldc
-    p.alpha, p.flags = alpha, flags
-    if bias is not None:
-        p.bias = bias.data_ptr()
-    if rowvec is not None:
-        p.rowvec, p.ld_rowvec, p.rows_per_batch = rowvec.data_ptr(), rowvec.stride(0), rows_per_batch
-    if residual is not None:
-        p.residual, p.ldr = residual.data_ptr(), ldr
-    if conv is None:
-        p.lda = A.stride(0)
-    else:
-        p.conv, p.ldx = 1, A.stride(2)
-        for key, val in conv.items():
-            setattr(p, key, val)
-    p.partial = workspace(m, n).data_ptr()
-    p.zero_page = ops().zero_page(A.device).data_ptr()
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    p = l.gemm_params(A=A.data_ptr(), W=W.data_ptr(), C=out.data_ptr(), M=m, N=n, K=k, lda=A.stride(0) if conv is None else 0,
+                      ldw=W.stride(0), ldc=ldc, conv=conv, bias=ptr(bias), residual=ptr(residual), ldr=ldr if residual is not None else 0,
+                      rowvec=ptr(rowvec), ld_rowvec=0 if rowvec is None else rowvec.stride(0), rows_per_batch=rows_per_batch, alpha=alpha,
+                      flags=flags, partial=workspace(m, n).data_ptr(), zero_page=ops().zero_page(A.device).data_ptr())
     tile, sk = C.c_int(), C.c_int()
     l.api.lb_gemm_plan(C.byref(p), C.byref(tile), C.byref(sk), None)
     assert l.conv_plan(p).route == l.ROUTE_GEMM, f"routed to {l.conv_plan(p).route}, not to the implicit GEMM"
@@ -235,17 +222,13 @@ def _run_conv_form(form, c, expect, bias, rv, res):
     B, H, Wd, cin, cin_p, cout, ks, stride, pad, ups, scatter = CONV_FORMS[form]
     xd, wd = c["x"].to(DEV), c["w"].to(DEV)
     bd, rvd, rd = [None if t is None else t.to(DEV) for t in (bias, rv, res)]
-    hout, wout = (H, Wd) if scatter else (((H << ups) + 2 * pad - ks) // stride + 1, ((Wd << ups) + 2 * pad - ks) // stride + 1)
-    m, k = B * hout * wout, ks * ks * cin_p
     out = torch.full(tuple(c["base"].shape), float("nan"), dtype=F16, device=DEV)
-    geo = dict(Hin=H, Win=Wd, Cin=cin_p, Hout=hout, Wout=wout, KH=ks, KW=ks, stride=stride, pad=pad, ups=ups)
     tiles = set()
     for par in ([(0, 0), (0, 1), (1, 0), (1, 1)] if scatter else [None]):
-        conv, wpar = dict(geo), wd
-        if par is not None:
-            conv.update(scatter=1, sc_py=par[0], sc_px=par[1])
-            wpar = wd[2 * par[0] + par[1]]
-        tiles.add(_launch(expect, xd, wpar, out, m, cout, k, cout, bias=bd, rowvec=rvd, rows_per_batch=hout * wout, residual=rd, ldr=cout, conv=conv))
+        g = lib().ConvGeom(H, Wd, cin_p, ks, ks, stride=stride, pad=pad, ups=ups, ldx=xd.stride(2), parity=par)
+        wpar = wd if par is None else wd[2 * par[0] + par[1]]
+        tiles.add(_launch(expect, xd, wpar, out, g.M(B), cout, g.K, cout, bias=bd, rowvec=rvd, rows_per_batch=g.Hout * g.Wout, residual=rd,
+                          ldr=cout, conv=g))
     return out.cpu(), tiles
 
 

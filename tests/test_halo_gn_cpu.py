@@ -90,9 +90,7 @@ def test_launchers_refuse_before_launching():
     with pytest.raises(RuntimeError, match="LB_GEMM_GN_A"):       # a conv the router sends to the implicit GEMM
         api.lb_gemm_f16(C.byref(_flagged(P(2, 16, 32, 96, 128))), None)
     with pytest.raises(RuntimeError, match="LB_GEMM_GN_A"):       # a plain GEMM
-        g = lib.LbGemmParams()
-        g.A = g.W = g.C = g.zero_page = 4096
-        g.M, g.N, g.K, g.lda, g.ldw, g.ldc, g.alpha = 64, 64, 64, 64, 64, 64, 1.0
+        g = lib.gemm_params(A=4096, W=4096, C=4096, zero_page=4096, M=64, N=64, K=64, lda=64, ldw=64, ldc=64)
         api.lb_gemm_f16(C.byref(_flagged(g)), None)
     with pytest.raises(RuntimeError, match="LB_GEMM_GN_A"):
         api.lb_gemm_f16(C.byref(_flagged(P(2, 16, 16, 64, 64, flags=lib.GEMM_C64))), None)
@@ -119,7 +117,7 @@ def _conv_of_groupnorm(rt, em, B, H, Cin, N, *, x_dtype=torch.float16, stats=Tru
     out = torch.empty(B * H * H, N, dtype=F32 if flags & lib.GEMM_OUT_F32 else torch.float16)
     gamma = torch.ones(Cin, dtype=F32)
     st = (torch.zeros(Cin, B * 4, 2, dtype=F32), 4) if stats else None
-    conv = dict(Hin=H, Win=H, Cin=Cin, Hout=H, Wout=H, KH=3, KW=3, stride=1, pad=1, ups=0, ldx=Cin)
+    conv = lib.ConvGeom.conv3x3(H, H, Cin)
     prog = rt.Program("t")
     with prog.record():
         g = em.gn_operand(x, w, M=B * H * H, conv=conv, flags=flags, has_residual=residual, gamma=gamma, beta=gamma, B=B, HW=H * H,

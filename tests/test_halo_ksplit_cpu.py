@@ -11,12 +11,8 @@ SLAB_BYTES = 256 * 128 * 4
 
 
 def conv_params(B, H, W, Cin, N, flags=0):
-    p = lib.LbGemmParams()
-    p.M, p.N, p.K, p.conv, p.flags = B * H * W, N, 9 * Cin, 1, flags
-    p.Hin, p.Hout, p.Win, p.Wout = H, H, W, W
-    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx, p.ldw, p.ldc = Cin, 3, 3, 1, 1, Cin, 9 * Cin, N
-    p.zero_page = 64
-    return p
+    g = lib.ConvGeom.conv3x3(H, W, Cin)
+    return lib.gemm_params(M=g.M(B), N=N, K=g.K, ldw=g.K, ldc=N, conv=g, flags=flags, zero_page=64)
 
 
 def ksplit_plan(p):

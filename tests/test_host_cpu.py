@@ -692,11 +692,7 @@ def test_gemm_tile_policy_is_pinned():
     assert plan(4456448, 4, 1152, conv=True)[0] == 3                    # conv_out: 3 real columns (this bare plan describes no 3x3 geometry)
 
     def conv_plan(B, H, Cin, N, flags=0):
-        p = lib.LbGemmParams()
-        p.M, p.N, p.K, p.conv, p.flags = B * H * H, N, 9 * Cin, 1, flags
-        p.Hin = p.Win = p.Hout = p.Wout = H
-        p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = Cin, 3, 3, 1, 1, Cin
-        p.zero_page = 64
+        p = lib.conv_probe(B, H, H, Cin, N, flags=flags)
         t, sk, nb = ctypes.c_int(), ctypes.c_int(), ctypes.c_long()
         lib.api.lb_gemm_plan(ctypes.byref(p), ctypes.byref(t), ctypes.byref(sk), ctypes.byref(nb))
         return t.value, nb.value
@@ -914,13 +910,7 @@ def test_halo_conv_persistent_work_split(B, H, W, Cin, N, ks):
     block keeps ONE channel block (and parity) for its whole life - what lets it keep its weight stream running across
     tile boundaries."""
     from latentblending_amd.hip import lib
-    p = lib.LbGemmParams()
-    p.conv, p.Hin, p.Win, p.Cin, p.Hout, p.Wout, p.stride, p.ups, p.ldx = 1, H, W, Cin, H, W, 1, 0, Cin
-    p.KH = p.KW = ks
-    p.pad = 1 if ks == 3 else 0
-    p.scatter = 2 if ks == 2 else 0
-    p.M, p.N, p.K = B * H * W, N, ks * ks * Cin
-    p.zero_page = 64                                     # (never dereferenced by the planner)
+    p = lib.conv_probe(B, H, W, Cin, N, ks)              # (zero_page: never dereferenced by the planner)
     kind, tw, items, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_long(), ctypes.c_long()
     lib.api.lb_conv_halo_plan(ctypes.byref(p), ctypes.byref(kind), ctypes.byref(tw), ctypes.byref(items), ctypes.byref(grid))
     assert kind.value == ks and tw.value in (16, 32)

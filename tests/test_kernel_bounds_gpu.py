@@ -317,11 +317,8 @@ def test_conv3x3_narrow_memory_contract(case, ldc_pad, ldx_pad, results_log):
     bp[:Cout] = b
     x_d, w_d = _nhwc_poisoned(x, Cin, Cin + ldx_pad), poisoned(wp, cout_p, 9 * Cin, 9 * Cin, NAN, DEV)
     flags = l.GEMM_OUT_F32 if f32 else 0
-    p = l.LbGemmParams()
-    p.M, p.N, p.K, p.conv, p.flags = B * H * H, cout_p, 9 * Cin, 1, flags
-    p.Hin = p.Win = p.Hout = p.Wout = H
-    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = Cin, 3, 3, 1, 1, Cin + ldx_pad
-    p.zero_page = o.zero_page(DEV).data_ptr()
+    p = l.conv_probe(B, H, H, Cin, cout_p, flags=flags, zero_page=o.zero_page(DEV).data_ptr())
+    p.ldx = Cin + ldx_pad                   # (the padded pixel stride of x_d)
     t = C.c_int()
     l.api.lb_gemm_plan(C.byref(p), C.byref(t), None, None)
     assert t.value == 8

@@ -786,11 +786,7 @@ def test_conv3x3_narrow_output(case, results_log):
     bp = torch.zeros(cout_p, dtype=torch.float32)
     bp[:Cout] = b
     xn = x.permute(0, 2, 3, 1).contiguous().to(DEV)
-    p = l.LbGemmParams()
-    p.M, p.N, p.K, p.conv, p.flags = B * H * H, cout_p, 9 * Cin, 1, (l.GEMM_OUT_F32 if f32 else 0)
-    p.Hin = p.Win = p.Hout = p.Wout = H
-    p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = Cin, 3, 3, 1, 1, Cin
-    p.zero_page = o.zero_page(DEV).data_ptr()
+    p = l.conv_probe(B, H, H, Cin, cout_p, flags=l.GEMM_OUT_F32 if f32 else 0, zero_page=o.zero_page(DEV).data_ptr())
     t = C.c_int()
     l.api.lb_gemm_plan(C.byref(p), C.byref(t), None, None)
     assert t.value == 8

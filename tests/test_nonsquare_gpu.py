@@ -235,10 +235,8 @@ def _gemm_plan(shape, flags):
     import ctypes as C
     l = lib()
     B, H, W, Cin, Cout = shape
-    p = l.LbGemmParams()
-    p.conv, p.M, p.N, p.K, p.flags = 1, B * H * W, Cout, 9 * Cin, flags
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.KH, p.KW, p.stride, p.pad, p.ldx = H, W, H, W, Cin, 3, 3, 1, 1, Cin
-    p.ldw, p.ldc, p.zero_page = 9 * Cin, Cout, 64
+    g = l.ConvGeom.conv3x3(H, W, Cin)
+    p = l.gemm_params(M=g.M(B), N=Cout, K=g.K, ldw=g.K, ldc=Cout, conv=g, flags=flags, zero_page=64)
     t, sk, nb = C.c_int(), C.c_int(), C.c_long()
     l.api.lb_gemm_plan(C.byref(p), C.byref(t), C.byref(sk), C.byref(nb))
     return t.value, sk.value, nb.value

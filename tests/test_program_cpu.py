@@ -53,22 +53,13 @@ def test_every_stream_launcher_has_a_replay_case():
 
 # ---------------------------------------------------------------- fake calls of every launcher
 def conv_params(B=1, H=16, W=32, Cin=64, N=128, ks=3, flags=0, scatter=0, ldc=None):
-    p = lib.LbGemmParams()
-    p.conv, p.M, p.N, p.K = 1, B * H * W, N, ks * ks * Cin
-    p.Hin = p.Hout = H
-    p.Win = p.Wout = W
-    p.Cin, p.KH, p.KW, p.stride, p.ldx, p.ldw = Cin, ks, ks, 1, Cin, ks * ks * Cin
-    p.pad, p.scatter = (1, 0) if ks == 3 else (0, scatter)
-    p.ldc = N if ldc is None else ldc
-    p.A, p.W, p.C, p.zero_page, p.flags = P[0], P[1], P[2], P[3], flags
-    return p
+    g = lib.ConvGeom.conv3x3(H, W, Cin) if ks == 3 else lib.ConvGeom(H, W, Cin, ks, ks, parity="all" if scatter == 2 else None)
+    return lib.gemm_params(A=P[0], W=P[1], C=P[2], zero_page=P[3], M=g.M(B), N=N, K=g.K, ldw=g.K, ldc=N if ldc is None else ldc, conv=g,
+                           flags=flags)
 
 
 def gemm_params(M=64, N=64, K=64, flags=0):
-    p = lib.LbGemmParams()
-    p.M, p.N, p.K, p.lda, p.ldw, p.ldc, p.flags = M, N, K, K, K, N, flags
-    p.A, p.W, p.C, p.zero_page = P[0], P[1], P[2], P[3]
-    return p
+    return lib.gemm_params(A=P[0], W=P[1], C=P[2], zero_page=P[3], M=M, N=N, K=K, lda=K, ldw=K, ldc=N, flags=flags)
 
 
 def attn_params(D=64, causal=0, Sq=128, Skv=128):

@@ -21,14 +21,9 @@ def lib():
 def c64_params(B=2, H=12, W=20, Cin=64, N=64, ups=0, stride=1, flags=None, **over):
     """An eligible flagged problem (fake pointers: nothing here launches), then the overrides."""
     l = lib()
-    p = l.LbGemmParams()
-    ho, wo = ((H << ups) - 1) // stride + 1, ((W << ups) - 1) // stride + 1
-    p.A, p.W, p.C, p.zero_page = 4096, 8192, 12288, 64
-    p.conv, p.M, p.N, p.K = 1, B * ho * wo, N, 9 * Cin
-    p.Hin, p.Win, p.Hout, p.Wout, p.Cin = H, W, ho, wo, Cin
-    p.KH, p.KW, p.stride, p.pad, p.ups = 3, 3, stride, 1, ups
-    p.ldx, p.ldw, p.ldc, p.ldr = Cin, 9 * Cin, N, N
-    p.flags = l.GEMM_C64 if flags is None else flags
+    g = l.ConvGeom.conv3x3(H, W, Cin, stride=stride, ups=ups)
+    p = l.gemm_params(A=4096, W=8192, C=12288, zero_page=64, M=g.M(B), N=N, K=g.K, ldw=g.K, ldc=N, ldr=N, conv=g,
+                      flags=l.GEMM_C64 if flags is None else flags)
     for k, v in over.items():
         setattr(p, k, v)
     return p
