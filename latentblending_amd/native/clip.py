@@ -23,14 +23,14 @@ import re
 import warnings
 import zlib
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from ..hip import lib
 from ..hip.lib import api
-from .runtime import Arena, Emitter, Program, F16, F32, _stream
-from .unet import Mark, capture_marks
+from .runtime import Program, RecordedProgram, F16, F32, _stream
+from .weights import Packer
 
 MAX_TOKENS = 77
 
@@ -74,10 +74,7 @@ class NativeCLIPText:
             base = getattr(provider, "prefix", "")
             prefix = "" if (base + "embeddings.token_embedding.weight") in state else "text_model."
         c, pv, p = cfg.hidden_size, provider, prefix
-
-        def dev(t, dt):
-            return t.to(device=self.device, dtype=dt).contiguous()
-
+        dev = Packer(pv, self.w, self.device).dev
         self.w["tok"] = dev(pv.weight(p + "embeddings.token_embedding.weight", (cfg.vocab_size, c), c, c ** 0.5 * 0.02), F16)
         self.w["pos"] = dev(pv.weight(p + "embeddings.position_embedding.weight", (cfg.max_position_embeddings, c), c, c ** 0.5 * 0.01), F16)
         for i in range(cfg.num_hidden_layers):
@@ -117,38 +114,24 @@ class NativeCLIPText:
         return _CLIPProgram(self, B, journal=journal)
 
 
-class _CLIPProgram:
+class _CLIPProgram(RecordedProgram):
     """One recorded tower forward for ``B`` prompts.  ``marks``: one ``Mark`` per emission unit - ``embed``; per layer ``L{i}.qkv``
     (LayerNorm 1 + projection), ``L{i}.attn``, ``L{i}.out`` (+ residual), ``L{i}.fc1`` (LayerNorm 2 + projection + activation),
     ``L{i}.fc2`` (+ residual); ``penultimate`` (the copy of the last layer's input, where it is emitted); ``pooled`` (EOS gather +
-    final LayerNorm + projection, towers with a projection only).  ``capture()`` fills ``taps``."""
+    final LayerNorm + projection, towers with a projection only).  ``capture()`` fills ``taps`` from the ids ``run`` left in the
+    buffers (fp16; the residual stream is updated in place, so a clone is the only way to see it)."""
 
     def __init__(self, net: NativeCLIPText, B: int, journal: bool = False):
+        super().__init__(net, B, journal=journal)
         cfg, dev = net.cfg, net.device
-        self.net, self.B = net, B
         c, S, M = cfg.hidden_size, cfg.max_position_embeddings, B * cfg.max_position_embeddings
-        self.arena = Arena(dev, journal=journal)
-        self.em = Emitter(self.arena)
-        self.marks: List[Mark] = []
-        self.taps: Dict[str, torch.Tensor] = {}
         self.ids = torch.zeros(M, dtype=torch.int32, device=dev)
         self.eos_rows = torch.zeros(B, dtype=torch.int32, device=dev)
         self.penultimate = torch.zeros(B, S, c, dtype=F16, device=dev)
         self.pooled = torch.zeros(B, cfg.projection_dim, dtype=F16, device=dev) if cfg.projection_dim else None
         self.prog = Program("clip-text")
-        with self.prog.record(), self.arena.clocked(self.prog):
+        with self._recording(self.prog):
             self._emit()
-
-    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
-        self.marks.append(Mark(name, kind, self.prog.name, self.prog.num_ops, out, tuple(inputs)))
-        return name
-
-    def capture(self) -> Dict[str, torch.Tensor]:
-        """Replay the program on the ids the buffers hold now (``run`` filled them), unit by unit, and keep a clone of every unit's
-        output in ``taps`` (fp16; the residual stream is updated in place, so a clone is the only way to see it).  Leaves
-        ``penultimate`` and ``pooled`` as a ``run`` would."""
-        self.taps = capture_marks({self.prog.name: self.prog}, self.marks)
-        return self.taps
 
     def _emit(self):
         net, cfg, em, ar, w = self.net, self.net.cfg, self.em, self.arena, self.net.w

@@ -20,7 +20,7 @@ import torch
 from ..hip import lib
 from ..hip.lib import api
 from .runtime import Arena, Emitter, F16, F32, _stream
-from .unet import _pad
+from .weights import Packer, pad_to
 
 ALEX_CONVS = [(3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1)]
 
@@ -29,15 +29,11 @@ class NativeLPIPS:
     def __init__(self, provider, device="cuda"):
         self.device = torch.device(device)
         self.w: Dict[str, torch.Tensor] = {}
+        pk = Packer(provider, self.w, self.device)
         for i, (cin, cout, k, _, _) in enumerate(ALEX_CONVS):
-            name = f"net.conv{i + 1}"
-            w = provider.weight(name + ".weight", (cout, cin, k, k), cin * k * k, 1.4)
-            cin_p = _pad(cin, 8)
-            packed = torch.zeros(cout, k, k, cin_p, dtype=torch.float32)
-            packed[..., :cin] = w.permute(0, 2, 3, 1)
-            self.w[name + ".weight"] = packed.reshape(cout, k * k * cin_p).to(self.device, F16).contiguous()
-            self.w[name + ".bias"] = provider.bias(name + ".bias", cout).to(self.device, F32)
-            self.w[f"lin{i}.weight"] = provider.positive(f"lin{i}.weight", cout).to(self.device, F32)
+            assert cout % 4 == 0                    # (the taps are read [HW, cout]: no padded output channels)
+            pk.conv(f"net.conv{i + 1}", cin, cout, k, gain=1.4)
+            self.w[f"lin{i}.weight"] = pk.dev(provider.positive(f"lin{i}.weight", cout), F32)
         self.arena = Arena(self.device)
         self.em = Emitter(self.arena)
         self._acc = torch.zeros(16, dtype=F32, device=self.device)
@@ -56,7 +52,7 @@ class NativeLPIPS:
                 pooled = torch.empty(N, ho, wo, cin, dtype=F16, device=self.device)
                 api.lb_maxpool3s2_nhwc_f16(h.data_ptr(), pooled.data_ptr(), N, hh, ww, cin, _stream())
                 h, hh, ww = pooled, ho, wo
-            g = lib.ConvGeom(hh, ww, _pad(cin, 8), k, k, stride=stride, pad=pad)
+            g = lib.ConvGeom(hh, ww, pad_to(cin, 8), k, k, stride=stride, pad=pad)
             ho, wo = g.Hout, g.Wout
             out = torch.empty(N, ho, wo, cout, dtype=F16, device=self.device)
             self.em.gemm(h, self.w[f"net.conv{i + 1}.weight"], out, M=g.M(N), bias=self.w[f"net.conv{i + 1}.bias"],

@@ -497,7 +497,7 @@ class StableDiffusionXLPipeline:
         def build():
             prog = self._tiny_encoder_net().build(B, L, c64=self._tiny_conv_c64)
             if self._use_graphs:
-                prog.prog.instantiate()
+                prog.enable_graphs()
             return prog
         return self._cached(self._tiny_encoder_programs, program_key(B, L), build)
 
@@ -518,17 +518,16 @@ class StableDiffusionXLPipeline:
             prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64) if tiny else \
                 self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
             if self._use_graphs:
-                prog.prog.instantiate()
+                prog.enable_graphs()
             return prog
         return self._cached(self._tiny_vae_programs if tiny else self._vae_programs, program_key(B, L), build)
 
     def enable_graphs(self, flag: bool = True):
         self._use_graphs = bool(flag)
         if flag:
-            for p in self._unet_programs.values():
-                p.enable_graphs()
-            for p in list(self._vae_programs.values()) + list(self._tiny_vae_programs.values()) + list(self._tiny_encoder_programs.values()):
-                p.prog.instantiate()
+            for cache in (self._unet_programs, self._vae_programs, self._tiny_vae_programs, self._tiny_encoder_programs):
+                for p in cache.values():
+                    p.enable_graphs()
 
     def synchronize(self):
         torch.cuda.synchronize(self.device)

@@ -9,18 +9,20 @@
   (optionally as one hipGraph) with a single ctypes call.
 * ``Emitter`` — thin typed helpers that fill the C structs and call the launchers (in record mode
   these calls are captured, in eager mode they launch immediately — same code path).
+* ``RecordedProgram`` — what every model's program object is: arena + emitter, the recording context, the unit marks
+  (``Mark``) and their replay (``capture_marks``), graph instantiation.
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from ..hip import lib
 from ..hip.lib import api, LbGemmParams, LbAttnParams
-from .geometry import use_ragged_halo
+from .geometry import latent_hw, use_ragged_halo
 
 F16, F32 = torch.float16, torch.float32
 
@@ -409,3 +411,87 @@ class Emitter:
     def copy(self, dst: torch.Tensor, src: torch.Tensor):
         assert dst.numel() * dst.element_size() == src.numel() * src.element_size()
         api.lb_copy_d2d(dst.data_ptr(), src.data_ptr(), src.numel() * src.element_size(), _stream())
+
+
+class Mark(NamedTuple):
+    """End of one emission unit of a recorded program (``RecordedProgram.marks``): the unit's ops are those from the previous mark of
+    the same program up to ``op_end`` (exclusive), ``out`` is the view its result is read through - valid right after op
+    ``op_end - 1``, the arena may hand the buffer on later - and ``inputs`` names the units (or program inputs) it read."""
+    name: str
+    kind: str
+    program: str
+    op_end: int
+    out: torch.Tensor
+    inputs: Tuple[str, ...]
+
+
+def capture_marks(progs: Dict[str, Program], marks: List[Mark], convert=None) -> Dict[str, torch.Tensor]:
+    """Replay ``progs`` (in order) from mark to mark with ``run_range`` and clone every unit's output right after its last op.
+    ``convert(mark, clone)`` may turn the clone into what the caller wants to see."""
+    taps: Dict[str, torch.Tensor] = {}
+    for pname, prog in progs.items():
+        at = 0
+        for m in marks:
+            if m.program != pname:
+                continue
+            if m.op_end > at:
+                prog.run_range(at, m.op_end)
+                at = m.op_end
+            t = m.out.clone()
+            taps[m.name] = convert(m, t) if convert is not None else t
+        if at < prog.num_ops:
+            prog.run_range(at, prog.num_ops)
+    return taps
+
+
+class RecordedProgram:
+    """Base of a model's program object: the launches of ``net`` for a fixed batch ``B`` (and latent size), recorded once.
+    ``L``: latent side or ``(H, W)`` -> ``.H`` / ``.W`` always, ``.L`` for square programs (else None); ``ragged_halo``: a
+    non-square program may send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo kernel
+    (``geometry.use_ragged_halo``); a square program records what it always recorded.  ``L=None``: a program without geometry.
+    A subclass allocates its buffers, then records each ``Program`` it owns inside ``with self._recording(prog):``; its emitting
+    code calls ``_mark`` at the end of every unit it wants to be seen.  ``programs``: the recorded ``Program``s in order."""
+
+    def __init__(self, net, B: int, L=None, ragged_halo: bool = True, journal: bool = False):
+        self.net, self.B = net, B
+        self.arena = Arena(net.device, journal=journal)
+        self.em = Emitter(self.arena)
+        if L is not None:
+            self.H, self.W = latent_hw(L)
+            self.L = self.H if self.H == self.W else None
+            self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and self.H != self.W
+        self.marks: List[Mark] = []
+        self.tap_names: Dict[str, str] = {}            # alias (the oracle's block taps) -> the unit whose output it is
+        self.taps: Dict[str, torch.Tensor] = {}
+        self.persistent: List[torch.Tensor] = []       # arena tensors that stay live after emission
+        self.programs: Tuple[Program, ...] = ()
+        self._rec: Optional[Program] = None
+
+    @contextlib.contextmanager
+    def _recording(self, prog: Program):
+        """``prog`` records, the arena's journal carries its clock, ``_mark`` counts its ops."""
+        self.programs += (prog,)
+        self._rec = prog
+        try:
+            with prog.record(), self.arena.clocked(prog):
+                yield prog
+        finally:
+            self._rec = None
+
+    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
+        self.marks.append(Mark(name, kind, self._rec.name, self._rec.num_ops, out, tuple(inputs)))
+        return name
+
+    def capture(self, convert=None) -> Dict[str, torch.Tensor]:
+        """Replay the programs on what the input buffers hold now, unit by unit, and keep a clone of every unit's output in ``taps``
+        (``convert(mark, clone)`` may change what is kept), also under the aliases of ``tap_names``.  Leaves the outputs as a plain
+        run would."""
+        taps = capture_marks({p.name: p for p in self.programs}, self.marks, convert)
+        for tap, unit in self.tap_names.items():
+            taps[tap] = taps[unit]
+        self.taps = taps
+        return taps
+
+    def enable_graphs(self) -> None:
+        for p in self.programs:
+            p.instantiate()

@@ -37,10 +37,8 @@ import torch
 
 from ..hip import lib
 from ..hip.lib import api
-from .geometry import latent_hw
-from .runtime import Arena, Emitter, Program, F16, F32, _stream
-from .unet import _pad
-from .weights import SyntheticProvider
+from .runtime import Program, RecordedProgram, F16, F32, _stream
+from .weights import Packer, SyntheticProvider, pad_to
 
 # LB_GEMM_C64 is set on a 64 -> 64 conv only where the flagged launch measured faster than the library's own route for the same
 # problem by more than the run-to-run spread (tools/tiny_vae_bench.py -> profiles/tiny_vae.txt, one MI355X, both launches
@@ -122,45 +120,26 @@ class _TinyNet:
     def __init__(self, cfg: TinyVAEConfig, provider, device="cuda"):
         self.cfg, self.device = cfg, torch.device(device)
         self.w: Dict[str, torch.Tensor] = {}
-        self._load(provider)
-
-    def _dev(self, t, dtype):
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _conv(self, pv, name, cin, cout, bias=True, gain=1.0, bias_shift=0.0, fold=False):
-        """Packed as ``NativeVAEDecoder._conv`` does: [cout_p][3][3][cin_p] fp16 ((ky, kx, cin) order), fp32 bias.  ``fold``: the
-        decoder's final ``2 x - 1`` goes into the last conv (``W * 2``: exact in fp16; ``b * 2 - 1``)."""
-        w = pv.weight(name + ".weight", (cout, cin, 3, 3), cin * 9, gain)
-        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
-        packed = torch.zeros(cout_p, 3, 3, cin_p, dtype=torch.float32)
-        packed[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
-        b = torch.zeros(cout_p, dtype=torch.float32)
-        if bias:
-            b[:cout] = pv.bias(name + ".bias", cout) + bias_shift
-        if fold:
-            packed, b = packed * 2.0, b * 2.0
-            b[:cout] -= 1.0
-        self.w[name + ".weight"] = self._dev(packed.reshape(cout_p, 9 * cin_p), F16)
-        self.w[name + ".bias"] = self._dev(b, F32) if (bias or fold) else None
+        self._load(Packer(provider, self.w, self.device))
 
 
 class NativeTinyVAEDecoder(_TinyNet):
-    def _load(self, pv):
+    def _load(self, pk):
         cfg = self.cfg
         # the synthetic stand-in: the last conv at gain 0.5 with 0.5 added to its biases, so that frames centre on mid-grey
         # instead of saturating at black; a real checkpoint (DictProvider) is taken as it is
-        synthetic = isinstance(pv, SyntheticProvider)
+        synthetic = isinstance(pk.pv, SyntheticProvider)
         for kind, n in layer_plan(cfg):
             p = f"decoder.layers.{n}"
             if kind == "in":
-                self._conv(pv, p, cfg.latent_channels, 64)
+                pk.conv(p, cfg.latent_channels, 64, 3)
             elif kind == "block":
                 for k in (0, 2, 4):
-                    self._conv(pv, f"{p}.conv.{k}", 64, 64)
+                    pk.conv(f"{p}.conv.{k}", 64, 64, 3)
             elif kind == "up":
-                self._conv(pv, p, 64, 64, bias=False)
-            else:
-                self._conv(pv, p, 64, cfg.out_channels, gain=0.5, bias_shift=0.5 if synthetic else 0.0, fold=True)
+                pk.conv(p, 64, 64, 3, bias=False)
+            else:       # the decoder's final ``2 x - 1`` goes into the last conv
+                pk.conv(p, 64, cfg.out_channels, 3, gain=0.5, bias_shift=0.5 if synthetic else 0.0, fold=True)
 
     def build(self, B: int, L, c64: bool = True) -> "TinyVAEProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels.  ``c64``: LB_GEMM_C64 on the 64 -> 64 convs where ``use_c64``
@@ -168,27 +147,14 @@ class NativeTinyVAEDecoder(_TinyNet):
         return TinyVAEProgram(self, B, L, c64=c64)
 
 
-class TinyVAEProgram:
-    """One recorded tiny decode for a fixed (batch, latent size); the surface of ``VAEProgram``."""
+class _TinyProgram(RecordedProgram):
+    """What the programs of the two halves share: the 64 -> 64 conv with its LB_GEMM_C64 rule, and the residual block.  (A
+    non-square program's unflagged 3x3 convs may take the ragged halo form, as in ``VAEProgram``.)"""
 
-    def __init__(self, net: NativeTinyVAEDecoder, B: int, L, c64: bool = True):
-        cfg = net.cfg
-        H, W = latent_hw(L)
-        self.net, self.B, self.H, self.W = net, B, H, W
-        self.L = H if H == W else None
+    def __init__(self, net: _TinyNet, B: int, L, c64: bool = True):
+        super().__init__(net, B, L)
         self.c64 = bool(c64)
         self.c64_launches = 0                   # convs recorded with the bit
-        dev = net.device
-        self.arena = Arena(dev)
-        self.em = Emitter(self.arena)
-        self.em.ragged_halo = H != W            # (the unflagged 3x3 convs of a non-square program, as in VAEProgram)
-        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
-        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
-        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
-        self.image_f32 = torch.zeros(B, SH, SW, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
-        self.prog = Program("tiny-vae-decode")
-        with self.prog.record():
-            self._emit()
 
     def _conv64(self, x, name, B, hin, win, *, ups=0, relu=True, residual=None):
         """One 64 -> 64 conv (on the nearest-2x upsampled map when ``ups``): flagged where the rule says so."""
@@ -203,10 +169,36 @@ class TinyVAEProgram:
         self.em.gemm(x, w[name + ".weight"], out, M=g.M(B), bias=w[name + ".bias"], residual=residual, flags=flags, splitk=False, conv=g)
         return out
 
+    def _block(self, h, p, B, sh, sw):
+        """relu(conv(relu(conv(relu(conv(h))))) + h) at ``p``.conv.{0,2,4}; takes ``h`` back to the arena."""
+        ar = self.arena
+        a = self._conv64(h, p + ".conv.0", B, sh, sw)
+        b = self._conv64(a, p + ".conv.2", B, sh, sw)
+        ar.release(a)
+        o = self._conv64(b, p + ".conv.4", B, sh, sw, residual=h)
+        ar.release(b)
+        ar.release(h)
+        return o
+
+
+class TinyVAEProgram(_TinyProgram):
+    """One recorded tiny decode for a fixed (batch, latent size); the surface of ``VAEProgram``."""
+
+    def __init__(self, net: NativeTinyVAEDecoder, B: int, L, c64: bool = True):
+        super().__init__(net, B, L, c64)
+        cfg, H, W, dev = net.cfg, self.H, self.W, net.device
+        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
+        self.image_f32 = torch.zeros(B, SH, SW, pad_to(cfg.out_channels, 4), dtype=F32, device=dev)
+        self.prog = Program("tiny-vae-decode")
+        with self._recording(self.prog):
+            self._emit()
+
     def _emit(self):
         cfg, em, w, ar, B = self.net.cfg, self.em, self.net.w, self.arena, self.B
         sh, sw = self.H, self.W
-        lc, lc_p = cfg.latent_channels, _pad(cfg.latent_channels, 8)
+        lc, lc_p = cfg.latent_channels, pad_to(cfg.latent_channels, 8)
         z8 = ar.alloc((B, sh, sw, lc_p))            # (pad channels written as zeros by the layout kernel)
         api.lb_nchw_to_nhwc_f16(self.z_in.data_ptr(), z8.data_ptr(), B, lc, sh * sw, lc_p, 1.0, _stream())
         h = None
@@ -218,13 +210,7 @@ class TinyVAEProgram:
                         conv=lib.ConvGeom.conv3x3(sh, sw, lc_p))
                 ar.release(z8)
             elif kind == "block":
-                a = self._conv64(h, p + ".conv.0", B, sh, sw)
-                b = self._conv64(a, p + ".conv.2", B, sh, sw)
-                ar.release(a)
-                o = self._conv64(b, p + ".conv.4", B, sh, sw, residual=h)
-                ar.release(b)
-                ar.release(h)
-                h = o
+                h = self._block(h, p, B, sh, sw)
             elif kind == "up":
                 o = self._conv64(h, p, B, sh, sw, ups=1, relu=False)
                 ar.release(h)
@@ -234,7 +220,7 @@ class TinyVAEProgram:
                 em.gemm(h, w[p + ".weight"], self.image_f32, M=B * sh * sw, bias=w[p + ".bias"], flags=lib.GEMM_OUT_F32, splitk=False,
                         conv=lib.ConvGeom.conv3x3(sh, sw, 64))
                 ar.release(h)
-        api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw, _pad(cfg.out_channels, 4), 1, _stream())
+        api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw, pad_to(cfg.out_channels, 4), 1, _stream())
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """z [B,4,H,W] final latents (scaled units) -> uint8 [B,8H,8W,3].  The decoder's input clamp ``tanh(z / 3) * 3`` is applied
@@ -296,63 +282,43 @@ def encoder_state_dict_keys(cfg: TinyVAEConfig = None):
 
 
 class NativeTinyVAEEncoder(_TinyNet):
-    def _load(self, pv):
+    def _load(self, pk):
         cfg = self.cfg
         for kind, n in encoder_layer_plan(cfg):
             p = f"encoder.layers.{n}"
             if kind == "in":
-                self._conv(pv, p, cfg.out_channels, 64)
+                pk.conv(p, cfg.out_channels, 64, 3)
             elif kind == "block":
                 for k in (0, 2, 4):
-                    self._conv(pv, f"{p}.conv.{k}", 64, 64)
+                    pk.conv(f"{p}.conv.{k}", 64, 64, 3)
             elif kind == "down":
-                self._conv(pv, p, 64, 64, bias=False)
+                pk.conv(p, 64, 64, 3, bias=False)
             else:
-                self._conv(pv, p, 64, cfg.latent_channels)
+                pk.conv(p, 64, cfg.latent_channels, 3)
 
     def build(self, B: int, L, c64: bool = True) -> "TinyEncoderProgram":
         """``L``: LATENT side, or a pair ``(H, W)`` in latent pixels (the picture is 8 times that).  ``c64`` as in the decoder."""
         return TinyEncoderProgram(self, B, L, c64=c64)
 
 
-class TinyEncoderProgram:
+class TinyEncoderProgram(_TinyProgram):
     """One recorded tiny encode for a fixed (batch, latent size): uint8 pictures [B, 8H, 8W, 3] -> fp16 latents [B, 4, H, W]."""
 
     def __init__(self, net: NativeTinyVAEEncoder, B: int, L, c64: bool = True):
-        cfg = net.cfg
-        H, W = latent_hw(L)
-        self.net, self.B, self.H, self.W = net, B, H, W
-        self.L = H if H == W else None
-        self.c64 = bool(c64)
-        self.c64_launches = 0
-        dev = net.device
-        self.arena = Arena(dev)
-        self.em = Emitter(self.arena)
-        self.em.ragged_halo = H != W
+        super().__init__(net, B, L, c64)
+        cfg, H, W, dev = net.cfg, self.H, self.W, net.device
         self.SH, self.SW = H * cfg.scale_factor, W * cfg.scale_factor
-        self.pc, self.pc_p = cfg.out_channels, _pad(cfg.out_channels, 8)
+        self.pc, self.pc_p = cfg.out_channels, pad_to(cfg.out_channels, 8)
         self.x_in = torch.zeros(B, self.SH, self.SW, self.pc_p, dtype=F16, device=dev)      # NHWC; the pad channels stay zero
         self.latents = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
         self.prog = Program("tiny-vae-encode")
-        with self.prog.record():
+        with self._recording(self.prog):
             self._emit()
-
-    def _conv64(self, x, name, B, h, w, *, residual=None):
-        """One biased 64 -> 64 block conv with ReLU: flagged where the rule says so."""
-        wt = self.net.w
-        out = self.arena.alloc((B, h, w, 64))
-        flags = lib.GEMM_RELU
-        if self.c64 and use_c64(B, h, w):
-            flags |= lib.GEMM_C64
-            self.c64_launches += 1
-        self.em.gemm(x, wt[name + ".weight"], out, M=B * h * w, bias=wt[name + ".bias"], residual=residual, flags=flags, splitk=False,
-                     conv=lib.ConvGeom.conv3x3(h, w, 64))
-        return out
 
     def _emit(self):
         cfg, em, w, ar, B = self.net.cfg, self.em, self.net.w, self.arena, self.B
         sh, sw = self.SH, self.SW
-        lc_p = _pad(cfg.latent_channels, 4)
+        lc_p = pad_to(cfg.latent_channels, 4)
         h = None
         for kind, n in encoder_layer_plan(cfg):
             p = f"encoder.layers.{n}"
@@ -361,13 +327,7 @@ class TinyEncoderProgram:
                 em.gemm(self.x_in, w[p + ".weight"], h, M=B * sh * sw, bias=w[p + ".bias"], flags=0, splitk=False,
                         conv=lib.ConvGeom.conv3x3(sh, sw, self.pc_p))
             elif kind == "block":
-                a = self._conv64(h, p + ".conv.0", B, sh, sw)
-                b = self._conv64(a, p + ".conv.2", B, sh, sw)
-                ar.release(a)
-                o = self._conv64(b, p + ".conv.4", B, sh, sw, residual=h)
-                ar.release(b)
-                ar.release(h)
-                h = o
+                h = self._block(h, p, B, sh, sw)
             elif kind == "down":
                 g = lib.ConvGeom.conv3x3(sh, sw, 64, stride=2)
                 ho, wo = g.Hout, g.Wout

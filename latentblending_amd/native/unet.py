@@ -20,14 +20,15 @@ MI355X-specific here:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, NamedTuple, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from ..hip import lib
 from ..hip.lib import api
 from .geometry import check_unet_latent_size, latent_hw
-from .runtime import Arena, Emitter, Program, F16, F32, _stream
+from .runtime import Program, RecordedProgram, F16, F32, _stream
+from .weights import Packer, pad_to
 
 CTX_TOKENS = 77
 CTX_PAD = 80
@@ -57,41 +58,6 @@ class UNetConfig:
         return self.pooled_dim + 6 * self.add_time_dim
 
 
-def _pad(n: int, m: int) -> int:
-    return (n + m - 1) // m * m
-
-
-class Mark(NamedTuple):
-    """End of one emission unit of a recorded program (``UNetProgram.marks`` / ``VAEProgram.marks``): the unit's ops are those from
-    the previous mark of the same program up to ``op_end`` (exclusive), ``out`` is the view its result is read through - valid right
-    after op ``op_end - 1``, the arena may hand the buffer on later - and ``inputs`` names the units (or program inputs) it read."""
-    name: str
-    kind: str
-    program: str
-    op_end: int
-    out: torch.Tensor
-    inputs: Tuple[str, ...]
-
-
-def capture_marks(progs: Dict[str, Program], marks: List[Mark], convert=None) -> Dict[str, torch.Tensor]:
-    """Replay ``progs`` (in order) from mark to mark with ``run_range`` and clone every unit's output right after its last op.
-    ``convert(mark, clone)`` may turn the clone into what the caller wants to see."""
-    taps: Dict[str, torch.Tensor] = {}
-    for pname, prog in progs.items():
-        at = 0
-        for m in marks:
-            if m.program != pname:
-                continue
-            if m.op_end > at:
-                prog.run_range(at, m.op_end)
-                at = m.op_end
-            t = m.out.clone()
-            taps[m.name] = convert(m, t) if convert is not None else t
-        if at < prog.num_ops:
-            prog.run_range(at, prog.num_ops)
-    return taps
-
-
 class NativeUNet:
     def __init__(self, cfg: UNetConfig, provider, device="cuda", fuse_layernorm="auto"):
         """``fuse_layernorm``: fold the three LayerNorms of every transformer block into the GEMMs that consume them
@@ -116,106 +82,67 @@ class NativeUNet:
         self._load(provider)
 
     # ------------------------------------------------------------------ weights -----------
-    def _dev(self, t: torch.Tensor, dtype) -> torch.Tensor:
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _linear(self, pv, name, cin, cout, bias=True, gain=1.0, keep_host=False):
-        w = pv.weight(name + ".weight", (cout, cin), cin, gain)
-        if not keep_host:
-            self.w[name + ".weight"] = self._dev(w, F16)
-        if bias:
-            self.w[name + ".bias"] = self._dev(pv.bias(name + ".bias", cout), F32)
-        return w
-
-    def _conv(self, pv, name, cin, cout, k, gain=1.0):
-        w = pv.weight(name + ".weight", (cout, cin, k, k), cin * k * k, gain)
-        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
-        packed = torch.zeros(cout_p, k, k, cin_p, dtype=torch.float32)
-        packed[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
-        self.w[name + ".weight"] = self._dev(packed.reshape(cout_p, k * k * cin_p), F16)
-        b = torch.zeros(cout_p, dtype=torch.float32)
-        b[:cout] = pv.bias(name + ".bias", cout)
-        self.w[name + ".bias"] = self._dev(b, F32)
-
-    def _upconv(self, pv, name, c):
-        """Upsampler conv (nearest-2x, then 3x3) stored as four 2x2 sub-pixel kernels (4/9 of the FLOPs)."""
-        from ..hip.ops import subpixel_upsample_weights
-        w = pv.weight(name + ".weight", (c, c, 3, 3), c * 9, 1.0)
-        subs = subpixel_upsample_weights(w, _pad(c, 8))
-        for (py, px), k in subs.items():
-            self.w[f"{name}.weight.sub{py}{px}"] = k.to(self.device)
-        # the same four kernels stacked [4][N][4 Cin] (parity py*2+px) for the one-launch halo form
-        self.w[f"{name}.weight.sub4"] = torch.stack([subs[(0, 0)], subs[(0, 1)], subs[(1, 0)], subs[(1, 1)]]).to(self.device).contiguous()
-        self.w[name + ".bias"] = self._dev(pv.bias(name + ".bias", c), F32)
-
-    def _norm(self, pv, name, c, keep_host=False):
-        g, b = pv.norm_weight(name + ".weight", c), pv.bias(name + ".bias", c)
-        if not keep_host:
-            self.w[name + ".weight"] = self._dev(g, F32)
-            self.w[name + ".bias"] = self._dev(b, F32)
-        return g, b
-
-    def _ln_linear(self, pv, norm_name, key, w: torch.Tensor, bias: Optional[torch.Tensor], c: int):
+    def _ln_linear(self, pk, norm_name, key, w: torch.Tensor, bias: Optional[torch.Tensor], c: int):
         """LayerNorm folded into the Linear that consumes it (``LB_GEMM_LN_A``): y = LN(x) W^T + b becomes
         rstd * (x W'^T - mean * colsum) + b' with W' = W diag(gamma) (rounded to fp16: the MFMA operand),
         colsum[n] = sum_k W'[n][k] (of the ROUNDED values) and b' = b + W beta.  ``key`` names the packed tensors."""
-        g, beta = self._norm(pv, norm_name, c, keep_host=not self.keep_ln_weights)
+        g, beta = pk.norm(norm_name, c, keep_host=not self.keep_ln_weights)
         if self.fuse_layernorm is False:        # stand-alone LayerNorms only: no folded copies of the weights in HBM
             return
         wf = (w.double() * g.double()[None, :]).to(torch.float16)
         self.w[key + ".weight"] = wf.to(self.device).contiguous()
-        self.w[key + ".colsum"] = self._dev(wf.double().sum(dim=1), F32)
+        self.w[key + ".colsum"] = pk.dev(wf.double().sum(dim=1), F32)
         b2 = w.double() @ beta.double()
         if bias is not None:
             b2 = b2 + bias.double()
-        self.w[key + ".bias"] = self._dev(b2, F32)
+        self.w[key + ".bias"] = pk.dev(b2, F32)
 
-    def _resnet(self, pv, p, cin, cout, temb_acc):
+    def _resnet(self, pk, p, cin, cout, temb_acc):
         T = self.cfg.time_embed_dim
-        self._norm(pv, p + ".norm1", cin)
-        self._conv(pv, p + ".conv1", cin, cout, 3)
-        tw = pv.weight(p + ".time_emb_proj.weight", (cout, T), T, 1.0)
-        tb = pv.bias(p + ".time_emb_proj.bias", cout)
+        pk.norm(p + ".norm1", cin)
+        pk.conv(p + ".conv1", cin, cout, 3)
+        tw = pk.pv.weight(p + ".time_emb_proj.weight", (cout, T), T, 1.0)
+        tb = pk.pv.bias(p + ".time_emb_proj.bias", cout)
         self.temb_slices[p] = (temb_acc["n"], cout)
         temb_acc["w"].append(tw)
         temb_acc["b"].append(tb)
         temb_acc["n"] += cout
-        self._norm(pv, p + ".norm2", cout)
-        self._conv(pv, p + ".conv2", cout, cout, 3, gain=0.5)
+        pk.norm(p + ".norm2", cout)
+        pk.conv(p + ".conv2", cout, cout, 3, gain=0.5)
         if cin != cout:
             # 1x1 shortcut as a plain GEMM on [tokens, cin]
-            w = pv.weight(p + ".conv_shortcut.weight", (cout, cin, 1, 1), cin, 1.0)
-            self.w[p + ".conv_shortcut.weight"] = self._dev(w.reshape(cout, cin), F16)
-            self.w[p + ".conv_shortcut.bias"] = self._dev(pv.bias(p + ".conv_shortcut.bias", cout), F32)
+            w = pk.pv.weight(p + ".conv_shortcut.weight", (cout, cin, 1, 1), cin, 1.0)
+            self.w[p + ".conv_shortcut.weight"] = pk.dev(w.reshape(cout, cin), F16)
+            self.w[p + ".conv_shortcut.bias"] = pk.dev(pk.pv.bias(p + ".conv_shortcut.bias", cout), F32)
 
-    def _transformer(self, pv, p, c, depth, ctx_acc):
+    def _transformer(self, pk, p, c, depth, ctx_acc):
         X = self.cfg.cross_dim
-        self._norm(pv, p + ".norm", c)
-        self._linear(pv, p + ".proj_in", c, c)
+        pk.norm(p + ".norm", c)
+        pk.linear(p + ".proj_in", c, c)
         for d in range(depth):
             b = f"{p}.transformer_blocks.{d}"
-            q = self._linear(pv, b + ".attn1.to_q", c, c, bias=False, keep_host=True)
-            k = self._linear(pv, b + ".attn1.to_k", c, c, bias=False, keep_host=True)
-            v = self._linear(pv, b + ".attn1.to_v", c, c, bias=False, keep_host=True)
+            q = pk.linear(b + ".attn1.to_q", c, c, bias=False, keep_host=True)
+            k = pk.linear(b + ".attn1.to_k", c, c, bias=False, keep_host=True)
+            v = pk.linear(b + ".attn1.to_v", c, c, bias=False, keep_host=True)
             qkv = torch.cat([q, k, v], 0)                                             # one [3C, C] projection
             if self.keep_ln_weights:
-                self.w[b + ".attn1.qkv"] = self._dev(qkv, F16)
-            self._ln_linear(pv, b + ".norm1", b + ".attn1.qkv_ln", qkv, None, c)
-            self._linear(pv, b + ".attn1.to_out.0", c, c, gain=0.5)
-            q2 = self._linear(pv, b + ".attn2.to_q", c, c, bias=False, keep_host=not self.keep_ln_weights)
-            self._ln_linear(pv, b + ".norm2", b + ".attn2.to_q_ln", q2, None, c)
-            ck = self._linear(pv, b + ".attn2.to_k", X, c, bias=False, keep_host=True)
-            cv = self._linear(pv, b + ".attn2.to_v", X, c, bias=False, keep_host=True)
+                self.w[b + ".attn1.qkv"] = pk.dev(qkv, F16)
+            self._ln_linear(pk, b + ".norm1", b + ".attn1.qkv_ln", qkv, None, c)
+            pk.linear(b + ".attn1.to_out.0", c, c, gain=0.5)
+            q2 = pk.linear(b + ".attn2.to_q", c, c, bias=False, keep_host=not self.keep_ln_weights)
+            self._ln_linear(pk, b + ".norm2", b + ".attn2.to_q_ln", q2, None, c)
+            ck = pk.linear(b + ".attn2.to_k", X, c, bias=False, keep_host=True)
+            cv = pk.linear(b + ".attn2.to_v", X, c, bias=False, keep_host=True)
             self.ctx_slices[b] = (ctx_acc["n"], c)
             ctx_acc["k"].append(ck)
             ctx_acc["v"].append(cv)
             ctx_acc["n"] += c
-            self._linear(pv, b + ".attn2.to_out.0", c, c, gain=0.5)
-            ff = self._linear(pv, b + ".ff.net.0.proj", c, 8 * c, keep_host=not self.keep_ln_weights)
-            ffb = pv.bias(b + ".ff.net.0.proj.bias", 8 * c)                   # (same seeded tensor _linear stored)
-            self._ln_linear(pv, b + ".norm3", b + ".ff.net.0.proj_ln", ff, ffb, c)
-            self._linear(pv, b + ".ff.net.2", 4 * c, c, gain=0.5)
-        self._linear(pv, p + ".proj_out", c, c, gain=0.5)
+            pk.linear(b + ".attn2.to_out.0", c, c, gain=0.5)
+            ff = pk.linear(b + ".ff.net.0.proj", c, 8 * c, keep_host=not self.keep_ln_weights)
+            ffb = pk.pv.bias(b + ".ff.net.0.proj.bias", 8 * c)                   # (same seeded tensor linear stored)
+            self._ln_linear(pk, b + ".norm3", b + ".ff.net.0.proj_ln", ff, ffb, c)
+            pk.linear(b + ".ff.net.2", 4 * c, c, gain=0.5)
+        pk.linear(p + ".proj_out", c, c, gain=0.5)
 
     def skip_channels(self) -> List[int]:
         ch = self.cfg.block_channels
@@ -238,49 +165,49 @@ class NativeUNet:
         return plan
 
     def _load(self, pv):
-        cfg = self.cfg
+        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
         ch, T = cfg.block_channels, cfg.time_embed_dim
         temb_acc = {"w": [], "b": [], "n": 0}
         ctx_acc = {"k": [], "v": [], "n": 0}
-        self._conv(pv, "conv_in", cfg.in_channels, ch[0], 3)
+        pk.conv("conv_in", cfg.in_channels, ch[0], 3)
         if cfg.time_cond_proj_dim is not None:
             # guidance-distilled UNets (LCM-SDXL and its kin): the guidance-scale embedding is projected onto the timestep
             # sinusoid in front of linear_1 (diffusers TimestepEmbedding.cond_proj: Linear(time_cond_proj_dim, C0, bias=False))
             if cfg.time_cond_proj_dim <= 0 or cfg.time_cond_proj_dim % 8:
                 raise ValueError(f"UNetConfig.time_cond_proj_dim must be a positive multiple of 8 (got {cfg.time_cond_proj_dim})")
-            self._linear(pv, "time_embedding.cond_proj", cfg.time_cond_proj_dim, ch[0], bias=False)
-        self._linear(pv, "time_embedding.linear_1", ch[0], T)
-        self._linear(pv, "time_embedding.linear_2", T, T)
-        self._linear(pv, "add_embedding.linear_1", cfg.add_in_dim, T)
-        self._linear(pv, "add_embedding.linear_2", T, T)
+            pk.linear("time_embedding.cond_proj", cfg.time_cond_proj_dim, ch[0], bias=False)
+        pk.linear("time_embedding.linear_1", ch[0], T)
+        pk.linear("time_embedding.linear_2", T, T)
+        pk.linear("add_embedding.linear_1", cfg.add_in_dim, T)
+        pk.linear("add_embedding.linear_2", T, T)
         prev = ch[0]
         for bi, c in enumerate(ch):
             for li in range(cfg.layers_per_block):
-                self._resnet(pv, f"down_blocks.{bi}.resnets.{li}", prev, c, temb_acc)
+                self._resnet(pk, f"down_blocks.{bi}.resnets.{li}", prev, c, temb_acc)
                 if cfg.transformer_depth[bi]:
-                    self._transformer(pv, f"down_blocks.{bi}.attentions.{li}", c, cfg.transformer_depth[bi], ctx_acc)
+                    self._transformer(pk, f"down_blocks.{bi}.attentions.{li}", c, cfg.transformer_depth[bi], ctx_acc)
                 prev = c
             if bi < len(ch) - 1:
-                self._conv(pv, f"down_blocks.{bi}.downsamplers.0.conv", c, c, 3)
+                pk.conv(f"down_blocks.{bi}.downsamplers.0.conv", c, c, 3)
         c = ch[-1]
-        self._resnet(pv, "mid_block.resnets.0", c, c, temb_acc)
-        self._transformer(pv, "mid_block.attentions.0", c, cfg.transformer_depth[-1], ctx_acc)
-        self._resnet(pv, "mid_block.resnets.1", c, c, temb_acc)
+        self._resnet(pk, "mid_block.resnets.0", c, c, temb_acc)
+        self._transformer(pk, "mid_block.attentions.0", c, cfg.transformer_depth[-1], ctx_acc)
+        self._resnet(pk, "mid_block.resnets.1", c, c, temb_acc)
         depths = list(reversed(cfg.transformer_depth))
         for ui, (c, cins) in enumerate(self.up_plan()):
             for li, (hid, skip) in enumerate(cins):
-                self._resnet(pv, f"up_blocks.{ui}.resnets.{li}", hid + skip, c, temb_acc)
+                self._resnet(pk, f"up_blocks.{ui}.resnets.{li}", hid + skip, c, temb_acc)
                 if depths[ui]:
-                    self._transformer(pv, f"up_blocks.{ui}.attentions.{li}", c, depths[ui], ctx_acc)
+                    self._transformer(pk, f"up_blocks.{ui}.attentions.{li}", c, depths[ui], ctx_acc)
             if ui < len(ch) - 1:
-                self._upconv(pv, f"up_blocks.{ui}.upsamplers.0.conv", c)
-        self._norm(pv, "conv_norm_out", ch[0])
-        self._conv(pv, "conv_out", ch[0], cfg.out_channels, 3, gain=0.5)
+                pk.upconv(f"up_blocks.{ui}.upsamplers.0.conv", c)
+        pk.norm("conv_norm_out", ch[0])
+        pk.conv("conv_out", ch[0], cfg.out_channels, 3, gain=0.5)
         # fused projections
-        self.w["temb_proj.weight"] = self._dev(torch.cat(temb_acc["w"], 0), F16)
-        self.w["temb_proj.bias"] = self._dev(torch.cat(temb_acc["b"], 0), F32)
+        self.w["temb_proj.weight"] = pk.dev(torch.cat(temb_acc["w"], 0), F16)
+        self.w["temb_proj.bias"] = pk.dev(torch.cat(temb_acc["b"], 0), F32)
         # every cross-attention K projection, then every V projection, of the text context: ONE [2 n_ctx, X] weight
-        self.w["ctx_kv.weight"] = self._dev(torch.cat(ctx_acc["k"] + ctx_acc["v"], 0), F16)
+        self.w["ctx_kv.weight"] = pk.dev(torch.cat(ctx_acc["k"] + ctx_acc["v"], 0), F16)
         self.n_temb, self.n_ctx = temb_acc["n"], ctx_acc["n"]
 
     def weight_bytes(self) -> int:
@@ -293,31 +220,22 @@ class NativeUNet:
         return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
 
 
-class UNetProgram:
+class UNetProgram(RecordedProgram):
     """One recorded forward for a fixed (batch, latent size).  Inputs are device buffers the
-    caller fills (torch copies on the launch stream); ``run`` replays the launches.
-    ``L``: latent side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for square programs (else None).  ``ragged_halo``: a
-    non-square program may send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo
-    kernel (``geometry.use_ragged_halo``); a square program records what it always recorded.
+    caller fills (torch copies on the launch stream); ``run`` replays the launches.  ``L`` / ``ragged_halo``: ``RecordedProgram``.
     ``marks``: one ``Mark`` per emission unit (``aug`` and ``ctx_kv`` of the conditioning program; ``temb_all``, ``conv_in``, every
     resnet / transformer / downsampler / upsampler by its weight prefix, and ``eps``); ``tap_names`` maps the block taps of the
-    oracle (``conv_in``, ``down0`` .., ``mid``, ``up0`` ..) to the unit whose output they are.  ``capture()`` fills ``taps``."""
+    oracle (``conv_in``, ``down0`` .., ``mid``, ``up0`` ..) to the unit whose output they are.  ``capture()`` fills ``taps`` from the
+    inputs ``set_conditioning`` / ``forward`` left in the buffers (fp16, NHWC for feature maps) and leaves ``eps`` as a ``forward`` would."""
 
     def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False):
         cfg = net.cfg
         H, W = latent_hw(L)
         check_unet_latent_size(H, W, len(cfg.block_channels))
-        self.net, self.B, self.H, self.W = net, B, H, W
-        self.L = H if H == W else None
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
         # LayerNorm handling of THIS program ("auto": fold into the consumers only where the program is launch-bound)
         self.ln_mode = net.fuse_layernorm if net.fuse_layernorm != "auto" else (B * max(H // 4, 1) * max(W // 4, 1) <= 1024)
         dev = net.device
-        self.arena = Arena(dev, journal=journal)
-        self.em = Emitter(self.arena)
-        self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
-        self.marks: List[Mark] = []
-        self.tap_names: Dict[str, str] = {}
-        self.persistent: List[torch.Tensor] = []       # arena tensors that stay live after emission
         T = cfg.time_embed_dim
         # ---- inputs / outputs (persistent) ----
         self.x_in = torch.zeros(B, cfg.in_channels, H, W, dtype=F16, device=dev)
@@ -333,34 +251,16 @@ class UNetProgram:
         self.ctx_kv = torch.zeros(B * CTX_PAD, 2 * net.n_ctx, dtype=F16, device=dev)   # [K of all blocks | V of all blocks]
         self.prog_cond = Program("unet-cond")
         self.prog_step = Program("unet-step")
-        with self.prog_cond.record(), self.arena.clocked(self.prog_cond):
-            self._rec = self.prog_cond
+        with self._recording(self.prog_cond):
             self._emit_cond()
-        with self.prog_step.record(), self.arena.clocked(self.prog_step):
-            self._rec = self.prog_step
+        with self._recording(self.prog_step):
             self._emit_step()
-        self._rec = None
-        self.taps: Dict[str, torch.Tensor] = {}
-
-    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
-        self.marks.append(Mark(name, kind, self._rec.name, self._rec.num_ops, out, tuple(inputs)))
-        return name
-
-    def capture(self) -> Dict[str, torch.Tensor]:
-        """Replay both programs on the inputs the buffers hold now (``set_conditioning`` / ``forward`` filled them), unit by unit,
-        and keep a clone of every unit's output in ``taps`` (fp16, NHWC for feature maps), also under the block-tap names of
-        ``tap_names``.  Leaves ``eps`` as a ``forward`` would."""
-        taps = capture_marks({p.name: p for p in (self.prog_cond, self.prog_step)}, self.marks)
-        for tap, unit in self.tap_names.items():
-            taps[tap] = taps[unit]
-        self.taps = taps
-        return taps
 
     # ---- helpers ------------------------------------------------------------------------
     def _conv(self, x, name, B, H, W, cin, cout, *, stride=1, ups=0, rowvec=None, ld_rowvec=None,
               residual=None, out=None, flags=0, k=3, pad=1):
         em, w = self.em, self.net.w
-        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
+        cin_p, cout_p = pad_to(cin, 8), pad_to(cout, 4)
         g = lib.ConvGeom(H, W, cin_p, k, k, stride=stride, pad=pad, ups=ups)
         ho, wo = g.Hout, g.Wout
         if out is None:
@@ -510,7 +410,7 @@ class UNetProgram:
         self.persistent.append(self.temb_all)
         self._mark("temb_all", "temb_all", self.temb_all, "tvals", "aug", *(("timestep_cond",) if self.timestep_cond is not None else ()))
         # input: NCHW latent -> NHWC (channels padded to 8)
-        cin_p = _pad(cfg.in_channels, 8)
+        cin_p = pad_to(cfg.in_channels, 8)
         x8 = ar.alloc((B, self.H, self.W, cin_p))
         api.lb_nchw_to_nhwc_f16(self.x_in.data_ptr(), x8.data_ptr(), B, cfg.in_channels, self.H * self.W, cin_p, 1.0, _stream())
         h, _, _ = self._conv(x8, "conv_in", B, self.H, self.W, cfg.in_channels, ch[0])
@@ -587,7 +487,7 @@ class UNetProgram:
         o, _, _ = self._conv(n, "conv_out", B, sh, sw, ch[0], cfg.out_channels)
         ar.release(n)
         api.lb_nhwc_to_nchw_f16(o.data_ptr(), self.eps.data_ptr(), B, cfg.out_channels, self.H * self.W,
-                                _pad(cfg.out_channels, 4), _stream())
+                                pad_to(cfg.out_channels, 4), _stream())
         ar.release(o)
         self._mark("eps", "out", self.eps, at)
 
@@ -620,7 +520,3 @@ class UNetProgram:
         self.tvals.copy_(tvals.reshape(-1, 1).to(F32))
         self.prog_step.launch()
         return self.eps
-
-    def enable_graphs(self):
-        self.prog_cond.instantiate()
-        self.prog_step.instantiate()

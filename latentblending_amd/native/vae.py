@@ -21,15 +21,14 @@ Output is quantised on device to uint8 NHWC frames.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, Tuple
 
 import torch
 
 from ..hip import lib
 from ..hip.lib import api
-from .geometry import latent_hw
-from .runtime import Arena, Emitter, Program, F16, F32, _stream
-from .unet import Mark, _pad, capture_marks
+from .runtime import Program, RecordedProgram, F16, F32, _stream
+from .weights import Packer, pad_to
 
 STREAM_SCALE = 1.0 / 16.0
 
@@ -58,76 +57,48 @@ class NativeVAEDecoder:
         self.w: Dict[str, torch.Tensor] = {}
         self._load(provider)
 
-    def _dev(self, t, dtype):
-        return t.to(device=self.device, dtype=dtype).contiguous()
-
-    def _conv(self, pv, name, cin, cout, k, gain=1.0):
-        w = pv.weight(name + ".weight", (cout, cin, k, k), cin * k * k, gain)
-        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
-        packed = torch.zeros(cout_p, k, k, cin_p, dtype=torch.float32)
-        packed[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
-        self.w[name + ".weight"] = self._dev(packed.reshape(cout_p, k * k * cin_p), F16)
-        b = torch.zeros(cout_p, dtype=torch.float32)
-        b[:cout] = pv.bias(name + ".bias", cout)
-        self.w[name + ".bias"] = self._dev(b, F32)
-
-    def _upconv(self, pv, name, c):
-        from ..hip.ops import subpixel_upsample_weights
-        w = pv.weight(name + ".weight", (c, c, 3, 3), c * 9, 1.0)
-        subs = subpixel_upsample_weights(w, _pad(c, 8))
-        for (py, px), k in subs.items():
-            self.w[f"{name}.weight.sub{py}{px}"] = k.to(self.device)
-        # the same four kernels stacked [4][N][4 Cin] (parity py*2+px) for the one-launch halo form
-        self.w[f"{name}.weight.sub4"] = torch.stack([subs[(0, 0)], subs[(0, 1)], subs[(1, 0)], subs[(1, 1)]]).to(self.device).contiguous()
-        self.w[name + ".bias"] = self._dev(pv.bias(name + ".bias", c), F32)
-
-    def _norm(self, pv, name, c):
-        self.w[name + ".weight"] = self._dev(pv.norm_weight(name + ".weight", c), F32)
-        self.w[name + ".bias"] = self._dev(pv.bias(name + ".bias", c), F32)
-
-    def _resnet(self, pv, p, cin, cout):
-        self._norm(pv, p + ".norm1", cin)
-        self._conv(pv, p + ".conv1", cin, cout, 3)
-        self._norm(pv, p + ".norm2", cout)
-        self._conv(pv, p + ".conv2", cout, cout, 3, gain=0.5)
+    def _resnet(self, pk, p, cin, cout):
+        pk.norm(p + ".norm1", cin)
+        pk.conv(p + ".conv1", cin, cout, 3)
+        pk.norm(p + ".norm2", cout)
+        pk.conv(p + ".conv2", cout, cout, 3, gain=0.5)
         if cin != cout:
-            w = pv.weight(p + ".conv_shortcut.weight", (cout, cin, 1, 1), cin, 1.0)
-            self.w[p + ".conv_shortcut.weight"] = self._dev(w.reshape(cout, cin), F16)
-            self.w[p + ".conv_shortcut.bias"] = self._dev(pv.bias(p + ".conv_shortcut.bias", cout), F32)
+            w = pk.pv.weight(p + ".conv_shortcut.weight", (cout, cin, 1, 1), cin, 1.0)
+            self.w[p + ".conv_shortcut.weight"] = pk.dev(w.reshape(cout, cin), F16)
+            self.w[p + ".conv_shortcut.bias"] = pk.dev(pk.pv.bias(p + ".conv_shortcut.bias", cout), F32)
 
     def _load(self, pv):
-        cfg = self.cfg
+        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
         rev = list(reversed(cfg.block_channels))
         top = rev[0]
-        self._conv(pv, "post_quant_conv", cfg.latent_channels, cfg.latent_channels, 1)
-        self._conv(pv, "decoder.conv_in", cfg.latent_channels, top, 3)
-        self._resnet(pv, "decoder.mid_block.resnets.0", top, top)
+        pk.conv("post_quant_conv", cfg.latent_channels, cfg.latent_channels, 1)
+        pk.conv("decoder.conv_in", cfg.latent_channels, top, 3)
+        self._resnet(pk, "decoder.mid_block.resnets.0", top, top)
         a = "decoder.mid_block.attentions.0"
-        self._norm(pv, a + ".group_norm", top)
-        for nm in ("to_q", "to_k"):
-            self.w[f"{a}.{nm}.weight"] = self._dev(pv.weight(f"{a}.{nm}.weight", (top, top), top), F16)
-            self.w[f"{a}.{nm}.bias"] = self._dev(pv.bias(f"{a}.{nm}.bias", top), F32)
+        pk.norm(a + ".group_norm", top)
+        pk.linear(a + ".to_q", top, top)
+        pk.linear(a + ".to_k", top, top)
         wv = pv.weight(a + ".to_v.weight", (top, top), top)
         bv = pv.bias(a + ".to_v.bias", top)
         wo = pv.weight(a + ".to_out.0.weight", (top, top), top, 0.5)
         bo = pv.bias(a + ".to_out.0.bias", top)
-        self.w[a + ".to_v.weight"] = self._dev(wv, F16)
-        self.w[a + ".to_out.0.weight"] = self._dev(wo, F16)
-        self.w[a + ".to_out.0.bias"] = self._dev(bo + wo.half().float() @ bv, F32)   # V bias folded
+        self.w[a + ".to_v.weight"] = pk.dev(wv, F16)
+        self.w[a + ".to_out.0.weight"] = pk.dev(wo, F16)
+        self.w[a + ".to_out.0.bias"] = pk.dev(bo + wo.half().float() @ bv, F32)   # V bias folded
         if top == 512:                      # fused form: ONE q | k | v projection feeding lb_attn_fwd_d512 (V bias folded as above)
             self.w[a + ".qkv.weight"] = torch.cat([self.w[a + ".to_q.weight"], self.w[a + ".to_k.weight"], self.w[a + ".to_v.weight"]], 0).contiguous()
             self.w[a + ".qkv.bias"] = torch.cat([self.w[a + ".to_q.bias"], self.w[a + ".to_k.bias"],
                                                  torch.zeros_like(self.w[a + ".to_q.bias"])], 0).contiguous()
-        self._resnet(pv, "decoder.mid_block.resnets.1", top, top)
+        self._resnet(pk, "decoder.mid_block.resnets.1", top, top)
         prev = top
         for ui, c in enumerate(rev):
             for li in range(cfg.layers_per_block + 1):
-                self._resnet(pv, f"decoder.up_blocks.{ui}.resnets.{li}", prev, c)
+                self._resnet(pk, f"decoder.up_blocks.{ui}.resnets.{li}", prev, c)
                 prev = c
             if ui < len(rev) - 1:
-                self._upconv(pv, f"decoder.up_blocks.{ui}.upsamplers.0.conv", c)
-        self._norm(pv, "decoder.conv_norm_out", rev[-1])
-        self._conv(pv, "decoder.conv_out", rev[-1], cfg.out_channels, 3, gain=0.5)
+                pk.upconv(f"decoder.up_blocks.{ui}.upsamplers.0.conv", c)
+        pk.norm("decoder.conv_norm_out", rev[-1])
+        pk.conv("decoder.conv_out", rev[-1], cfg.out_channels, 3, gain=0.5)
         for key in [k for k in self.w if k.endswith(".bias")]:          # biases in stream units (x 2^-4, exact)
             self.w[key + "_s"] = self.w[key] * STREAM_SCALE
 
@@ -137,53 +108,32 @@ class NativeVAEDecoder:
         return VAEProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
 
 
-class VAEProgram:
-    """One recorded decode for a fixed (batch, latent size): ``L`` = a side or ``(H, W)``; ``.H`` / ``.W`` always, ``.L`` for
-    square programs (else None).  ``ragged_halo`` as in ``UNetProgram``.
+class VAEProgram(RecordedProgram):
+    """One recorded decode for a fixed (batch, latent size); ``L`` / ``ragged_halo``: ``RecordedProgram``.
     ``marks``: one ``Mark`` per emission unit (``conv_in`` = post_quant_conv + conv_in, every resnet and upsampler by its weight
     prefix, ``mid_attention``, ``image_f32``); ``tap_names`` maps the oracle's block taps (``mid``, ``up0`` ..) to units;
     ``capture()`` fills ``taps``."""
 
     def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
-        cfg = net.cfg
-        H, W = latent_hw(L)
-        self.net, self.B, self.H, self.W = net, B, H, W
-        self.L = H if H == W else None
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+        cfg, H, W = net.cfg, self.H, self.W
         self.scaled = bool(cfg.stream_fp16_scaled)
         self.fuse_gn_stats = bool(getattr(cfg, "fuse_gn_stats", True))
         self.fused_mid_attention = bool(getattr(cfg, "fused_mid_attention", True))
         dev = net.device
-        self.arena = Arena(dev, journal=journal)
-        self.em = Emitter(self.arena)
-        self.ragged_halo = self.em.ragged_halo = bool(ragged_halo) and H != W
-        self.marks: List[Mark] = []
-        self.tap_names: Dict[str, str] = {}
-        self.persistent: List[torch.Tensor] = []       # arena tensors that stay live after emission: none
-        self.taps: Dict[str, torch.Tensor] = {}
         SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
         self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
         self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
-        self.image_f32 = torch.zeros(B, SH, SW, _pad(cfg.out_channels, 4), dtype=F32, device=dev)
-        self._pq = torch.zeros(B, H, W, _pad(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
+        self.image_f32 = torch.zeros(B, SH, SW, pad_to(cfg.out_channels, 4), dtype=F32, device=dev)
+        self._pq = torch.zeros(B, H, W, pad_to(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
         self.prog = Program("vae-decode")
-        with self.prog.record(), self.arena.clocked(self.prog):
+        with self._recording(self.prog):
             self._emit()
 
-    def _mark(self, name: str, kind: str, out: torch.Tensor, *inputs: str) -> str:
-        self.marks.append(Mark(name, kind, self.prog.name, self.prog.num_ops, out, tuple(inputs)))
-        return name
-
     def capture(self) -> Dict[str, torch.Tensor]:
-        """Replay the program on the latent ``z_in`` holds now, unit by unit, and keep a clone of every unit's output in ``taps``
-        (NHWC), also under the block-tap names of ``tap_names``.  Stream tensors come back in real units as fp32: the 2^-4 of the
-        scaled fp16 stream is undone (exactly).  Leaves ``frames`` / ``image_f32`` as a ``decode`` would."""
-        def real(m, t):
-            return t.float() / STREAM_SCALE if (self.scaled and m.kind != "out") else t
-        taps = capture_marks({self.prog.name: self.prog}, self.marks, real)
-        for tap, unit in self.tap_names.items():
-            taps[tap] = taps[unit]
-        self.taps = taps
-        return taps
+        """``RecordedProgram.capture`` on the latent ``z_in`` holds now (taps are NHWC).  Stream tensors come back in real units as
+        fp32: the 2^-4 of the scaled fp16 stream is undone (exactly).  Leaves ``frames`` / ``image_f32`` as a ``decode`` would."""
+        return super().capture(lambda m, t: t.float() / STREAM_SCALE if (self.scaled and m.kind != "out") else t)
 
     # ---- residual-stream format --------------------------------------------------------------
     # scaled (default): stream tensors hold value * 2^-4 in fp16;  f32: plain fp32 (see module docstring)
@@ -201,7 +151,7 @@ class VAEProgram:
     def _stream_conv_args(self, H, W, cin, residual):
         """(flags, geometry) of a stream conv: the one copy ``_gn_for_conv`` plans with and ``_stream_conv`` launches."""
         flags = 0 if self.scaled else (lib.GEMM_OUT_F32 | (lib.GEMM_RES_F32 if residual else 0))
-        return flags, lib.ConvGeom.conv3x3(H, W, _pad(cin, 8))
+        return flags, lib.ConvGeom.conv3x3(H, W, pad_to(cin, 8))
 
     def _gn_for_conv(self, x, norm, silu, name, B, H, W, cin, *, residual=False):
         """The GroupNorm ``norm`` of ``x`` whose only consumer is the stream conv ``name``: emitted here (see ``Emitter.gn_operand``:
@@ -217,7 +167,7 @@ class VAEProgram:
         """3x3 conv whose output goes to the residual stream (or feeds only the next GroupNorm).  ``gn`` = what ``_gn_for_conv``
         returned for this conv: it consumes GroupNorm(x)."""
         w, sc = self.net.w, self.scaled
-        cin_p, cout_p = _pad(cin, 8), _pad(cout, 4)
+        cin_p, cout_p = pad_to(cin, 8), pad_to(cout, 4)
         if out is None:
             out = self.arena.alloc((B, H, W, cout_p), F16 if sc else F32)
         flags, conv = self._stream_conv_args(H, W, cin, residual is not None)
@@ -324,7 +274,7 @@ class VAEProgram:
         sc = self.scaled
         rev = list(reversed(cfg.block_channels))
         top, lc = rev[0], cfg.latent_channels
-        lc_p = _pad(lc, 8)
+        lc_p = pad_to(lc, 8)
         z8 = ar.alloc((B, LH, LW, lc_p))
         api.lb_nchw_to_nhwc_f16(self.z_in.data_ptr(), z8.data_ptr(), B, lc, LH * LW, lc_p, 1.0 / cfg.scaling_factor,
                                 _stream())
@@ -362,7 +312,7 @@ class VAEProgram:
                 sh, sw = 2 * sh, 2 * sw
                 at = self._mark(name, "upsample", h, at)
             self.tap_names[f"up{ui}"] = at
-        conv_out = lib.ConvGeom.conv3x3(sh, sw, _pad(rev[-1], 8))
+        conv_out = lib.ConvGeom.conv3x3(sh, sw, pad_to(rev[-1], 8))
         g = em.gn_operand(h, w["decoder.conv_out.weight"], M=B * sh * sw, conv=conv_out, flags=lib.GEMM_OUT_F32,
                           **self._gn_args(h, "decoder.conv_norm_out", B, sh * sw, rev[-1], True))
         self._gn_done(h)
@@ -371,7 +321,7 @@ class VAEProgram:
         ar.release(h)
         self._mark("image_f32", "out", self.image_f32, at)
         api.lb_postprocess_u8(self.image_f32.data_ptr(), self.frames.data_ptr(), B * sh * sw,
-                              _pad(cfg.out_channels, 4), 1, _stream())
+                              pad_to(cfg.out_channels, 4), 1, _stream())
 
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """z [B,4,H,W] fp16 final latents (NOT yet divided by the scaling factor) -> uint8 [B,8H,8W,3]."""

@@ -13,6 +13,9 @@ diffusers state-dict name (``down_blocks.1.attentions.0.transformer_blocks.0.att
   output projections use gain 0.5 so that 70 stacked transformer blocks stay tame in fp16.
   Values are rounded to fp16 so every consumer (fp16 device path, fp32 CPU oracle) sees
   bit-identical parameters.  Seeds depend only on (name, seed): order independent.
+
+``Packer`` turns what a provider yields into the device tensors of a model's ``w``; ``pad_to`` is the channel padding it and the
+emitters share.
 """
 from __future__ import annotations
 
@@ -107,6 +110,67 @@ class SyntheticProvider:
 
     def positive(self, name: str, n: int) -> torch.Tensor:        # LPIPS lin layers (non-negative)
         return self._out(name, (n,), lambda: _seeded(name, (n,), 1.0, self.seed).abs() / n)
+
+
+def pad_to(n: int, m: int) -> int:
+    return (n + m - 1) // m * m
+
+
+class Packer:
+    """Packs what a provider yields into ``w`` (name -> tensor on ``device``) in the layouts the kernels read: the one place a
+    model's ``_load`` gets its device tensors from.  fp16 for MFMA operands, fp32 for biases and norm parameters."""
+
+    def __init__(self, provider, w: Dict[str, Optional[torch.Tensor]], device):
+        self.pv, self.w, self.device = provider, w, torch.device(device)
+
+    def dev(self, t: torch.Tensor, dtype) -> torch.Tensor:
+        return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def linear(self, name, cin, cout, bias=True, gain=1.0, keep_host=False) -> torch.Tensor:
+        """[cout][cin] fp16 + fp32 bias; returns the host weight (``keep_host``: the weight is NOT stored - the caller fuses it)."""
+        w = self.pv.weight(name + ".weight", (cout, cin), cin, gain)
+        if not keep_host:
+            self.w[name + ".weight"] = self.dev(w, torch.float16)
+        if bias:
+            self.w[name + ".bias"] = self.dev(self.pv.bias(name + ".bias", cout), torch.float32)
+        return w
+
+    def norm(self, name, c, keep_host=False):
+        g, b = self.pv.norm_weight(name + ".weight", c), self.pv.bias(name + ".bias", c)
+        if not keep_host:
+            self.w[name + ".weight"] = self.dev(g, torch.float32)
+            self.w[name + ".bias"] = self.dev(b, torch.float32)
+        return g, b
+
+    def conv(self, name, cin, cout, k, gain=1.0, bias=True, bias_shift=0.0, fold=False) -> None:
+        """[cout_p][k][k][cin_p] fp16 ((ky, kx, cin) order; cin padded to 8, cout to 4, with zeros) and an fp32 bias [cout_p].
+        ``bias=False``: no bias parameter - ``None`` is stored.  ``fold``: y -> 2 y - 1 folded into the conv (``W * 2``: exact in
+        fp16; ``b * 2 - 1``, also without a bias parameter)."""
+        w = self.pv.weight(name + ".weight", (cout, cin, k, k), cin * k * k, gain)
+        cin_p, cout_p = pad_to(cin, 8), pad_to(cout, 4)
+        packed = torch.zeros(cout_p, k, k, cin_p, dtype=torch.float32)
+        packed[:cout, :, :, :cin] = w.permute(0, 2, 3, 1)
+        b = torch.zeros(cout_p, dtype=torch.float32)
+        if bias:
+            b[:cout] = self.pv.bias(name + ".bias", cout)
+            if bias_shift:
+                b[:cout] += bias_shift
+        if fold:
+            packed, b = packed * 2.0, b * 2.0
+            b[:cout] -= 1.0
+        self.w[name + ".weight"] = self.dev(packed.reshape(cout_p, k * k * cin_p), torch.float16)
+        self.w[name + ".bias"] = self.dev(b, torch.float32) if (bias or fold) else None
+
+    def upconv(self, name, c) -> None:
+        """Upsampler conv (nearest-2x, then 3x3) stored as four 2x2 sub-pixel kernels (4/9 of the FLOPs)."""
+        from ..hip.ops import subpixel_upsample_weights
+        w = self.pv.weight(name + ".weight", (c, c, 3, 3), c * 9, 1.0)
+        subs = subpixel_upsample_weights(w, pad_to(c, 8))
+        for (py, px), k in subs.items():
+            self.w[f"{name}.weight.sub{py}{px}"] = k.to(self.device)
+        # the same four kernels stacked [4][N][4 Cin] (parity py*2+px) for the one-launch halo form
+        self.w[f"{name}.weight.sub4"] = torch.stack([subs[(0, 0)], subs[(0, 1)], subs[(1, 0)], subs[(1, 1)]]).to(self.device).contiguous()
+        self.w[name + ".bias"] = self.dev(self.pv.bias(name + ".bias", c), torch.float32)
 
 
 class DictProvider:
