@@ -8,6 +8,8 @@ makes those lines return the MI355X-native SDXL pipe, so the scripts run unchang
 * weights: HF-layout safetensors under ``$LB_WEIGHTS_DIR/{unet,vae}/`` when present (plus ``text_encoder/``,
   ``text_encoder_2/``, ``tokenizer*/`` for real prompt conditioning and ``lpips/`` for the real metric), otherwise
   seeded synthetic SDXL-shaped stand-ins, each announced with a ``UserWarning`` (no network / checkpoint here);
+* LoRA files: ``pipe.load_lora_weights(path, adapter_name=...)``, ``pipe.set_adapters(names, adapter_weights=...)`` and
+  ``pipe.unload_lora_weights()`` are methods of the returned pipe (``NativeSDXLPipe.load_lora`` and its kin);
 * if a real ``diffusers`` distribution exists further down ``sys.path`` it is loaded instead and
   this module gets out of the way.
 """
@@ -51,7 +53,7 @@ else:
             # text_encoder/ + text_encoder_2/ (+ tokenizer/, tokenizer_2/), and lpips/ = {alexnet*.safetensors | .pth ,
             # alex*.pth | lpips_lin*.safetensors} (torchvision AlexNet trunk + the lpips v0.1 linear layers)
             if root and os.path.isdir(os.path.join(root, "text_encoder")) and os.path.isdir(os.path.join(root, "text_encoder_2")):
-                kw["text_encoder_fn"] = N.NativeTextEncoders.from_dir(root).encode
+                kw["encoders"] = N.NativeTextEncoders.from_dir(root)      # (with their providers: LoRA adapters reach the towers)
             lp_dir = os.path.join(root, "lpips") if root else None
             if lp_dir and os.path.isdir(lp_dir):
                 kw["lpips_provider"] = _lpips_from_dir(N, lp_dir)

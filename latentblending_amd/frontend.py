@@ -64,6 +64,7 @@ class BlendingVariableHolder:
         self.jpg_quality = 80
         self.fp_movie = ''
         self.fp_json = ''
+        self.loras: List = []              # [(path, scale), ...]: LoRA adapters of the movie being edited (generate_movie, write_json)
 
     # ---- selections (gradio_ui.py:133-139) ----
     def preview_img_selected(self, data, button=None):
@@ -112,6 +113,9 @@ class BlendingVariableHolder:
         with self.session.bound() as be:
             header = {"settings": "sdxl", "width": be.dh.width_img, "height": be.dh.height_img,
                       "num_inference_steps": be.dh.num_inference_steps}
+        if self.loras:
+            from .replay import _loras_header
+            header["loras"] = _loras_header(self.loras)
         with open(self.fp_json, 'w') as f:
             json.dump([header] + list(self.data), f, indent=4)
 
@@ -161,10 +165,11 @@ class BlendingVariableHolder:
 
     # ---- gradio_ui.py:222-262: the chain over the edited list, one part per segment, concatenated ----
     def generate_movie(self, t_per_segment=10, fps: int = 30, movie_encoder: Optional[str] = None, movie_size=None,
-                       movie_resample: Optional[str] = None, noise: Optional[str] = None):
+                       movie_resample: Optional[str] = None, noise: Optional[str] = None, loras=None):
         """``movie_encoder``: "host" / "device" for the parts' ``write_movie_transition``; ``movie_size`` / ``movie_resample``: its
         ``size_output=(W, H)`` / ``resample=`` (None: the session's settings); ``noise``: "stream" / "counter" = the native pipe's
-        sampler noise for this movie (None: the session's ``noise``, else as the pipe stands)."""
+        sampler noise for this movie (None: the session's ``noise``, else as the pipe stands); ``loras``: ``[(path, scale), ...]`` =
+        the LoRA adapters of this movie (None: the holder's ``loras``, which ``write_json`` also puts into the JSON header)."""
         from .replay import run_multi_transition
         if len(self.data) < 2:
             raise ValueError("generate_movie: the movie needs at least two images (add_image_to_video)")
@@ -174,7 +179,8 @@ class BlendingVariableHolder:
             run_multi_transition(be, [it["prompt"] for it in self.data], [it["seed"] for it in self.data], self.fp_movie,
                                  duration_single_trans=t_per_segment,
                                  list_negative_prompts=[it["negative_prompt"] for it in self.data], fps=fps, dp_parts=self.dp_out,
-                                 movie_encoder=movie_encoder, movie_size=movie_size, movie_resample=movie_resample, noise=noise)
+                                 movie_encoder=movie_encoder, movie_size=movie_size, movie_resample=movie_resample, noise=noise,
+                                 loras=self.loras if loras is None else loras)
         print(f"DONE! MOVIE SAVED IN {self.fp_movie}")
         return self.fp_movie
 

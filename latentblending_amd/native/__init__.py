@@ -4,7 +4,9 @@ from .unet import NativeUNet, UNetConfig
 from .vae import NativeVAEDecoder, VAEConfig
 from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
 from .clip import CLIPTextConfig, NativeCLIPText, NativeTextEncoders
-from .weights import DictProvider, SyntheticProvider, from_safetensors, lpips_provider
+from .weights import DictProvider, LoRAProvider, SyntheticProvider, from_safetensors, lpips_provider
+from .lora import read_lora
 
 __all__ = ["NativeSDXLPipe", "StableDiffusionXLPipeline", "NativeUNet", "UNetConfig", "NativeVAEDecoder",
-           "VAEConfig", "NativeTinyVAEDecoder", "NativeTinyVAEEncoder", "TinyVAEConfig", "TinyVAEProgram", "TinyEncoderProgram", "DictProvider", "SyntheticProvider", "from_safetensors", "lpips_provider", "CLIPTextConfig", "NativeCLIPText", "NativeTextEncoders"]
+           "VAEConfig", "NativeTinyVAEDecoder", "NativeTinyVAEEncoder", "TinyVAEConfig", "TinyVAEProgram", "TinyEncoderProgram", "DictProvider", "SyntheticProvider", "from_safetensors", "lpips_provider", "CLIPTextConfig", "NativeCLIPText", "NativeTextEncoders",
+           "LoRAProvider", "read_lora"]

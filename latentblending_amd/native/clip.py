@@ -30,7 +30,7 @@ import torch
 from ..hip import lib
 from ..hip.lib import api
 from .runtime import Program, RecordedProgram, F16, F32, _stream
-from .weights import Packer
+from .weights import Packer, Reloadable
 
 MAX_TOKENS = 77
 
@@ -60,9 +60,10 @@ class CLIPTextConfig:
                               hidden_act="gelu", projection_dim=1280, pad_token_id=0)
 
 
-class NativeCLIPText:
+class NativeCLIPText(Reloadable):
     """One CLIP text tower.  ``forward(ids)`` -> (penultimate hidden states [B, 77, C] fp16,
-    projected EOS embedding [B, P] fp16 or None)."""
+    projected EOS embedding [B, P] fp16 or None).  ``reload(provider)`` (``weights.Reloadable``) rewrites the packed weights in
+    place: the cached programs keep working."""
 
     def __init__(self, cfg: CLIPTextConfig, provider, device="cuda", prefix: Optional[str] = None):
         assert cfg.hidden_size % 64 == 0 and cfg.hidden_size // cfg.num_attention_heads == 64, "head_dim must be 64"
@@ -73,7 +74,13 @@ class NativeCLIPText:
             state = getattr(provider, "state", None) or {}
             base = getattr(provider, "prefix", "")
             prefix = "" if (base + "embeddings.token_embedding.weight") in state else "text_model."
-        c, pv, p = cfg.hidden_size, provider, prefix
+        self.prefix = prefix
+        self._load(provider)
+        self._programs: Dict[int, "_CLIPProgram"] = {}
+
+    def _load(self, pv):
+        cfg, prefix = self.cfg, self.prefix
+        c, p = cfg.hidden_size, prefix
         dev = Packer(pv, self.w, self.device).dev
         self.w["tok"] = dev(pv.weight(p + "embeddings.token_embedding.weight", (cfg.vocab_size, c), c, c ** 0.5 * 0.02), F16)
         self.w["pos"] = dev(pv.weight(p + "embeddings.position_embedding.weight", (cfg.max_position_embeddings, c), c, c ** 0.5 * 0.01), F16)
@@ -97,7 +104,6 @@ class NativeCLIPText:
         if cfg.projection_dim:
             root = prefix[:-len("text_model.")] if prefix.endswith("text_model.") else prefix
             self.w["proj"] = dev(pv.weight(root + "text_projection.weight", (cfg.projection_dim, c), c), F16)
-        self._programs: Dict[int, "_CLIPProgram"] = {}
 
     def forward(self, ids: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """ids: [B, 77] integer token ids (any device)."""
@@ -223,9 +229,12 @@ class NativeTextEncoders:
     """Both SDXL text towers + tokenisers; ``encode`` is a ``text_encoder_fn`` for ``NativeSDXLPipe``."""
 
     def __init__(self, enc1: NativeCLIPText, enc2: NativeCLIPText, tokenizer1=None, tokenizer2=None,
-                 allow_synthetic: bool = False):
+                 allow_synthetic: bool = False, providers: Optional[Sequence] = None):
+        """``providers``: the two providers the towers were packed from - what ``pipe.load_lora`` needs to merge an adapter into
+        a tower and to unload it again (``from_dir`` keeps them)."""
         assert enc2.cfg.projection_dim, "the second tower must be a CLIPTextModelWithProjection"
         self.enc1, self.enc2 = enc1, enc2
+        self.providers = None if providers is None else tuple(providers)
         synthetic = tokenizer1 is None or tokenizer2 is None
         self.tok1 = tokenizer1 or HashTokenizer(enc1.cfg)
         self.tok2 = tokenizer2 or HashTokenizer(enc2.cfg)
@@ -237,8 +246,10 @@ class NativeTextEncoders:
     def from_dir(cls, root: str, device="cuda", **kw) -> "NativeTextEncoders":
         """HF layout: ``root/text_encoder``, ``root/text_encoder_2`` (safetensors), ``root/tokenizer``, ``root/tokenizer_2``."""
         from .weights import from_safetensors
-        e1 = NativeCLIPText(CLIPTextConfig.clip_l(), from_safetensors(os.path.join(root, "text_encoder")), device)
-        e2 = NativeCLIPText(CLIPTextConfig.openclip_bigg(), from_safetensors(os.path.join(root, "text_encoder_2")), device)
+        p1, p2 = from_safetensors(os.path.join(root, "text_encoder")), from_safetensors(os.path.join(root, "text_encoder_2"))
+        e1 = NativeCLIPText(CLIPTextConfig.clip_l(), p1, device)
+        e2 = NativeCLIPText(CLIPTextConfig.openclip_bigg(), p2, device)
+        kw.setdefault("providers", (p1, p2))
         toks = []
         for name in ("tokenizer", "tokenizer_2"):
             d = os.path.join(root, name)

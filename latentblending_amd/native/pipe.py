@@ -42,10 +42,19 @@ from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
 from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
-from .weights import SyntheticProvider
+from ..replay import lora_entries
+from .lora import COMPONENTS, TEXT_KEY_PREFIXES, LoRARecord, load_state, read_lora
+from .weights import LoRAProvider, SyntheticProvider
 
 F16, F32 = torch.float16, torch.float32
 NOISE_MODES = ("stream", "counter")
+
+
+class _Adapter:
+    """One loaded LoRA adapter: its normalised record, its scale, and the path it came from (None for a state dict)."""
+
+    def __init__(self, record: LoRARecord, scale: float, path):
+        self.record, self.scale, self.path = record, scale, path
 
 
 def _synthetic_embedding(text: str, shape, salt: int) -> torch.Tensor:
@@ -118,8 +127,13 @@ class StableDiffusionXLPipeline:
                  text_encoder_fn=None, unet_native: Optional[NativeUNet] = None,
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
                  scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
-                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream"):
-        """``noise``: "stream" (default) = per-step sampler noise (Euler-ancestral, LCM) drawn from a generator, as ever - the value an
+                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream", encoders=None, loras=None):
+        """``loras``: [(src, scale), ...] = LoRA adapters loaded right after construction, in order (``load_lora``).
+        ``encoders``: a ``clip.NativeTextEncoders``; its ``encode`` becomes ``text_encoder_fn`` (unless one is given) and, when it
+        carries the providers its towers were packed from, LoRA adapters reach the text towers too.  Adapters are merged from the
+        providers the pipe was built with (``unet_provider``, ``encoders.providers``): a pipe given a ready-made ``unet_native``
+        needs the provider that UNet was packed from beside it (``unet_provider=``) before ``load_lora`` can touch it.
+        ``noise``: "stream" (default) = per-step sampler noise (Euler-ancestral, LCM) drawn from a generator, as ever - the value an
         element receives depends on the draws before it; "counter" = counter-based noise (``native/noise.py``): every value is a
         function of (trajectory, step, element), so a seed renders the same whatever batch, order or rank serves the draw.
         ``pipe.noise`` switches it afterwards.  The START latents stay host-seeded under both.
@@ -164,7 +178,11 @@ class StableDiffusionXLPipeline:
         if lpips_provider is None:
             self._synthetic_notice("LPIPS-Alex weights (the branch-insertion metric is then NOT LPIPS)",
                                    "pass lpips_provider=native.lpips_provider(alexnet_state_dict, lpips_lin_state_dict)")
-        self.unet_native = unet_native or NativeUNet(self.unet_cfg, unet_provider or SyntheticProvider(seed), self.device)
+        # the base providers LoRA adapters are merged from (load_lora); None = a ready-made module whose provider nobody named
+        self._unet_provider = unet_provider if (unet_native is not None or unet_provider is not None) else SyntheticProvider(seed)
+        self.encoders = encoders
+        self._loras: "OrderedDict[str, _Adapter]" = OrderedDict()
+        self.unet_native = unet_native or NativeUNet(self.unet_cfg, self._unet_provider, self.device)
         self.vae_native = vae_native or NativeVAEDecoder(self.vae_cfg, vae_provider or SyntheticProvider(seed + 1), self.device)
         self.lpips_metric = NativeLPIPS(lpips_provider or SyntheticProvider(7), self.device)
         self.tiny_vae_native, self._tiny_vae_provider, self._tiny_seed = tiny_vae_native, tiny_vae_provider, seed + 2
@@ -175,7 +193,7 @@ class StableDiffusionXLPipeline:
         self.vae_scale_factor = self.vae_cfg.scale_factor
         self.default_sample_size = self.unet_cfg.sample_size
         self.text_encoder_2 = None
-        self.text_encoder_fn = text_encoder_fn
+        self.text_encoder_fn = text_encoder_fn if (text_encoder_fn is not None or encoders is None) else encoders.encode
         self._guidance_scale = 0.0 if turbo else 5.0
         self._guidance_rescale = 0.0
         self._clip_skip = None
@@ -211,6 +229,131 @@ class StableDiffusionXLPipeline:
         self._side_stream = None            # lazily created: conditioning programs of big batches run here beside the small anchor steps
         self._noise = "stream"
         self.noise = noise
+        for src, scale in lora_entries(loras):
+            self.load_lora(src, scale)
+
+    # ---- LoRA adapters --------------------------------------------------------------------
+    @property
+    def loras(self) -> "OrderedDict[str, float]":
+        """Loaded adapters in load order: name -> scale."""
+        return OrderedDict((n, a.scale) for n, a in self._loras.items())
+
+    def _lora_component(self, comp: str):
+        """(model, base provider, prefix of the adapters' names over the model's) of "unet" / "te1" / "te2"; the provider is None
+        when the pipe was not told it, the model is None when the pipe has no such component."""
+        if comp == "unet":
+            return self.unet_native, self._unet_provider, ""
+        enc = self.encoders
+        if enc is None:
+            return None, None, ""
+        tower = enc.enc1 if comp == "te1" else enc.enc2
+        base = None if enc.providers is None else enc.providers[0 if comp == "te1" else 1]
+        return tower, base, "" if tower.prefix.endswith("text_model.") else "text_model."
+
+    def _lora_check(self, comps) -> None:
+        for comp in comps:
+            net, base, _ = self._lora_component(comp)
+            if comp == "unet" and base is None:
+                raise ValueError("NativeSDXLPipe.load_lora: this pipe was given a ready-made unet_native without the provider it was packed "
+                                 "from, so there are no base weights to merge an adapter into; pass unet_provider=<that provider> beside "
+                                 "unet_native= (or let the pipe build the UNet from unet_provider=)")
+            if comp != "unet" and net is None:
+                raise ValueError(f"NativeSDXLPipe.load_lora: the adapter targets the text encoder '{comp}' but the pipe has no native text "
+                                 "towers; pass encoders=native.NativeTextEncoders.from_dir(<dir>) (or strict=False to leave these deltas out)")
+            if comp != "unet" and base is None:
+                raise ValueError(f"NativeSDXLPipe.load_lora: the adapter targets the text encoder '{comp}' but encoders= carries no providers; "
+                                 "build it with NativeTextEncoders(..., providers=(provider_1, provider_2)) or NativeTextEncoders.from_dir")
+
+    def _lora_apply(self, comps) -> None:
+        """Rebuild the merged provider of every component in ``comps`` from the adapters now loaded and reload that model in place."""
+        for comp in comps:
+            net, base, prefix = self._lora_component(comp)
+            if net is None:
+                continue
+            adapters = [(a.record.components[comp], a.scale) for a in self._loras.values() if a.record.components[comp]]
+            net.reload(LoRAProvider(base, adapters, prefix) if adapters else base)
+            if comp != "unet":
+                self._embed_cache.clear()               # embeddings of the towers as they were
+
+    def load_lora(self, src, scale: float = 1.0, name: Optional[str] = None, strict: bool = True) -> str:
+        """Merge the LoRA adapter ``src`` (a ``.safetensors`` file, a directory holding one, or a loaded state dict; ``lora.read_lora``
+        for the accepted namings) into the UNet and the text towers it targets, at ``scale``, on top of the adapters already loaded.
+        The packed weights are rewritten in place: every recorded program and instantiated graph keeps working.  Returns the
+        adapter's name (``name``, else the file's stem, else ``lora<k>``).  ``strict=False``: keys that resolve to nothing, and deltas
+        for text towers this pipe does not have, are left out."""
+        enc = self.encoders
+        state = load_state(src)
+        if enc is None:             # no towers to resolve text-encoder keys against: say so (or leave them out) before anything else
+            te_keys = [k for k in state if k.startswith(TEXT_KEY_PREFIXES)]
+            if te_keys and strict:
+                self._lora_check(("te1",))
+            state = {k: v for k, v in state.items() if k not in set(te_keys)}
+        rec = read_lora(state, unet_cfg=self.unet_cfg, te_cfgs=(enc.enc1.cfg, enc.enc2.cfg) if enc is not None else (None, None),
+                        strict=strict)
+        self._lora_check(rec.touched())
+        if name is None:
+            stem = os.path.splitext(os.path.basename(os.fspath(src)))[0] if isinstance(src, (str, os.PathLike)) else ""
+            name, k = stem or f"lora{len(self._loras)}", 0
+            while name in self._loras:
+                k += 1
+                name = f"{stem or 'lora'}_{k}"
+        elif name in self._loras:
+            raise ValueError(f"NativeSDXLPipe.load_lora: an adapter named '{name}' is loaded already ({list(self._loras)})")
+        self._loras[name] = _Adapter(rec, float(scale), src if isinstance(src, (str, os.PathLike)) else None)
+        try:
+            self._lora_apply(rec.touched())
+        except Exception:
+            del self._loras[name]
+            self._lora_apply(rec.touched())             # (a component reloaded before the failure goes back to what is loaded now)
+            raise
+        return name
+
+    def set_lora_scale(self, name: str, scale: float) -> None:
+        if name not in self._loras:
+            raise KeyError(f"NativeSDXLPipe.set_lora_scale: no adapter named '{name}' ({list(self._loras)})")
+        a = self._loras[name]
+        if float(scale) != a.scale:
+            a.scale = float(scale)
+            self._lora_apply(a.record.touched())
+
+    def unload_lora(self, name: Optional[str] = None) -> None:
+        """Unload one adapter, or all (``None``): the components it touched are reloaded from the base providers and what stays."""
+        if name is not None and name not in self._loras:
+            raise KeyError(f"NativeSDXLPipe.unload_lora: no adapter named '{name}' ({list(self._loras)})")
+        gone = [self._loras.pop(n) for n in ([name] if name is not None else list(self._loras))]
+        self._lora_apply([c for c in COMPONENTS if any(c in a.record.touched() for a in gone)])
+
+    # the names diffusers users type
+    def load_lora_weights(self, path, adapter_name: Optional[str] = None, **_):
+        self.load_lora(path, name=adapter_name)
+
+    def set_adapters(self, names, adapter_weights=None) -> None:
+        """diffusers' meaning: the named adapters are active at ``adapter_weights`` (default 1.0 each), every other one at 0."""
+        names = [names] if isinstance(names, str) else list(names)
+        weights = [1.0] * len(names) if adapter_weights is None else \
+            ([float(adapter_weights)] * len(names) if isinstance(adapter_weights, (int, float)) else [float(w) for w in adapter_weights])
+        if len(weights) != len(names):
+            raise ValueError("set_adapters: one weight per adapter name")
+        unknown = [n for n in names if n not in self._loras]
+        if unknown:
+            raise KeyError(f"set_adapters: no adapter named {unknown} ({list(self._loras)})")
+        want = dict(zip(names, weights))
+        changed = []
+        for n, a in self._loras.items():
+            s = want.get(n, 0.0)
+            if s != a.scale:
+                a.scale = s
+                changed += list(a.record.touched())
+        self._lora_apply([c for c in COMPONENTS if c in changed])
+
+    def unload_lora_weights(self) -> None:
+        self.unload_lora()
+
+    def fuse_lora(self, *_a, **_k) -> None:
+        """No-op: adapters are always merged into the packed weights here (there is no unfused low-rank side path to fuse)."""
+
+    def unfuse_lora(self, *_a, **_k) -> None:
+        """No-op, for the same reason: ``unload_lora_weights`` / ``set_adapters`` restore or rescale the merged weights."""
 
     def _synthetic_notice(self, what: str, how: str):
         if self.allow_synthetic or what in self._warned:

@@ -28,7 +28,7 @@ from ..hip import lib
 from ..hip.lib import api
 from .geometry import check_unet_latent_size, latent_hw
 from .runtime import Program, RecordedProgram, F16, F32, _stream
-from .weights import Packer, pad_to
+from .weights import Packer, Reloadable, pad_to
 
 CTX_TOKENS = 77
 CTX_PAD = 80
@@ -58,7 +58,7 @@ class UNetConfig:
         return self.pooled_dim + 6 * self.add_time_dim
 
 
-class NativeUNet:
+class NativeUNet(Reloadable):
     def __init__(self, cfg: UNetConfig, provider, device="cuda", fuse_layernorm="auto"):
         """``fuse_layernorm``: fold the three LayerNorms of every transformer block into the GEMMs that consume them
         (LB_GEMM_LN_A: no LayerNorm launch, no normalised copy of the hidden state).

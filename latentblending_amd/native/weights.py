@@ -13,6 +13,8 @@ diffusers state-dict name (``down_blocks.1.attentions.0.transformer_blocks.0.att
   output projections use gain 0.5 so that 70 stacked transformer blocks stay tame in fp16.
   Values are rounded to fp16 so every consumer (fp16 device path, fp32 CPU oracle) sees
   bit-identical parameters.  Seeds depend only on (name, seed): order independent.
+* ``LoRAProvider``      — wraps either and adds the low-rank deltas of loaded LoRA adapters to the weights it passes on
+  (``native/lora.py`` reads the files); ``Reloadable.reload`` puts what such a provider packs into a live model in place.
 
 ``Packer`` turns what a provider yields into the device tensors of a model's ``w``; ``pad_to`` is the channel padding it and the
 emitters share.
@@ -200,6 +202,92 @@ class DictProvider:
     def positive(self, name, n):
         t = self.state[self.prefix + name]
         return t.detach().to(torch.float32).reshape(n)
+
+
+class LoRAProvider:
+    """A provider that merges LoRA adapters into what ``base`` yields: ``weight(name, ...)`` returns
+
+        W + sum_j  s_j * (alpha_j / r_j) * up_j @ down_j
+
+    over the adapters that target ``name``, in load order, evaluated in float64 and rounded ONCE to float32 - so every layout the
+    ``Packer`` derives (qkv, the gamma-folded copies and their colsum, ctx_kv, temb_proj, packed convs, the sub-pixel kernels) is
+    that of the merged model.  ``adapters``: [(targets, scale), ...], ``targets`` = {parameter name: (down, up, alpha)} as
+    ``lora.read_lora`` gives them per component; a conv's ``down`` [r, cin, k, k] is flattened to [r, cin k k] and the product
+    reshaped to [cout, cin, k, k].  An adapter at scale 0 is SKIPPED, not multiplied by zero: the base tensor comes back bit for
+    bit.  ``prefix``: what the adapters' names carry in front of the names this provider is asked for (a text tower loaded without
+    its ``text_model.`` nesting).  ``bias``, ``norm_weight`` and ``positive`` pass through."""
+
+    def __init__(self, base, adapters, prefix: str = ""):
+        self.base, self.prefix = base, prefix
+        self.adapters = [(targets, float(scale)) for targets, scale in adapters]
+
+    def weight(self, name, shape, fan_in=0, gain=1.0):
+        w = self.base.weight(name, shape, fan_in, gain)
+        shape = tuple(int(v) for v in shape)
+        acc = None
+        for targets, scale in self.adapters:
+            hit = targets.get(self.prefix + name) if scale != 0.0 else None
+            if hit is None:
+                continue
+            down, up, alpha = hit
+            r = int(down.shape[0])
+            want = (r,) + shape[1:]
+            if tuple(down.shape) != want or tuple(up.shape[:2]) != (shape[0], r) or up.numel() != shape[0] * r:
+                raise ValueError(f"LoRA delta for '{self.prefix + name}' {shape}: down {tuple(down.shape)} / up {tuple(up.shape)} do not "
+                                 f"fit (expected {want} and {(shape[0], r)})")
+            if acc is None:
+                acc = w.to(torch.float64)
+            delta = up.to(torch.float64).reshape(shape[0], r) @ down.to(torch.float64).reshape(r, -1)
+            acc = acc + (scale * (float(alpha) / r)) * delta.reshape(shape)
+        return w if acc is None else acc.to(torch.float32)
+
+    def bias(self, name, n):
+        return self.base.bias(name, n)
+
+    def norm_weight(self, name, n):
+        return self.base.norm_weight(name, n)
+
+    def positive(self, name, n):
+        return self.base.positive(name, n)
+
+
+class Reloadable:
+    """In-place reload for a native model whose ``_load(provider)`` fills ``self.w``: recorded launch programs and their hipGraphs
+    hold raw pointers into ``self.w``, so new weights are COPIED INTO the live tensors - none is replaced, no program is dropped, an
+    instantiated graph replays against the new values."""
+
+    def reload(self, provider) -> None:
+        """Pack ``provider`` through the model's own ``_load`` into a scratch dict, refuse unless its keys, shapes and dtypes are
+        those of the live ``w``, synchronise the device, ``copy_`` tensor by tensor.  Until it returns the device holds a second
+        copy of the weights; it is freed (and handed back by the caching allocator) before the return."""
+        live = self.w
+        self.w = {}
+        try:
+            self._load(provider)
+            fresh = self.w
+        finally:
+            self.w = live
+        if list(fresh) != list(live):
+            odd = sorted(set(fresh) ^ set(live))
+            raise ValueError(f"{type(self).__name__}.reload: the provider packs other tensors than the live model holds ({odd[:4]} ...)")
+        for k, t in fresh.items():
+            have = live[k]
+            if (t is None) != (have is None) or (t is not None and (t.shape != have.shape or t.dtype != have.dtype)):
+                raise ValueError(f"{type(self).__name__}.reload: '{k}' is {None if t is None else (tuple(t.shape), t.dtype)} but the "
+                                 f"live tensor is {None if have is None else (tuple(have.shape), have.dtype)}")
+        cuda = self.device.type == "cuda"
+        if cuda:
+            torch.cuda.synchronize(self.device)         # launches that read the old weights may still be in flight
+        with torch.no_grad():
+            for k, t in fresh.items():
+                if t is not None:
+                    live[k].copy_(t)
+        if cuda:
+            torch.cuda.synchronize(self.device)
+        fresh.clear()
+        t = have = None
+        if cuda:
+            torch.cuda.empty_cache()
 
 
 def from_safetensors(path: str, prefix: str = "") -> DictProvider:

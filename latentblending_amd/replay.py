@@ -9,9 +9,10 @@ is that loop behind two calls, with the same observable order of engine calls (s
 trajectories and the part files are what the scripts produce), plus reader / writer of the JSON file
 the gradio UI saves (``gradio_ui.py:168-190``):
 
-    [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S},
+    [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S, "loras": [{"path": ..., "scale": ...}]},
       {"iteration": i, "seed": s, "prompt": "...", "negative_prompt": "...", "preview_image": ...}, ... ]
 
+``"loras"`` is optional: the LoRA adapters the whole movie is rendered under (paths relative to the JSON file).
 An item may also carry ``"image"`` (a picture file, path relative to the JSON file) and ``"image_strength"`` (default 0.5): that
 key frame is an image anchor (``BlendingEngine.set_anchor_image1`` / ``2``) instead of a picture invented from its prompt.
 
@@ -42,10 +43,31 @@ def load_movie_json(fp_json: str) -> Tuple[Dict, List[Dict]]:
     return header, items
 
 
-def save_movie_json(fp_json: str, be, items: Sequence[Dict]) -> None:
-    """Write the file the UI writes (gradio_ui.py:168-173): header from the engine's holder, then the items."""
+def lora_entries(loras) -> List[Tuple[object, float]]:
+    """``[(src, scale), ...]`` from what the drivers and the pipe's ``loras=`` accept: ``(src, scale)`` pairs, bare sources (scale 1)
+    and the movie JSON's ``{"path": ..., "scale": ...}`` items."""
+    out = []
+    for it in loras or ():
+        if isinstance(it, dict) and "path" in it:
+            out.append((it["path"], float(it.get("scale", 1.0))))
+        elif isinstance(it, (tuple, list)) and len(it) == 2:
+            out.append((it[0], float(it[1])))
+        else:
+            out.append((it, 1.0))
+    return out
+
+
+def _loras_header(loras) -> List[Dict]:
+    return [{"path": os.fspath(src), "scale": scale} for src, scale in lora_entries(loras)]
+
+
+def save_movie_json(fp_json: str, be, items: Sequence[Dict], loras: Optional[Sequence] = None) -> None:
+    """Write the file the UI writes (gradio_ui.py:168-173): header from the engine's holder, then the items.  ``loras``
+    (``[(path, scale), ...]``) goes into the header as ``"loras": [{"path": ..., "scale": ...}]`` - what ``run_movie_json`` loads."""
     header = {"settings": "sdxl", "width": be.dh.width_img, "height": be.dh.height_img,
               "num_inference_steps": be.dh.num_inference_steps}
+    if loras:
+        header["loras"] = _loras_header(loras)
     with open(fp_json, "w") as fh:
         json.dump([header] + [dict(it) for it in items], fh, indent=4)
 
@@ -57,7 +79,7 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
                          movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
                          list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None,
-                         noise: Optional[str] = None) -> List[List]:
+                         noise: Optional[str] = None, loras: Optional[Sequence] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -83,12 +105,16 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     ``noise``: "stream" / "counter" = the native pipe's ``noise`` for this chain (None: as the pipe stands); the previous value is
     restored afterwards.  Under "counter" a key frame's per-step noise depends on its seed alone, so the chain renders the same
     frames with and without ``pipeline_keyframes``, at any frontier width and under a farm of any size.
+    ``loras``: ``[(src, scale), ...]`` (or the movie JSON's ``{"path": ..., "scale": ...}`` items) = LoRA adapters the native pipe
+    loads for this chain (``pipe.load_lora``), once, before the first key frame, on top of what it has loaded; they are unloaded
+    again afterwards.  None: the pipe's adapters as they stand.  One set per chain: a recycled key frame rendered under other
+    scales would be a picture of another model.
     """
     images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
     if images is not None and pipeline_keyframes:
         raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
                          "it cannot be combined with image key frames (list_images)")
-    with _decoder_as(be, decoder), _noise_as(be, noise):
+    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras):
         try:
             return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
                                          keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
@@ -141,6 +167,25 @@ def _noise_as(be, noise: Optional[str]):
         yield
     finally:
         pipe.noise = previous
+
+
+@contextlib.contextmanager
+def _loras_as(be, loras):
+    """Run the body with ``loras`` loaded into the engine's native pipe on top of its own (None / empty: untouched), then unload them."""
+    if not loras:
+        yield
+        return
+    pipe = be.dh.pipe
+    if not hasattr(pipe, "load_lora"):
+        raise ValueError("loras=... needs the native pipe (NativeSDXLPipe)")
+    names = []
+    try:
+        for src, scale in lora_entries(loras):
+            names.append(pipe.load_lora(src, scale))
+        yield
+    finally:
+        for name in reversed(names):
+            pipe.unload_lora(name)
 
 
 def _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts, keep_parts,
@@ -220,10 +265,15 @@ def _precompute_chain(be, list_prompts, list_seeds, list_negative_prompts):
 def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_single_trans: float = 10,
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
-                   decoder: Optional[str] = None, noise: Optional[str] = None) -> List[List]:
+                   decoder: Optional[str] = None, noise: Optional[str] = None, loras: Optional[Sequence] = None) -> List[List]:
     """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder``, ``noise`` as there).
-    Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames."""
+    Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames.
+    The header's ``"loras": [{"path": ..., "scale": ...}]`` (paths relative to the JSON file) are the chain's LoRA adapters; ``loras=``
+    given here replaces them."""
     header, items = load_movie_json(fp_json)
+    if loras is None and header.get("loras"):
+        base = os.path.dirname(os.path.abspath(fp_json))
+        loras = [(os.path.join(base, it["path"]), float(it.get("scale", 1.0))) for it in header["loras"]]
     images = strengths = None
     if any(it.get("image") is not None for it in items):
         from PIL import Image
@@ -236,4 +286,4 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
                                 movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
-                                list_image_strengths=strengths, noise=noise)
+                                list_image_strengths=strengths, noise=noise, loras=loras)
