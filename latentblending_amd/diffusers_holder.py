@@ -117,7 +117,7 @@ class DiffusersHolder:
     @torch.no_grad()
     def image2latent(self, image) -> torch.Tensor:
         """Encode a picture (PIL image, or what the pipe's encoder takes) of the holder's size to scaled latents [1, 4, h, w]:
-        the native pipe's TAESDXL encoder, else ``pipe.vae.encode`` of the picture in [-1, 1] (``latent_dist.mode()`` when the
+        the native pipe's ``native_image2latent`` (its ``encoder``: TAESDXL, or the full SDXL VAE encoder), else ``pipe.vae.encode`` of the picture in [-1, 1] (``latent_dist.mode()`` when the
         VAE returns a distribution, else ``.latents``) times ``vae.config.scaling_factor``."""
         pipe = self.pipe
         if _is_native(pipe):

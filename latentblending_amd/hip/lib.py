@@ -105,6 +105,16 @@ class ConvGeom(_ConvGeomFields):
         return cls(H, W, cin, 3, 3, stride, 1, ups, ldx)
 
     @classmethod
+    def down3x3(cls, H: int, W: int, cin: int, ldx: Optional[int] = None) -> "ConvGeom":
+        """The SDXL VAE encoder's downsampler: 3x3 / stride 2 / pad 0 over the input padded by one zero row at the bottom and one
+        zero column at the right ONLY (``F.pad(x, (0, 1, 0, 1))``).  Output (oy, ox) reads rows 2 oy .. 2 oy + 2, so the last output
+        row and column reach one pixel past the image: the implicit-GEMM gather masks them (``iy < Hin``, ``ix < Win``).  ``Hout`` =
+        H / 2 is what a symmetric ``pad`` cannot express; H and W must be even (an odd side would need no far pad at all)."""
+        if H <= 0 or W <= 0 or H % 2 or W % 2:
+            raise ValueError(f"ConvGeom.down3x3: H and W must be positive and even (got {H} x {W})")
+        return tuple.__new__(cls, (H, W, cin, 3, 3, 2, 0, 0, cin if ldx is None else ldx, None, H // 2, W // 2))
+
+    @classmethod
     def subpixel(cls, H: int, W: int, cin: int, parity, ldx: Optional[int] = None) -> "ConvGeom":
         return cls(H, W, cin, 2, 2, ldx=ldx, parity=parity)
 

@@ -41,7 +41,7 @@ from .noise import CounterNoise
 from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
 from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
-from .vae import NativeVAEDecoder, VAEConfig, VAEProgram
+from .vae import NativeVAEDecoder, NativeVAEEncoder, VAEConfig, VAEEncoderProgram, VAEProgram, sample_moments
 from ..replay import lora_entries
 from .lora import COMPONENTS, TEXT_KEY_PREFIXES, LoRARecord, load_state, read_lora
 from .weights import LoRAProvider, SyntheticProvider
@@ -102,8 +102,52 @@ class _VAEFacade:
         prog.decode((z.float() * self._pipe.active_vae_cfg.scaling_factor).to(F16))
         return (prog.image_f32[..., :3].permute(0, 3, 1, 2).clone(),)
 
+    @torch.no_grad()
+    def encode(self, x, return_dict=True):
+        """x [B, 3, H, W] in [-1, 1], any float dtype (diffusers convention) -> an object with ``latent_dist`` (``.mean``,
+        ``.logvar``, ``.mode()``, ``.sample(generator=None)``, NCHW fp32 in UNSCALED units: multiply by the SDXL VAE's
+        ``scaling_factor``).  Always the full ``AutoencoderKL`` encoder, whatever ``pipe.encoder`` says."""
+        pipe = self._pipe
+        f = pipe.vae_cfg.scale_factor
+        B, _, H, W = x.shape
+        if H % f or W % f:
+            raise ValueError(f"vae.encode: the picture size {W} x {H} is no multiple of {f}")
+        prog = pipe.vae_encoder_program(B, (H // f, W // f))
+        prog.encode_normalized(x.to(pipe.device))
+        out = SimpleNamespace(latent_dist=_LatentDist(prog.moments().clone()))
+        return out if return_dict else (out.latent_dist,)
+
     def to(self, *a, **k):
         return self
+
+
+class _LatentDist:
+    """diffusers' ``DiagonalGaussianDistribution`` over the fp32 moments [B, h, w, 2 C] of one encode (channels last: mean |
+    logvar); what it hands out is NCHW fp32, unscaled.  The sample is computed in torch (``vae.sample_moments``): the clamp, ``exp``
+    and a ``randn`` on the device from the generator."""
+
+    def __init__(self, moments: torch.Tensor):
+        self._moments = moments
+
+    @staticmethod
+    def _nchw(t):
+        return t.permute(0, 3, 1, 2).contiguous()
+
+    @property
+    def mean(self):
+        return self._nchw(self._moments.chunk(2, dim=-1)[0])
+
+    @property
+    def logvar(self):
+        return self._nchw(torch.clamp(self._moments.chunk(2, dim=-1)[1], -30.0, 20.0))
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, generator=None):
+        B, h, w, c2 = self._moments.shape          # (eps is drawn in NCHW order, as diffusers' randn_tensor(mean.shape) draws it)
+        eps = torch.randn((B, c2 // 2, h, w), generator=generator, device=self._moments.device, dtype=self._moments.dtype)
+        return self._nchw(sample_moments(self._moments, eps=eps.permute(0, 2, 3, 1)))
 
 
 class _ImageProcessor:
@@ -127,7 +171,8 @@ class StableDiffusionXLPipeline:
                  text_encoder_fn=None, unet_native: Optional[NativeUNet] = None,
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
                  scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
-                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream", encoders=None, loras=None):
+                 tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream", encoders=None, loras=None,
+                 encoder: str = "tiny", vae_encoder_native: Optional[NativeVAEEncoder] = None):
         """``loras``: [(src, scale), ...] = LoRA adapters loaded right after construction, in order (``load_lora``).
         ``encoders``: a ``clip.NativeTextEncoders``; its ``encode`` becomes ``text_encoder_fn`` (unless one is given) and, when it
         carries the providers its towers were packed from, LoRA adapters reach the text towers too.  Adapters are merged from the
@@ -143,6 +188,13 @@ class StableDiffusionXLPipeline:
         is built on first use from ``tiny_vae_native`` / ``tiny_vae_provider`` (``native.from_safetensors(<dir>/taesdxl)``), else
         from the seeded synthetic stand-in (announced like the others).  The same provider serves the TAESDXL ENCODER
         (``native_image2latent``: pictures -> latents, whatever ``decoder`` says), built on first use as well.
+        ``encoder``: what ``native_image2latent`` (image anchors) encodes pictures with: "tiny" (default) = the TAESDXL encoder, as ever;
+        "full" = the SDXL ``AutoencoderKL`` encoder (``native/vae.py``: ``vae.encode(x).latent_dist.mode() * scaling_factor``, the
+        autoencoder the full decoder belongs to).  Case-insensitive, anything else raises ``ValueError``; ``pipe.encoder`` switches
+        it afterwards.  The full encoder is built on first use from ``vae_encoder_native`` or from ``vae_provider`` (the ``encoder.*``
+        / ``quant_conv.*`` keys of the same ``vae/*.safetensors``); with neither a provider nor a ``vae_native`` it is the seeded
+        synthetic stand-in (announced like the others).  A ready-made ``vae_native`` WITHOUT ``vae_provider`` raises ``ValueError``
+        there: a real decoder is never paired with a synthetic encoder silently.
         ``scheduler``: None or "euler" = the reference pipes' choice (Euler-ancestral for Turbo, Euler for base); "ddim" = diffusers'
         DDIMScheduler (eta 0) behind the same native loops - also with ``turbo=True`` (the Turbo guidance / branching defaults
         stay, only the sampler changes: deterministic, "leading" spacing); "lcm" = the latent-consistency sampler (diffusers'
@@ -159,6 +211,12 @@ class StableDiffusionXLPipeline:
         # Euler-ancestral schedulers, the other names are this pipe's own)
         self.scheduler = make_scheduler(scheduler, turbo, torch.device(device))
         self._decoder = self._check_decoder(decoder)
+        self._encoder = self._check_encoder(encoder)
+        self._vae_provider, self._vae_seed = vae_provider, seed + 1
+        self._vae_native_given = vae_native is not None
+        self.vae_encoder_native = vae_encoder_native
+        if self._encoder == "full":
+            self._full_encoder_source()
         if not torch.cuda.is_available():
             raise RuntimeError("NativeSDXLPipe needs an MI355X (HIP device); there is no CPU fallback")
         self.device = torch.device(device)
@@ -214,6 +272,7 @@ class StableDiffusionXLPipeline:
         # like the tiny decoder's and dropped by the same switch
         self.tiny_vae_encoder_native: Optional[NativeTinyVAEEncoder] = None
         self._tiny_encoder_programs: "OrderedDict[Tuple[int, ...], TinyEncoderProgram]" = OrderedDict()
+        self._vae_encoder_programs: "OrderedDict[Tuple[int, ...], VAEEncoderProgram]" = OrderedDict()  # (encoder="full" / vae.encode)
         self.vae_encodes = 0                # pictures encoded by native_image2latent
         side = self.unet_cfg.sample_size * self.vae_cfg.scale_factor
         self.render_size = (side, side)     # (H, W) of the pictures this pipe is rendering: what prepare_latents was last asked for
@@ -580,7 +639,7 @@ class StableDiffusionXLPipeline:
         flag = bool(flag)
         if flag != self._ragged_halo:
             self._ragged_halo = flag
-            for cache in (self._unet_programs, self._vae_programs):
+            for cache in (self._unet_programs, self._vae_programs, self._vae_encoder_programs):
                 stale = [k for k in cache if len(k) == 3]           # (square programs, keyed (B, L), never carry the flag)
                 if stale:
                     torch.cuda.synchronize(self.device)
@@ -600,6 +659,53 @@ class StableDiffusionXLPipeline:
     @decoder.setter
     def decoder(self, name: str):
         self._decoder = self._check_decoder(name)
+
+    @staticmethod
+    def _check_encoder(name) -> str:
+        if not isinstance(name, str) or name.strip().lower() not in ("full", "tiny"):
+            raise ValueError(f"NativeSDXLPipe: encoder must be 'tiny' or 'full' (got {name!r})")
+        return name.strip().lower()
+
+    @property
+    def encoder(self) -> str:
+        return self._encoder
+
+    @encoder.setter
+    def encoder(self, name: str):
+        name = self._check_encoder(name)
+        if name == "full":
+            self._full_encoder_source()
+        self._encoder = name
+
+    def _full_encoder_source(self):
+        """What the full encoder is (or would be) packed from: None = the ready-made ``vae_encoder_native``, else a provider.  A
+        ready-made decoder without the provider it was packed from has no encoder weights to offer: ``ValueError``."""
+        if self.vae_encoder_native is not None:
+            return None
+        if self._vae_provider is not None:
+            return self._vae_provider
+        if self._vae_native_given:
+            raise ValueError("NativeSDXLPipe: the full VAE encoder needs weights, and the pipe was given a ready-made vae_native= without "
+                             "the provider it was packed from; pass vae_provider= (the encoder.* / quant_conv.* keys of the same "
+                             "checkpoint) or vae_encoder_native= beside it - a synthetic encoder is never paired with a given decoder")
+        return SyntheticProvider(self._vae_seed)
+
+    def _vae_encoder_net(self) -> NativeVAEEncoder:
+        if self.vae_encoder_native is None:
+            source = self._full_encoder_source()
+            if self._vae_provider is None:
+                self._synthetic_notice("VAE encoder weights", "pass vae_provider=native.from_safetensors(<dir>/vae)")
+            self.vae_encoder_native = NativeVAEEncoder(self.vae_cfg, source, self.device)
+        return self.vae_encoder_native
+
+    def vae_encoder_program(self, B: int, L) -> VAEEncoderProgram:
+        """The full SDXL VAE encoder's program for ``B`` pictures of latent size ``L`` (side or ``(H, W)``)."""
+        def build():
+            prog = self._vae_encoder_net().build(B, L, ragged_halo=self._ragged_halo)
+            if self._use_graphs:
+                prog.enable_graphs()
+            return prog
+        return self._cached(self._vae_encoder_programs, program_key(B, L), build)
 
     @property
     def active_vae_cfg(self):
@@ -668,7 +774,8 @@ class StableDiffusionXLPipeline:
     def enable_graphs(self, flag: bool = True):
         self._use_graphs = bool(flag)
         if flag:
-            for cache in (self._unet_programs, self._vae_programs, self._tiny_vae_programs, self._tiny_encoder_programs):
+            for cache in (self._unet_programs, self._vae_programs, self._tiny_vae_programs, self._tiny_encoder_programs,
+                          self._vae_encoder_programs):
                 for p in cache.values():
                     p.enable_graphs()
 
@@ -1021,7 +1128,8 @@ class StableDiffusionXLPipeline:
 
     @torch.no_grad()
     def native_image2latent(self, images) -> torch.Tensor:
-        """Pictures -> the latents the TAESDXL encoder gives them: fp16 [B, 4, H / 8, W / 8] on the device, in scaled units
+        """Pictures -> the latents the pipe's ``encoder`` gives them ("tiny": TAESDXL; "full": the SDXL VAE's ``encode(x).mode() *
+        scaling_factor``): fp16 [B, 4, H / 8, W / 8] on the device, in scaled units
         (UNet latents as they stand, whatever ``decoder`` is active).  ``images``: a PIL image, a list of them, or a uint8
         [B, H, W, 3] tensor or array; H and W must be the pipe's current render size (``render_size``: what ``prepare_latents``
         was last asked for - the holder states its own before it calls) - any other size is a ``ValueError``."""
@@ -1030,10 +1138,11 @@ class StableDiffusionXLPipeline:
         if (H, W) != tuple(self.render_size):
             raise ValueError(f"native_image2latent: the pictures are {W} x {H} (width x height) but the pipe renders "
                              f"{self.render_size[1]} x {self.render_size[0]}; resize them first")
-        f = self.tiny_vae_cfg.scale_factor
+        full = self._encoder == "full"
+        f = (self.vae_cfg if full else self.tiny_vae_cfg).scale_factor
         if H % f or W % f:
             raise ValueError(f"native_image2latent: the render size {W} x {H} is no multiple of {f}")
-        prog = self.tiny_encoder_program(u8.shape[0], (H // f, W // f))
+        prog = (self.vae_encoder_program if full else self.tiny_encoder_program)(u8.shape[0], (H // f, W // f))
         z = prog.encode(u8).clone()
         self.vae_encodes += int(u8.shape[0])
         return z

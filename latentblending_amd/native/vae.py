@@ -17,6 +17,9 @@ Either way the MFMA work runs at the fp16 rate (16x the fp32 MFMA rate on gfx950
 The mid-block attention (1 head, d = 512) is GEMM -> row softmax -> GEMM; its V bias is folded
 into the output projection bias at load time (softmax rows sum to 1).
 Output is quantised on device to uint8 NHWC frames.
+
+The encoder (``AutoencoderKL.encode``: ``NativeVAEEncoder`` / ``VAEEncoderProgram``, at the end of this file) shares the weight
+layouts (``_VAENet``) and the residual stream with its units (``_VAEStreamProgram``) with the decoder.
 """
 from __future__ import annotations
 
@@ -51,7 +54,10 @@ class VAEConfig:
         return 2 ** (len(self.block_channels) - 1)
 
 
-class NativeVAEDecoder:
+class _VAENet:
+    """What the two halves of the SDXL VAE share: the packed weights, loaded from one provider - resnets, the mid-block attention
+    (fused ``qkv`` when the top width is 512, V bias folded into ``to_out``) and the biases in stream units."""
+
     def __init__(self, cfg: VAEConfig, provider, device="cuda"):
         self.cfg, self.device = cfg, torch.device(device)
         self.w: Dict[str, torch.Tensor] = {}
@@ -67,14 +73,8 @@ class NativeVAEDecoder:
             self.w[p + ".conv_shortcut.weight"] = pk.dev(w.reshape(cout, cin), F16)
             self.w[p + ".conv_shortcut.bias"] = pk.dev(pk.pv.bias(p + ".conv_shortcut.bias", cout), F32)
 
-    def _load(self, pv):
-        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
-        rev = list(reversed(cfg.block_channels))
-        top = rev[0]
-        pk.conv("post_quant_conv", cfg.latent_channels, cfg.latent_channels, 1)
-        pk.conv("decoder.conv_in", cfg.latent_channels, top, 3)
-        self._resnet(pk, "decoder.mid_block.resnets.0", top, top)
-        a = "decoder.mid_block.attentions.0"
+    def _attention(self, pk, a, top):
+        pv = pk.pv
         pk.norm(a + ".group_norm", top)
         pk.linear(a + ".to_q", top, top)
         pk.linear(a + ".to_k", top, top)
@@ -89,6 +89,21 @@ class NativeVAEDecoder:
             self.w[a + ".qkv.weight"] = torch.cat([self.w[a + ".to_q.weight"], self.w[a + ".to_k.weight"], self.w[a + ".to_v.weight"]], 0).contiguous()
             self.w[a + ".qkv.bias"] = torch.cat([self.w[a + ".to_q.bias"], self.w[a + ".to_k.bias"],
                                                  torch.zeros_like(self.w[a + ".to_q.bias"])], 0).contiguous()
+
+    def _stream_biases(self):
+        for key in [k for k in self.w if k.endswith(".bias")]:          # biases in stream units (x 2^-4, exact)
+            self.w[key + "_s"] = self.w[key] * STREAM_SCALE
+
+
+class NativeVAEDecoder(_VAENet):
+    def _load(self, pv):
+        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
+        rev = list(reversed(cfg.block_channels))
+        top = rev[0]
+        pk.conv("post_quant_conv", cfg.latent_channels, cfg.latent_channels, 1)
+        pk.conv("decoder.conv_in", cfg.latent_channels, top, 3)
+        self._resnet(pk, "decoder.mid_block.resnets.0", top, top)
+        self._attention(pk, "decoder.mid_block.attentions.0", top)
         self._resnet(pk, "decoder.mid_block.resnets.1", top, top)
         prev = top
         for ui, c in enumerate(rev):
@@ -99,8 +114,7 @@ class NativeVAEDecoder:
                 pk.upconv(f"decoder.up_blocks.{ui}.upsamplers.0.conv", c)
         pk.norm("decoder.conv_norm_out", rev[-1])
         pk.conv("decoder.conv_out", rev[-1], cfg.out_channels, 3, gain=0.5)
-        for key in [k for k in self.w if k.endswith(".bias")]:          # biases in stream units (x 2^-4, exact)
-            self.w[key + "_s"] = self.w[key] * STREAM_SCALE
+        self._stream_biases()
 
     def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "VAEProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
@@ -108,32 +122,20 @@ class NativeVAEDecoder:
         return VAEProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
 
 
-class VAEProgram(RecordedProgram):
-    """One recorded decode for a fixed (batch, latent size); ``L`` / ``ragged_halo``: ``RecordedProgram``.
-    ``marks``: one ``Mark`` per emission unit (``conv_in`` = post_quant_conv + conv_in, every resnet and upsampler by its weight
-    prefix, ``mid_attention``, ``image_f32``); ``tap_names`` maps the oracle's block taps (``mid``, ``up0`` ..) to units;
-    ``capture()`` fills ``taps``."""
+class _VAEStreamProgram(RecordedProgram):
+    """What the programs of the two halves share: the residual stream in its two formats (module docstring) and the units built on it -
+    stream convs with their GroupNorm operands and producer statistics, resnets, the mid-block attention."""
 
-    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
+    def __init__(self, net: _VAENet, B: int, L, ragged_halo: bool = True, journal: bool = False):
         super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
-        cfg, H, W = net.cfg, self.H, self.W
+        cfg = net.cfg
         self.scaled = bool(cfg.stream_fp16_scaled)
         self.fuse_gn_stats = bool(getattr(cfg, "fuse_gn_stats", True))
         self.fused_mid_attention = bool(getattr(cfg, "fused_mid_attention", True))
-        dev = net.device
-        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
-        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
-        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
-        self.image_f32 = torch.zeros(B, SH, SW, pad_to(cfg.out_channels, 4), dtype=F32, device=dev)
-        self._pq = torch.zeros(B, H, W, pad_to(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
-        self.prog = Program("vae-decode")
-        with self._recording(self.prog):
-            self._emit()
 
-    def capture(self) -> Dict[str, torch.Tensor]:
-        """``RecordedProgram.capture`` on the latent ``z_in`` holds now (taps are NHWC).  Stream tensors come back in real units as
-        fp32: the 2^-4 of the scaled fp16 stream is undone (exactly).  Leaves ``frames`` / ``image_f32`` as a ``decode`` would."""
-        return super().capture(lambda m, t: t.float() / STREAM_SCALE if (self.scaled and m.kind != "out") else t)
+    def _stream_units(self, m, t):
+        """``capture``'s conversion: stream tensors in real units as fp32 (the 2^-4 of the scaled fp16 stream undone, exactly)."""
+        return t.float() / STREAM_SCALE if (self.scaled and m.kind != "out") else t
 
     # ---- residual-stream format --------------------------------------------------------------
     # scaled (default): stream tensors hold value * 2^-4 in fp16;  f32: plain fp32 (see module docstring)
@@ -230,9 +232,9 @@ class VAEProgram(RecordedProgram):
             ar.release(xs)
         return out
 
-    def _mid_attention(self, h, B, H, W, c):
+    def _mid_attention(self, h, a, B, H, W, c):
+        """The mid-block attention whose weights sit under the prefix ``a``, added onto the stream ``h`` in place."""
         em, w, ar, sc = self.em, self.net.w, self.arena, self.scaled
-        a = "decoder.mid_block.attentions.0"
         S = H * W
         n = ar.alloc((B * S, c))
         self._gn(h, n, a + ".group_norm", B, S, c, False)
@@ -244,7 +246,7 @@ class VAEProgram(RecordedProgram):
             em.attention(qkv.data_ptr(), qkv.data_ptr() + 2 * c, qkv.data_ptr() + 4 * c, o, B=B, H=1, Sq=S, Skv=S, valid=S,
                          ldq=3 * c, ldk=3 * c, ldv=3 * c, ldo=c, head_dim=512)
             ar.release(qkv)
-            return self._attn_out(o, h, B, S)
+            return self._attn_out(o, h, a, B, S)
         q, k = ar.alloc((B * S, c)), ar.alloc((B * S, c))
         em.gemm(n, w[a + ".to_q.weight"], q, M=B * S, bias=w[a + ".to_q.bias"])
         em.gemm(n, w[a + ".to_k.weight"], k, M=B * S, bias=w[a + ".to_k.bias"])
@@ -259,15 +261,39 @@ class VAEProgram(RecordedProgram):
             api.lb_softmax_rows_f16(scores.data_ptr(), S, S, S, 1.0, _stream())
             em.gemm(scores, vt[:, b * S:(b + 1) * S], ob, M=S, lda=S)    # W = V^T slice [c, S], ldw = B*S
         ar.release(scores); ar.release(q); ar.release(k); ar.release(vt)
-        return self._attn_out(o, h, B, S)
+        return self._attn_out(o, h, a, B, S)
 
-    def _attn_out(self, o, h, B, S):
+    def _attn_out(self, o, h, a, B, S):
         em, w, ar, sc = self.em, self.net.w, self.arena, self.scaled
-        a = "decoder.mid_block.attentions.0"
         em.gemm(o, w[a + ".to_out.0.weight"], h, M=B * S, bias=w[a + (".to_out.0.bias_s" if sc else ".to_out.0.bias")],
                 residual=h, flags=0 if sc else (lib.GEMM_OUT_F32 | lib.GEMM_RES_F32), alpha=STREAM_SCALE if sc else 1.0)
         ar.release(o)
         return h
+
+
+class VAEProgram(_VAEStreamProgram):
+    """One recorded decode for a fixed (batch, latent size); ``L`` / ``ragged_halo``: ``RecordedProgram``.
+    ``marks``: one ``Mark`` per emission unit (``conv_in`` = post_quant_conv + conv_in, every resnet and upsampler by its weight
+    prefix, ``mid_attention``, ``image_f32``); ``tap_names`` maps the oracle's block taps (``mid``, ``up0`` ..) to units;
+    ``capture()`` fills ``taps``."""
+
+    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+        cfg, H, W = net.cfg, self.H, self.W
+        dev = net.device
+        SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.frames = torch.zeros(B, SH, SW, 3, dtype=torch.uint8, device=dev)
+        self.image_f32 = torch.zeros(B, SH, SW, pad_to(cfg.out_channels, 4), dtype=F32, device=dev)
+        self._pq = torch.zeros(B, H, W, pad_to(cfg.latent_channels, 8), dtype=F16, device=dev)  # pad channels stay 0
+        self.prog = Program("vae-decode")
+        with self._recording(self.prog):
+            self._emit()
+
+    def capture(self) -> Dict[str, torch.Tensor]:
+        """``RecordedProgram.capture`` on the latent ``z_in`` holds now (taps are NHWC).  Stream tensors come back in real units as
+        fp32: the 2^-4 of the scaled fp16 stream is undone (exactly).  Leaves ``frames`` / ``image_f32`` as a ``decode`` would."""
+        return super().capture(self._stream_units)
 
     def _emit(self):
         net, cfg, em, w, ar, B, LH, LW = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B, self.H, self.W
@@ -285,7 +311,7 @@ class VAEProgram(RecordedProgram):
         at = self._mark("conv_in", "conv_in", h, "z_in")        # ``at``: the unit whose output h is
         nxt = self._resnet(h, "decoder.mid_block.resnets.0", B, LH, LW, top, top); ar.release(h); h = nxt
         at = self._mark("decoder.mid_block.resnets.0", "resnet", h, at)
-        h = self._mid_attention(h, B, LH, LW, top)
+        h = self._mid_attention(h, "decoder.mid_block.attentions.0", B, LH, LW, top)
         at = self._mark("mid_attention", "mid_attention", h, at)
         nxt = self._resnet(h, "decoder.mid_block.resnets.1", B, LH, LW, top, top); ar.release(h); h = nxt
         at = self.tap_names["mid"] = self._mark("decoder.mid_block.resnets.1", "resnet", h, at)
@@ -328,3 +354,200 @@ class VAEProgram(RecordedProgram):
         self.z_in.copy_(z)
         self.prog.launch()
         return self.frames
+
+
+# ====================================================================== encoder
+# The other half of the same checkpoint (``encoder.*``, ``quant_conv.*``): diffusers' ``AutoencoderKL.encode``, restated (no diffusers
+# here; the tests pin the restatement against the latent-diffusion encoder that ``transformers`` ships as ``JanusVQVAEEncoder``):
+#
+#     x in [-1, 1]                                             (a uint8 picture: u8 / 127.5 - 1)
+#     encoder.conv_in                     conv 3 -> ch[0], 3x3, pad 1
+#     encoder.down_blocks.{i}.resnets.{0,1}                    widths ch = (128, 256, 512, 512); a 1x1 conv_shortcut where cin != cout
+#     encoder.down_blocks.{0,1,2}.downsamplers.0.conv          3x3, stride 2, pad 0 on F.pad(x, (0, 1, 0, 1)): ONE zero row at the
+#                                                              bottom and ONE zero column at the right (``ConvGeom.down3x3``)
+#     encoder.mid_block.resnets.0, .attentions.0, .resnets.1   one head over all channels, as in the decoder
+#     encoder.conv_norm_out -> SiLU -> encoder.conv_out        ch[-1] -> 8 (mean | logvar)
+#     quant_conv                          8 -> 8, 1x1
+#     moments -> mean, logvar = chunk(2); mode() = mean; sample = mean + exp(0.5 clamp(logvar, -30, 20)) randn
+#     UNet latents = that * scaling_factor
+#
+# GroupNorm: 32 groups, eps 1e-6.  ``quant_conv`` is folded into ``encoder.conv_out`` at pack time, in float64 (W' = Wq Wout,
+# b' = Wq bout + bq, rounded once): one narrow-N launch with N = 8 that writes the fp32 moments, no fp16 rounding between the two
+# linear maps.  No new kernel: the stride-1 convs, GroupNorms and the attention are the decoder's launches; the three downsamplers
+# run on the implicit GEMM, whose gather masks the far edge (every other conv route refuses stride 2 / pad 0).  The residual stream
+# is the decoder's, in both formats: diffusers upcasts the whole VAE for ``encode`` as well.
+def encoder_state_dict_keys(cfg: VAEConfig = None):
+    """The ``encoder.*`` / ``quant_conv.*`` keys of the SDXL VAE's ``diffusion_pytorch_model.safetensors`` the encoder reads, in
+    layer order (the order ``NativeVAEEncoder`` asks its provider for them)."""
+    cfg = cfg or VAEConfig()
+    ch = cfg.block_channels
+    keys = []
+
+    def both(p):
+        keys.extend([p + ".weight", p + ".bias"])
+
+    def resnet(p, cin, cout):
+        for part in ("norm1", "conv1", "norm2", "conv2") + (("conv_shortcut",) if cin != cout else ()):
+            both(f"{p}.{part}")
+
+    both("encoder.conv_in")
+    prev = ch[0]
+    for bi, c in enumerate(ch):
+        for li in range(cfg.layers_per_block):
+            resnet(f"encoder.down_blocks.{bi}.resnets.{li}", prev, c)
+            prev = c
+        if bi < len(ch) - 1:
+            both(f"encoder.down_blocks.{bi}.downsamplers.0.conv")
+    resnet("encoder.mid_block.resnets.0", prev, prev)
+    for part in ("group_norm", "to_q", "to_k", "to_v", "to_out.0"):
+        both(f"encoder.mid_block.attentions.0.{part}")
+    resnet("encoder.mid_block.resnets.1", prev, prev)
+    both("encoder.conv_norm_out")
+    both("encoder.conv_out")
+    both("quant_conv")
+    return keys
+
+
+class NativeVAEEncoder(_VAENet):
+    def _load(self, pv):
+        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
+        ch = cfg.block_channels
+        top, mc = ch[-1], 2 * cfg.latent_channels
+        pk.conv("encoder.conv_in", cfg.out_channels, ch[0], 3)          # (Cin 3 padded to 8)
+        prev = ch[0]
+        for bi, c in enumerate(ch):
+            for li in range(cfg.layers_per_block):
+                self._resnet(pk, f"encoder.down_blocks.{bi}.resnets.{li}", prev, c)
+                prev = c
+            if bi < len(ch) - 1:
+                pk.conv(f"encoder.down_blocks.{bi}.downsamplers.0.conv", c, c, 3)      # (the packing does not depend on the stride)
+        self._resnet(pk, "encoder.mid_block.resnets.0", top, top)
+        self._attention(pk, "encoder.mid_block.attentions.0", top)
+        self._resnet(pk, "encoder.mid_block.resnets.1", top, top)
+        pk.norm("encoder.conv_norm_out", top)
+        # quant_conv (1x1) folded into conv_out, in float64, rounded once: ``encoder.moments`` = the conv that writes the moments
+        wo = pv.weight("encoder.conv_out.weight", (mc, top, 3, 3), top * 9, 0.5).double()
+        bo = pv.bias("encoder.conv_out.bias", mc).double()
+        wq = pv.weight("quant_conv.weight", (mc, mc, 1, 1), mc).double().reshape(mc, mc)
+        bq = pv.bias("quant_conv.bias", mc).double()
+        mc_p = pad_to(mc, 4)
+        packed = torch.zeros(mc_p, 3, 3, top, dtype=torch.float64)
+        packed[:mc] = torch.einsum("om,mcyx->oyxc", wq, wo)
+        bias = torch.zeros(mc_p, dtype=torch.float64)
+        bias[:mc] = wq @ bo + bq
+        self.w["encoder.moments.weight"] = pk.dev(packed.reshape(mc_p, 9 * top), F16)
+        self.w["encoder.moments.bias"] = pk.dev(bias, F32)
+        self._stream_biases()
+
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "VAEEncoderProgram":
+        """``L``: LATENT side, or a pair ``(H, W)`` in latent pixels (the picture is ``cfg.scale_factor`` times that)."""
+        return VAEEncoderProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
+
+
+def sample_moments(moments: torch.Tensor, generator=None, eps: torch.Tensor = None) -> torch.Tensor:
+    """diffusers' ``DiagonalGaussianDistribution.sample`` on ``moments`` [..., 2 C] (channels last: mean | logvar):
+    ``mean + exp(0.5 clamp(logvar, -30, 20)) eps`` in the moments' own arithmetic; ``eps``: given, or ``randn`` on the moments'
+    device from ``generator``."""
+    mean, logvar = moments.chunk(2, dim=-1)
+    std = torch.exp(0.5 * torch.clamp(logvar, -30.0, 20.0))
+    if eps is None:
+        eps = torch.randn(mean.shape, generator=generator, device=moments.device, dtype=moments.dtype)
+    return mean + std * eps
+
+
+class VAEEncoderProgram(_VAEStreamProgram):
+    """One recorded encode for a fixed (batch, latent size): pictures [B, 8H, 8W, 3] -> fp32 ``moments_f32`` [B, H, W, 8] (mean | logvar,
+    unscaled) and fp16 ``latents`` [B, 4, H, W] = mean * scaling_factor.  ``marks``: ``conv_in``, every resnet and downsampler by
+    its weight prefix, ``mid_attention``, ``moments``; ``tap_names``: ``down0`` .. and ``mid``; ``capture()`` fills ``taps``."""
+
+    def __init__(self, net: NativeVAEEncoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+        cfg, H, W, dev = net.cfg, self.H, self.W, net.device
+        self.SH, self.SW = H * cfg.scale_factor, W * cfg.scale_factor
+        self.pc, self.pc_p = cfg.out_channels, pad_to(cfg.out_channels, 8)
+        self.x_in = torch.zeros(B, self.SH, self.SW, self.pc_p, dtype=F16, device=dev)      # NHWC; the pad channels stay zero
+        self.moments_f32 = torch.zeros(B, H, W, pad_to(2 * cfg.latent_channels, 4), dtype=F32, device=dev)
+        self.latents = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)
+        self.prog = Program("vae-encode")
+        with self._recording(self.prog):
+            self._emit()
+
+    def capture(self) -> Dict[str, torch.Tensor]:
+        """``RecordedProgram.capture`` on the picture ``x_in`` holds now (taps are NHWC, stream tensors in real units as fp32).
+        Leaves ``moments_f32`` / ``latents`` as an ``encode`` would."""
+        return super().capture(self._stream_units)
+
+    def _emit(self):
+        cfg, em, w, ar, B, sc = self.net.cfg, self.em, self.net.w, self.arena, self.B, self.scaled
+        ch = cfg.block_channels
+        top, lc = ch[-1], cfg.latent_channels
+        sh, sw = self.SH, self.SW
+        h = self._stream_conv(self.x_in, "encoder.conv_in", B, sh, sw, self.pc, ch[0])
+        at = self._mark("conv_in", "conv_in", h, "x_in")
+        prev = ch[0]
+        for bi, c in enumerate(ch):
+            for li in range(cfg.layers_per_block):
+                p = f"encoder.down_blocks.{bi}.resnets.{li}"
+                nxt = self._resnet(h, p, B, sh, sw, prev, c)
+                ar.release(h); h = nxt
+                at = self._mark(p, "resnet", h, at)
+                prev = c
+            if bi < len(ch) - 1:
+                name = f"encoder.down_blocks.{bi}.downsamplers.0.conv"
+                g = lib.ConvGeom.down3x3(sh, sw, c)
+                h16, owned = self._stream_as_operand(h, B, sh, sw, c)
+                dn = ar.alloc((B, g.Hout, g.Wout, c), F16 if sc else F32)
+                # operand carries the 2^-4 scale (as the decoder's upsampler): scaled mode keeps it, fp32 mode multiplies back.  The
+                # implicit GEMM leaves no statistics: the GroupNorm behind it runs its two-pass form
+                em.gemm(h16, w[name + ".weight"], dn, M=g.M(B), bias=w[name + (".bias_s" if sc else ".bias")],
+                        flags=0 if sc else lib.GEMM_OUT_F32, alpha=1.0 if sc else 1.0 / STREAM_SCALE, conv=g)
+                if owned:
+                    ar.release(h16)
+                ar.release(h)
+                h, sh, sw = dn, g.Hout, g.Wout
+                at = self._mark(name, "downsample", h, at)
+            self.tap_names[f"down{bi}"] = at
+        assert (sh, sw) == (self.H, self.W)
+        nxt = self._resnet(h, "encoder.mid_block.resnets.0", B, sh, sw, top, top); ar.release(h); h = nxt
+        at = self._mark("encoder.mid_block.resnets.0", "resnet", h, at)
+        h = self._mid_attention(h, "encoder.mid_block.attentions.0", B, sh, sw, top)
+        at = self._mark("mid_attention", "mid_attention", h, at)
+        nxt = self._resnet(h, "encoder.mid_block.resnets.1", B, sh, sw, top, top); ar.release(h); h = nxt
+        at = self.tap_names["mid"] = self._mark("encoder.mid_block.resnets.1", "resnet", h, at)
+        conv_out = lib.ConvGeom.conv3x3(sh, sw, top)
+        g = em.gn_operand(h, w["encoder.moments.weight"], M=B * sh * sw, conv=conv_out, flags=lib.GEMM_OUT_F32,
+                          **self._gn_args(h, "encoder.conv_norm_out", B, sh * sw, top, True))
+        self._gn_done(h)
+        em.gemm(h, w["encoder.moments.weight"], self.moments_f32, M=B * sh * sw, bias=w["encoder.moments.bias"],
+                flags=lib.GEMM_OUT_F32, conv=conv_out, gn=g)
+        ar.release(h)
+        self._mark("moments", "out", self.moments_f32, at)
+        mc_p = self.moments_f32.shape[-1]
+        m16 = ar.alloc((B, sh, sw, mc_p))
+        api.lb_cast_f32_to_f16(self.moments_f32.data_ptr(), m16.data_ptr(), self.moments_f32.numel(), float(cfg.scaling_factor), _stream())
+        api.lb_nhwc_to_nchw_f16(m16.data_ptr(), self.latents.data_ptr(), B, lc, sh * sw, mc_p, _stream())     # (the mean half)
+        ar.release(m16)
+
+    def encode_normalized(self, x: torch.Tensor) -> torch.Tensor:
+        """x [B, 3, 8H, 8W] in [-1, 1] (any float dtype) -> ``latents``; the picture is rounded to the fp16 operand here."""
+        if tuple(x.shape) != (self.B, self.pc, self.SH, self.SW) or not x.is_floating_point():
+            raise ValueError(f"VAEEncoderProgram.encode_normalized: expected a float tensor {(self.B, self.pc, self.SH, self.SW)}, "
+                             f"got {x.dtype} {tuple(x.shape)}")
+        self.x_in[..., :self.pc].copy_(x.permute(0, 2, 3, 1))
+        self.prog.launch()
+        return self.latents
+
+    def encode(self, u8: torch.Tensor) -> torch.Tensor:
+        """uint8 pictures [B, 8H, 8W, 3] on the device -> fp16 latents [B, 4, H, W] in scaled units (the program's own buffer:
+        clone what must outlive the next call).  ``f16(fp32(u8) / 127.5 - 1)`` is staged here, in torch, as the tiny encoder stages
+        ``u8 / 255``."""
+        if tuple(u8.shape) != (self.B, self.SH, self.SW, self.pc) or u8.dtype != torch.uint8:
+            raise ValueError(f"VAEEncoderProgram.encode: expected uint8 {(self.B, self.SH, self.SW, self.pc)}, "
+                             f"got {u8.dtype} {tuple(u8.shape)}")
+        self.x_in[..., :self.pc].copy_(u8.to(F32) / 127.5 - 1.0)
+        self.prog.launch()
+        return self.latents
+
+    def moments(self) -> torch.Tensor:
+        """The fp32 moments [B, H, W, 8] (mean | logvar, unscaled) of the last encode: the program's own buffer."""
+        return self.moments_f32[..., :2 * self.net.cfg.latent_channels]

@@ -9,10 +9,13 @@ is that loop behind two calls, with the same observable order of engine calls (s
 trajectories and the part files are what the scripts produce), plus reader / writer of the JSON file
 the gradio UI saves (``gradio_ui.py:168-190``):
 
-    [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S, "loras": [{"path": ..., "scale": ...}]},
+    [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S, "loras": [{"path": ..., "scale": ...}],
+       "image_encoder": "full"},
       {"iteration": i, "seed": s, "prompt": "...", "negative_prompt": "...", "preview_image": ...}, ... ]
 
 ``"loras"`` is optional: the LoRA adapters the whole movie is rendered under (paths relative to the JSON file).
+``"image_encoder"`` is optional too: the native pipe's ``encoder`` ("tiny" / "full") the movie's image key frames are encoded with;
+a file without it leaves the pipe as it stands, and ``save_movie_json`` writes the key only when it is not the default ("tiny").
 An item may also carry ``"image"`` (a picture file, path relative to the JSON file) and ``"image_strength"`` (default 0.5): that
 key frame is an image anchor (``BlendingEngine.set_anchor_image1`` / ``2``) instead of a picture invented from its prompt.
 
@@ -61,13 +64,25 @@ def _loras_header(loras) -> List[Dict]:
     return [{"path": os.fspath(src), "scale": scale} for src, scale in lora_entries(loras)]
 
 
-def save_movie_json(fp_json: str, be, items: Sequence[Dict], loras: Optional[Sequence] = None) -> None:
+DEFAULT_IMAGE_ENCODER = "tiny"
+
+
+def save_movie_json(fp_json: str, be, items: Sequence[Dict], loras: Optional[Sequence] = None,
+                    image_encoder: Optional[str] = None) -> None:
     """Write the file the UI writes (gradio_ui.py:168-173): header from the engine's holder, then the items.  ``loras``
-    (``[(path, scale), ...]``) goes into the header as ``"loras": [{"path": ..., "scale": ...}]`` - what ``run_movie_json`` loads."""
+    (``[(path, scale), ...]``) goes into the header as ``"loras": [{"path": ..., "scale": ...}]`` - what ``run_movie_json`` loads.
+    ``image_encoder``: "tiny" / "full" (None: the native pipe's ``encoder`` as it stands, "tiny" for any other pipe); written as
+    ``"image_encoder"`` only when it is not the default, so a movie of the default encoder is the file it always was."""
     header = {"settings": "sdxl", "width": be.dh.width_img, "height": be.dh.height_img,
               "num_inference_steps": be.dh.num_inference_steps}
     if loras:
         header["loras"] = _loras_header(loras)
+    if image_encoder is None:
+        image_encoder = getattr(be.dh.pipe, "encoder", DEFAULT_IMAGE_ENCODER)
+    if not isinstance(image_encoder, str) or image_encoder.strip().lower() not in ("tiny", "full"):
+        raise ValueError(f"save_movie_json: image_encoder must be 'tiny' or 'full' (got {image_encoder!r})")
+    if image_encoder.strip().lower() != DEFAULT_IMAGE_ENCODER:
+        header["image_encoder"] = image_encoder.strip().lower()
     with open(fp_json, "w") as fh:
         json.dump([header] + [dict(it) for it in items], fh, indent=4)
 
@@ -79,7 +94,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          pipeline_keyframes: bool = False, movie_encoder: Optional[str] = None,
                          movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
                          list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None,
-                         noise: Optional[str] = None, loras: Optional[Sequence] = None) -> List[List]:
+                         noise: Optional[str] = None, loras: Optional[Sequence] = None,
+                         image_encoder: Optional[str] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -109,12 +125,14 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     loads for this chain (``pipe.load_lora``), once, before the first key frame, on top of what it has loaded; they are unloaded
     again afterwards.  None: the pipe's adapters as they stand.  One set per chain: a recycled key frame rendered under other
     scales would be a picture of another model.
+    ``image_encoder``: "tiny" / "full" = the native pipe's ``encoder`` for this chain - what the image key frames are encoded with
+    (None: as the pipe stands); the previous value is restored afterwards.
     """
     images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
     if images is not None and pipeline_keyframes:
         raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
                          "it cannot be combined with image key frames (list_images)")
-    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras):
+    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras), _encoder_as(be, image_encoder):
         try:
             return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
                                          keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
@@ -150,6 +168,23 @@ def _decoder_as(be, decoder: Optional[str]):
         yield
     finally:
         pipe.decoder = previous
+
+
+@contextlib.contextmanager
+def _encoder_as(be, encoder: Optional[str]):
+    """Run the body with the engine's native pipe on ``encoder`` (None: untouched), then put the previous value back."""
+    if encoder is None:
+        yield
+        return
+    pipe = be.dh.pipe
+    if not hasattr(type(pipe), "encoder"):
+        raise ValueError("image_encoder=... needs the native pipe (NativeSDXLPipe)")
+    previous = pipe.encoder
+    pipe.encoder = encoder
+    try:
+        yield
+    finally:
+        pipe.encoder = previous
 
 
 @contextlib.contextmanager
@@ -265,12 +300,16 @@ def _precompute_chain(be, list_prompts, list_seeds, list_negative_prompts):
 def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_single_trans: float = 10,
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
-                   decoder: Optional[str] = None, noise: Optional[str] = None, loras: Optional[Sequence] = None) -> List[List]:
+                   decoder: Optional[str] = None, noise: Optional[str] = None, loras: Optional[Sequence] = None,
+                   image_encoder: Optional[str] = None) -> List[List]:
     """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder``, ``noise`` as there).
     Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames.
     The header's ``"loras": [{"path": ..., "scale": ...}]`` (paths relative to the JSON file) are the chain's LoRA adapters; ``loras=``
-    given here replaces them."""
+    given here replaces them.  The header's ``"image_encoder"`` selects the encoder of the image key frames for this movie (the pipe
+    is restored afterwards); ``image_encoder=`` given here replaces it; neither: the pipe as it stands."""
     header, items = load_movie_json(fp_json)
+    if image_encoder is None:
+        image_encoder = header.get("image_encoder")
     if loras is None and header.get("loras"):
         base = os.path.dirname(os.path.abspath(fp_json))
         loras = [(os.path.join(base, it["path"]), float(it.get("scale", 1.0))) for it in header["loras"]]
@@ -286,4 +325,4 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
                                 movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
-                                list_image_strengths=strengths, noise=noise, loras=loras)
+                                list_image_strengths=strengths, noise=noise, loras=loras, image_encoder=image_encoder)
