@@ -62,35 +62,40 @@ int lb_lerp_f32(const void* p0, const void* p1, void* out, long n, double fract,
 /* params_dev: float[batch][8] = {sigma_from, sigma_next, sigma_up, guidance, dt, -, -, -} */
 int lb_scale_model_input_f16(const void* x, void* out, const float* params_dev, long per_sample,
                              int batch, int dup_for_cfg, void* stream);
-/* `ancestral` is a MODE: 0 = Euler, 1 = Euler-ancestral (`noise` required), 2 = latent-consistency (LCM) step; anything else is
- * refused.  Mode 2 (diffusers 0.25.0 LCMScheduler.step, epsilon prediction; fp16 tensor arithmetic rounded op by op, like DDIM):
+/* `ancestral`: 0 = Euler, 1 = Euler-ancestral (`noise` required); `cfg`: 0 or 1.  Anything else is refused before any launch
+ * (ancestral == 2, once the latent-consistency step, with a message that names lb_lcm_step_f16). */
+int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
+                      const float* params_dev, long per_sample, int batch, int cfg, int ancestral,
+                      void* stream);
+/* Latent-consistency (LCM) step (diffusers 0.25.0 LCMScheduler.step, epsilon prediction; fp16 tensor arithmetic rounded op by op,
+ * like DDIM):
  *   params_dev: float[batch][8] = {0, c_skip, sqrt(abar_prev), guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev),
  *                                  1 / sqrt(abar_t), c_out}
  *   x0 = (x - sqrt(1 - abar_t) eps) / sqrt(abar_t);  den = c_out x0 + c_skip x;  out = sqrt(abar_prev) den + sqrt(1 - abar_prev) noise.
  *   A row with slot 5 == 0 is the LAST step of its schedule: out = den bit for bit and `noise` is not read for it.
- *   `cfg`: bit 0 = CFG as in the other modes; bit 1 = the host's statement that EVERY row is such a last step - only then
- *   may `noise` be null (a null `noise` without bit 1 is refused; the rows are never read back from the device). */
-int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
-                      const float* params_dev, long per_sample, int batch, int cfg, int ancestral,
-                      void* stream);
+ *   `cfg`: 0 or 1, as for the Euler step.  `all_last` != 0 is the host's statement that EVERY row is such a last step - only then
+ *   may `noise` be null (a null `noise` without it is refused; the rows are never read back from the device). */
+int lb_lcm_step_f16(const void* x, const void* eps, const void* noise, void* out, const float* params_dev,
+                    long per_sample, int batch, int cfg, int all_last, void* stream);
 /* diffusers DDIMScheduler.step, eta = 0, epsilon prediction (diffusers_holder.py:356 with a DDIM scheduler on the pipe; the
  * reference's SDXL pipes carry Euler schedulers, :42).  params_dev: float[batch][8] = {0, sqrt(abar_t), sqrt(abar_prev),
  * guidance, sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t), -} - slot 0 = 0 makes lb_scale_model_input_f16 the identity, as
  * DDIM's scale_model_input is; slot 6 is the fp32 reciprocal the kernel MULTIPLIES by where diffusers divides a device tensor by a
  * 0-dim host tensor (the tensor library's true-division kernel multiplies by 1 / b for a host scalar b).  fp16 tensor arithmetic
- * rounded op by op like diffusers' (no fp32 upcast in DDIM).  eps as above.
- *   `cfg` is a bit field: bit 0 = CFG; bit 1 = the DPM-Solver++ 2M step (Lu et al. 2022, algorithm 2; DDIM is that solver at
- *   order 1); any other bit is refused ("cfg bits").  Before bit 1 existed every non-zero value meant CFG - that reading of 2
- *   and 3 is gone; nothing ever passed them.  With bit 1 clear the launch is the DDIM step above, unchanged.
- *   With bit 1 set `x` and `out` are two-plane buffers [2][batch][per_sample] (fp16): plane 0 of `x` the latent, plane 1 the
- *   previous step's x0 prediction m1; plane 0 of `out` the next latent, plane 1 this step's x0 prediction m0.  The kernel keeps
- *   no state: feed `out` of step i as `x` of step i + 1.  `x` and `out` must NOT overlap (not checked).  params_dev rows are
- *   {0, sigma_s, ratio, guidance, c0, c1, 1 / alpha_s, 1 / r0}; every tensor operation rounds to fp16 (CFG combine first) -
- *     m0 = (x - sigma_s eps) (1 / alpha_s);  y = ratio x - c0 m0;  if c1 != 0: y = y - c1 ((1 / r0) (m0 - m1))
- *   A row with c1 == 0 is a first-order row: plane 1 of `x` is not read for it (it may hold anything).  A schedule's last row
- *   (ratio 0, c0 -1, c1 0) returns m0 bit for bit in both planes. */
+ * rounded op by op like diffusers' (no fp32 upcast in DDIM).  eps as above.  `cfg`: 0 or 1; anything else is refused ("cfg
+ * bits"; 2 and 3, once the DPM-Solver++ 2M step, with a message that names lb_dpmpp2m_step_f16). */
 int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
                      int cfg, void* stream);
+/* DPM-Solver++ 2M step (Lu et al. 2022, algorithm 2; DDIM is that solver at order 1).  TWO-PLANE CONTRACT: `state` and `out` are
+ * buffers [2][batch][per_sample] (fp16), twice the size of the other steps' `x` / `out`: plane 0 of `state` the latent, plane 1
+ * the previous step's x0 prediction m1; plane 0 of `out` the next latent, plane 1 this step's x0 prediction m0.  The kernel keeps
+ * no state: feed `out` of step i as `state` of step i + 1.  `state` and `out` must NOT overlap (not checked).  params_dev rows are
+ * {0, sigma_s, ratio, guidance, c0, c1, 1 / alpha_s, 1 / r0}; every tensor operation rounds to fp16 (CFG combine first) -
+ *     m0 = (x - sigma_s eps) (1 / alpha_s);  y = ratio x - c0 m0;  if c1 != 0: y = y - c1 ((1 / r0) (m0 - m1))
+ *   A row with c1 == 0 is a first-order row: plane 1 of `state` is not read for it (it may hold anything).  A schedule's last row
+ *   (ratio 0, c0 -1, c1 0) returns m0 bit for bit in both planes.  `cfg`: 0 or 1 (eps holds 2 * batch samples). */
+int lb_dpmpp2m_step_f16(const void* state, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
+                        int cfg, void* stream);
 /* Counter-based sampler noise (the `noise` operand of the ancestral / LCM steps above when a pipe runs with noise="counter"):
  * Philox4x32-10 words turned into fp16 normals in float64, each value a pure function of its row's key and counter words and of
  * its element index - so a seed gives the same noise whatever batch, order or rank serves the draw.  The step kernels are

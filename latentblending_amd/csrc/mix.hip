@@ -424,34 +424,57 @@ extern "C" int lb_lerp_f32(const void* p0, const void* p1, void* out, long n, do
 // ------------------------------------------------------------------------------------------
 #define LB_STEP_STRIDE 8
 
-// Both kernels: 16 B per lane (8 halves), blockIdx.y walks the samples so the per-sample scalars are loaded once per
-// block (no per-element division / parameter fetch); a scalar tail covers per_sample % 8 and unaligned buffers.
-
-// x_in = half(x / sqrt(sigma^2 + 1)); with `dup` the batch is written twice (CFG: [uncond | cond]).
-template <bool VEC>
-__global__ void __launch_bounds__(256) scale_input_kernel(const f16* __restrict__ x, f16* __restrict__ out,
-                                                           const float* __restrict__ params, long per_sample, int batch,
-                                                           int dup) {
+// ONE kernel for every sampler: 16 B per lane (8 halves), blockIdx.y walks the samples so the per-sample scalars are loaded once
+// per block (no per-element division / parameter fetch); a scalar tail covers per_sample % 8 and unaligned buffers.  What differs
+// between samplers is a policy S, a plain struct that IS the row - its members are the row slots the sampler reads - and states
+//   EPS / NOISE               whether the sampler has an `eps` / a `noise` operand at all (a missing one is a null pointer)
+//   X_PLANES / OUT_PLANES     1, or 2 for [2][batch][per_sample] buffers whose second plane starts per_sample * batch elements in
+//   load(row, noise)          the row slots, from params + b * LB_STEP_STRIDE
+//   reads_noise()             (NOISE only) whether THIS row reads its noise         } uniform over a block (blockIdx.y is the
+//   reads_plane1()            (X_PLANES == 2 only) whether THIS row reads plane 1   } sample); a batch may mix both kinds of row
+//   one<CFG>(x, eu, et, nz, m1, y, m0)   the per-element arithmetic: y to plane 0 of `out`, m0 to plane 1 (OUT_PLANES == 2 only)
+// An operand a row does not read is not touched for that row (zero stands in for it); each element is read before the same index
+// is written and nowhere else, so `out` may be one of the single-plane inputs (bench.py: noise == out).
+// eps layout: CFG == false: eps[b] ; CFG == true: eps[0..B) = uncond, eps[B..2B) = text.
+template <class S, bool VEC, bool CFG>
+__global__ void __launch_bounds__(256) sampler_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps,
+                                                            const f16* __restrict__ noise, f16* __restrict__ out,
+                                                            const float* __restrict__ params, long per_sample, int batch) {
     const long total = per_sample * batch;
     for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const float s = params[b * LB_STEP_STRIDE + 0];
-        const float denom = sqrtf(s * s + 1.0f);
-        const f16* xs = x + (long)b * per_sample;
-        f16* os = out + (long)b * per_sample;
+        const S row = S::load(params + (long)b * LB_STEP_STRIDE, noise);
+        bool rd_noise = false, rd_plane1 = false;
+        if constexpr (S::NOISE) rd_noise = row.reads_noise();
+        if constexpr (S::X_PLANES == 2) rd_plane1 = row.reads_plane1();
+        const long base = (long)b * per_sample;
         const long nvec = VEC ? per_sample >> 3 : 0;
         const long stride = (long)gridDim.x * blockDim.x;
+        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
         for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-            const f16x8 v = *reinterpret_cast<const f16x8*>(xs + i * 8);
-            f16x8 r;
+            const long o = base + i * 8;
+            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
+            const f16x8 eu = S::EPS ? *reinterpret_cast<const f16x8*>(eps + o) : zero8;
+            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
+            const f16x8 nz = rd_noise ? *reinterpret_cast<const f16x8*>(noise + o) : zero8;
+            const f16x8 mv = rd_plane1 ? *reinterpret_cast<const f16x8*>(x + total + o) : zero8;
+            f16x8 y, m;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = (f16)__fdiv_rn((float)v[j], denom);
-            *reinterpret_cast<f16x8*>(os + i * 8) = r;
-            if (dup) *reinterpret_cast<f16x8*>(os + total + i * 8) = r;
+            for (int j = 0; j < 8; ++j) {
+                f16 yj, mj = (f16)0.f;
+                row.template one<CFG>(xv[j], eu[j], et[j], nz[j], mv[j], yj, mj);
+                y[j] = yj;
+                m[j] = mj;
+            }
+            *reinterpret_cast<f16x8*>(out + o) = y;
+            if constexpr (S::OUT_PLANES == 2) *reinterpret_cast<f16x8*>(out + total + o) = m;
         }
         for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
-            const f16 v = (f16)__fdiv_rn((float)xs[i], denom);
-            os[i] = v;
-            if (dup) os[i + total] = v;
+            const long o = base + i;
+            f16 y, m = (f16)0.f;
+            row.template one<CFG>(x[o], S::EPS ? eps[o] : (f16)0.f, CFG ? eps[o + total] : (f16)0.f, rd_noise ? noise[o] : (f16)0.f,
+                                  rd_plane1 ? x[o + total] : (f16)0.f, y, m);
+            out[o] = y;
+            if constexpr (S::OUT_PLANES == 2) out[o + total] = m;
         }
     }
 }
@@ -463,15 +486,44 @@ static dim3 sample_grid(long per_sample, int batch) {
     return dim3((unsigned)gx, (unsigned)(batch < 32768 ? batch : 32768), 1);
 }
 
+// The one launch of sampler_step_kernel.  The vector form needs per_sample % 8 == 0 (which also keeps the second planes, at
+// per_sample * batch elements, 16-byte aligned) and every operand the sampler HAS aligned; one it has not, and a `noise` the caller
+// may leave out, is null and counts as aligned.
+template <class S>
+static void step_launch(const void* x, const void* eps, const void* noise, void* out, const float* params_dev, long per_sample,
+                        int batch, bool cfg, hipStream_t s) {
+    if (!S::EPS) eps = nullptr;
+    if (!S::NOISE) noise = nullptr;
+    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(noise) && aligned16(out);
+    static constexpr decltype(&sampler_step_kernel<S, false, false>) kern[2][2] = {      // [vec][cfg]; no eps, no CFG form
+        {sampler_step_kernel<S, false, false>, sampler_step_kernel<S, false, S::EPS>},
+        {sampler_step_kernel<S, true, false>, sampler_step_kernel<S, true, S::EPS>}};
+    hipLaunchKernelGGL(kern[vec][cfg], sample_grid(per_sample, batch), dim3(256), 0, s, (const f16*)x, (const f16*)eps,
+                       (const f16*)noise, (f16*)out, params_dev, per_sample, batch);
+}
+
+// x_in = half(x / sqrt(sigma^2 + 1)); with DUP the batch is written twice (CFG: [uncond | cond]).
+template <bool DUP>
+struct ScaleInput {
+    static constexpr bool EPS = false, NOISE = false;
+    static constexpr int X_PLANES = 1, OUT_PLANES = DUP ? 2 : 1;
+    float denom;
+    static __device__ __forceinline__ ScaleInput load(const float* row, const f16*) {
+        const float s = row[0];
+        return {sqrtf(s * s + 1.0f)};
+    }
+    template <bool CFG>
+    __device__ __forceinline__ void one(f16 xh, f16, f16, f16, f16, f16& y, f16& copy) const {
+        y = copy = (f16)__fdiv_rn((float)xh, denom);
+    }
+};
+
 extern "C" int lb_scale_model_input_f16(const void* x, void* out, const float* params_dev,
                                         long per_sample, int batch, int dup_for_cfg, void* stream) {
     LB_REQUIRE(per_sample > 0 && batch > 0, "lb_scale_model_input_f16: sizes");
-    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(out);
-    LB_DISPATCH_STMT("lb_scale_model_input_f16",
-                     if (vec) hipLaunchKernelGGL(scale_input_kernel<true>, sample_grid(per_sample, batch), dim3(256), 0, s,
-                                                 (const f16*)x, (f16*)out, params_dev, per_sample, batch, dup_for_cfg);
-                     else hipLaunchKernelGGL(scale_input_kernel<false>, sample_grid(per_sample, batch), dim3(256), 0, s,
-                                             (const f16*)x, (f16*)out, params_dev, per_sample, batch, dup_for_cfg));
+    if (dup_for_cfg)
+        LB_DISPATCH_STMT("lb_scale_model_input_f16", step_launch<ScaleInput<true>>(x, nullptr, nullptr, out, params_dev, per_sample, batch, false, s));
+    LB_DISPATCH_STMT("lb_scale_model_input_f16", step_launch<ScaleInput<false>>(x, nullptr, nullptr, out, params_dev, per_sample, batch, false, s));
 }
 
 // eps layout: cfg == 0: eps[b] ; cfg == 1: eps[0..B) = uncond, eps[B..2B) = text.
@@ -493,49 +545,31 @@ __device__ __forceinline__ f16 euler_one(f16 xh, f16 eu, f16 et, f16 nz, float s
     return (f16)nxt;
 }
 
-template <bool VEC, bool CFG, bool ANC>
-__global__ void __launch_bounds__(256) euler_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps,
-                                                          const f16* __restrict__ noise, f16* __restrict__ out,
-                                                          const float* __restrict__ params, long per_sample, int batch) {
-    const long total = per_sample * batch;
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const float s_from = params[b * LB_STEP_STRIDE + 0];
-        const float dt = params[b * LB_STEP_STRIDE + 4];
-        const float s_up = params[b * LB_STEP_STRIDE + 2];
-        const float g = params[b * LB_STEP_STRIDE + 3];
-        const long base = (long)b * per_sample;
-        const long nvec = VEC ? per_sample >> 3 : 0;
-        const long stride = (long)gridDim.x * blockDim.x;
-        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-            const long o = base + i * 8;
-            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
-            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
-            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
-            const f16x8 nz = ANC ? *reinterpret_cast<const f16x8*>(noise + o) : zero8;
-            f16x8 r;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = euler_one(xv[j], eu[j], et[j], nz[j], s_from, dt, s_up, g, CFG, ANC);
-            *reinterpret_cast<f16x8*>(out + o) = r;
-        }
-        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
-            const long o = base + i;
-            out[o] = euler_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, ANC ? noise[o] : (f16)0.f, s_from, dt, s_up, g, CFG, ANC);
-        }
+template <bool ANC>           // (Euler-ancestral: every row reads its noise; plain Euler has no noise operand)
+struct EulerStep {
+    static constexpr bool EPS = true, NOISE = ANC;
+    static constexpr int X_PLANES = 1, OUT_PLANES = 1;
+    float s_from, dt, s_up, g;
+    static __device__ __forceinline__ EulerStep load(const float* row, const f16*) { return {row[0], row[4], row[2], row[3]}; }
+    __device__ __forceinline__ bool reads_noise() const { return true; }
+    template <bool CFG>
+    __device__ __forceinline__ void one(f16 xh, f16 eu, f16 et, f16 nz, f16, f16& y, f16&) const {
+        y = euler_one(xh, eu, et, nz, s_from, dt, s_up, g, CFG, ANC);
     }
-}
+};
 
-template <bool VEC>
-static void euler_launch(const void* x, const void* eps, const void* noise, void* out, const float* params_dev,
-                         long per_sample, int batch, int cfg, int ancestral, hipStream_t s) {
-    const dim3 grid = sample_grid(per_sample, batch), block(256);
-#define LB_EULER(C, A) hipLaunchKernelGGL((euler_step_kernel<VEC, C, A>), grid, block, 0, s, (const f16*)x, (const f16*)eps, \
-                                          (const f16*)noise, (f16*)out, params_dev, per_sample, batch)
-    if (cfg && ancestral) LB_EULER(true, true);
-    else if (cfg) LB_EULER(true, false);
-    else if (ancestral) LB_EULER(false, true);
-    else LB_EULER(false, false);
-#undef LB_EULER
+// `ancestral`: 0 = Euler, 1 = Euler-ancestral (needs noise).  `cfg`: 0 or 1.
+extern "C" int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
+                                 const float* params_dev, long per_sample, int batch, int cfg,
+                                 int ancestral, void* stream) {
+    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_euler_step_f16: sizes");
+    LB_REQUIRE(ancestral != 2, "lb_euler_step_f16: ancestral is 0 or 1 (the latent-consistency step is lb_lcm_step_f16)");
+    LB_REQUIRE(ancestral == 0 || ancestral == 1, "lb_euler_step_f16: ancestral is 0 or 1");
+    LB_REQUIRE(cfg == 0 || cfg == 1, "lb_euler_step_f16: cfg is 0 or 1");
+    LB_REQUIRE(!ancestral || noise != nullptr, "lb_euler_step_f16: ancestral step needs noise");
+    if (ancestral)
+        LB_DISPATCH_STMT("lb_euler_step_f16", step_launch<EulerStep<true>>(x, eps, noise, out, params_dev, per_sample, batch, cfg, s));
+    LB_DISPATCH_STMT("lb_euler_step_f16", step_launch<EulerStep<false>>(x, eps, noise, out, params_dev, per_sample, batch, cfg, s));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -577,39 +611,30 @@ __device__ __forceinline__ f16 ddim_one(f16 xh, f16 eu, f16 et, float inv_sa_t, 
     return r16(__fadd_rn((float)t3, (float)dir));
 }
 
-template <bool VEC, bool CFG>
-__global__ void __launch_bounds__(256) ddim_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps, f16* __restrict__ out,
-                                                         const float* __restrict__ params, long per_sample, int batch) {
-    const long total = per_sample * batch;
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const float sa_t = params[b * LB_STEP_STRIDE + 6], sa_p = params[b * LB_STEP_STRIDE + 2], g = params[b * LB_STEP_STRIDE + 3];      // (sa_t: the RECIPROCAL 1 / sqrt(abar_t))
-        const float sb_t = params[b * LB_STEP_STRIDE + 4], sb_p = params[b * LB_STEP_STRIDE + 5];
-        const long base = (long)b * per_sample;
-        const long nvec = VEC ? per_sample >> 3 : 0;
-        const long stride = (long)gridDim.x * blockDim.x;
-        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-            const long o = base + i * 8;
-            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
-            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
-            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
-            f16x8 r;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = ddim_one(xv[j], eu[j], et[j], sa_t, sa_p, sb_t, sb_p, g, CFG);
-            *reinterpret_cast<f16x8*>(out + o) = r;
-        }
-        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
-            const long o = base + i;
-            out[o] = ddim_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, sa_t, sa_p, sb_t, sb_p, g, CFG);
-        }
+struct DdimStep {
+    static constexpr bool EPS = true, NOISE = false;
+    static constexpr int X_PLANES = 1, OUT_PLANES = 1;
+    float inv_sa_t, sa_p, sb_t, sb_p, g;            // (inv_sa_t: the RECIPROCAL 1 / sqrt(abar_t))
+    static __device__ __forceinline__ DdimStep load(const float* row, const f16*) { return {row[6], row[2], row[4], row[5], row[3]}; }
+    template <bool CFG>
+    __device__ __forceinline__ void one(f16 xh, f16 eu, f16 et, f16, f16, f16& y, f16&) const {
+        y = ddim_one(xh, eu, et, inv_sa_t, sa_p, sb_t, sb_p, g, CFG);
     }
+};
+
+// `cfg`: 0 or 1 (classifier-free guidance: eps holds 2 * batch samples).
+extern "C" int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
+                                int cfg, void* stream) {
+    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_ddim_step_f16: sizes");
+    LB_REQUIRE((cfg & ~3) == 0, "lb_ddim_step_f16: cfg bits (cfg is 0 or 1)");
+    LB_REQUIRE((cfg & 2) == 0, "lb_ddim_step_f16: cfg is 0 or 1 (the DPM-Solver++ 2M step is lb_dpmpp2m_step_f16)");
+    LB_DISPATCH_STMT("lb_ddim_step_f16", step_launch<DdimStep>(x, eps, nullptr, out, params_dev, per_sample, batch, cfg, s));
 }
 
 // ------------------------------------------------------------------------------------------------
 // DPM-Solver++ 2M step (Lu et al. 2022, "DPM-Solver++", algorithm 2: multistep, order 2, data prediction; the midpoint form
 // diffusers' DPMSolverMultistepScheduler takes with algorithm_type "dpmsolver++", epsilon prediction, final sigma zero).
-// Bit 1 of lb_ddim_step_f16's `cfg` (DDIM is this solver at order 1; a dedicated symbol follows when the replay registry is
-// next opened).  `x` and `out` are TWO-PLANE buffers [2][batch][per_sample]: plane 0 of `x` the latent, plane 1 the previous
+// lb_dpmpp2m_step_f16 (DDIM is this solver at order 1).  `x` and `out` are TWO-PLANE buffers [2][batch][per_sample]: plane 0 of `x` the latent, plane 1 the previous
 // step's x0 prediction m1; plane 0 of `out` the next latent, plane 1 this step's x0 prediction m0.  The kernel keeps no state:
 // the caller feeds `out` of step i as `x` of step i + 1 (so `x` and `out` must not overlap - not checked).
 //   params row: {0 (sigma of lb_scale_model_input_f16: the identity), sigma_s, ratio, guidance, c0, c1, 1 / alpha_s, 1 / r0}
@@ -652,77 +677,30 @@ __device__ __forceinline__ void dpmpp2m_one(f16 xh, f16 eu, f16 et, f16 m1, floa
     m0_out = m0;
 }
 
-template <bool VEC, bool CFG>
-__global__ void __launch_bounds__(256) dpmpp2m_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps, f16* __restrict__ out,
-                                                            const float* __restrict__ params, long per_sample, int batch) {
-    const long total = per_sample * batch;          // (also the plane stride of x and out)
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const float* row = params + (long)b * LB_STEP_STRIDE;
-        const float sig = row[1], ratio = row[2], g = row[3], c0 = row[4], c1 = row[5], inv_alpha = row[6], inv_r0 = row[7];
-        const bool second = c1 != 0.f;                // (uniform over the block: blockIdx.y is the sample)
-        const long base = (long)b * per_sample;
-        const long nvec = VEC ? per_sample >> 3 : 0;
-        const long stride = (long)gridDim.x * blockDim.x;
-        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-            const long o = base + i * 8;
-            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
-            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
-            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
-            const f16x8 mv = second ? *reinterpret_cast<const f16x8*>(x + total + o) : zero8;
-            f16x8 y, m;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                f16 yj, mj;
-                dpmpp2m_one(xv[j], eu[j], et[j], mv[j], sig, ratio, g, c0, c1, inv_alpha, inv_r0, CFG, second, yj, mj);
-                y[j] = yj;
-                m[j] = mj;
-            }
-            *reinterpret_cast<f16x8*>(out + o) = y;
-            *reinterpret_cast<f16x8*>(out + total + o) = m;
-        }
-        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
-            const long o = base + i;
-            f16 y, m;
-            dpmpp2m_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, second ? x[o + total] : (f16)0.f, sig, ratio, g, c0, c1,
-                        inv_alpha, inv_r0, CFG, second, y, m);
-            out[o] = y;
-            out[o + total] = m;
-        }
+struct Dpmpp2mStep {
+    static constexpr bool EPS = true, NOISE = false;
+    static constexpr int X_PLANES = 2, OUT_PLANES = 2;
+    float sig, ratio, g, c0, c1, inv_alpha, inv_r0;
+    static __device__ __forceinline__ Dpmpp2mStep load(const float* row, const f16*) { return {row[1], row[2], row[3], row[4], row[5], row[6], row[7]}; }
+    __device__ __forceinline__ bool reads_plane1() const { return c1 != 0.f; }          // a second-order row
+    template <bool CFG>
+    __device__ __forceinline__ void one(f16 xh, f16 eu, f16 et, f16, f16 m1, f16& y, f16& m0) const {
+        dpmpp2m_one(xh, eu, et, m1, sig, ratio, g, c0, c1, inv_alpha, inv_r0, CFG, c1 != 0.f, y, m0);
     }
-}
+};
 
-// `cfg`: bit 0 = classifier-free guidance (eps holds 2 * batch samples); bit 1 = the DPM-Solver++ 2M step above on two-plane
-// `x` / `out`.  With bit 1 clear this is the DDIM launch it always was.  Any other bit is refused (before bit 1 existed every
-// non-zero value meant CFG; nothing passed anything but 0 or 1).
-extern "C" int lb_ddim_step_f16(const void* x, const void* eps, void* out, const float* params_dev, long per_sample, int batch,
-                                int cfg, void* stream) {
-    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_ddim_step_f16: sizes");
-    LB_REQUIRE((cfg & ~3) == 0, "lb_ddim_step_f16: cfg bits (bit 0 CFG, bit 1 DPM-Solver++ 2M step on two-plane buffers)");
-    const dim3 grid = sample_grid(per_sample, batch), block(256);
-    if (cfg & 2) {
-        // (the second plane starts per_sample * batch elements in: the vector form needs that offset to keep 16-byte alignment,
-        //  which per_sample % 8 == 0 gives)
-        const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
-        const int c = cfg & 1;
-#define LB_DPMPP(V, C) hipLaunchKernelGGL((dpmpp2m_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (f16*)out, params_dev, per_sample, batch)
-        LB_DISPATCH_STMT("lb_ddim_step_f16",
-                         if (vec && c) LB_DPMPP(true, true); else if (vec) LB_DPMPP(true, false);
-                         else if (c) LB_DPMPP(false, true); else LB_DPMPP(false, false));
-#undef LB_DPMPP
-    }
-    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out);
-#define LB_DDIM(V, C) hipLaunchKernelGGL((ddim_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (f16*)out, params_dev, per_sample, batch)
-    LB_DISPATCH_STMT("lb_ddim_step_f16",
-                     if (vec && cfg) LB_DDIM(true, true); else if (vec) LB_DDIM(true, false);
-                     else if (cfg) LB_DDIM(false, true); else LB_DDIM(false, false));
-#undef LB_DDIM
+// `state` and `out`: two-plane buffers [2][batch][per_sample], which must not overlap (not checked).  `cfg`: 0 or 1.
+extern "C" int lb_dpmpp2m_step_f16(const void* state, const void* eps, void* out, const float* params_dev, long per_sample,
+                                   int batch, int cfg, void* stream) {
+    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_dpmpp2m_step_f16: sizes");
+    LB_REQUIRE(cfg == 0 || cfg == 1, "lb_dpmpp2m_step_f16: cfg bits (cfg is 0 or 1)");
+    LB_DISPATCH_STMT("lb_dpmpp2m_step_f16", step_launch<Dpmpp2mStep>(state, eps, nullptr, out, params_dev, per_sample, batch, cfg, s));
 }
 
 // ------------------------------------------------------------------------------------------------
 // Latent-consistency step (Luo et al. 2023, multistep consistency sampling; diffusers 0.25.0 LCMScheduler.step as LCM-SDXL
-// configures it: epsilon prediction, timestep_scaling 10, sigma_data 0.5, no clipping / thresholding).  Mode 2 of
-// lb_euler_step_f16 (a dedicated symbol follows when the replay registry is next opened).
+// configures it: epsilon prediction, timestep_scaling 10, sigma_data 0.5, no clipping / thresholding).
+// lb_lcm_step_f16.
 //   params row: {0 (sigma of lb_scale_model_input_f16: the identity, as for DDIM), c_skip, sqrt(abar_prev), guidance,
 //                sqrt(1 - abar_t), sqrt(1 - abar_prev), 1 / sqrt(abar_t) [fp32], c_out}
 // Like DDIM, diffusers does not upcast: fp16 tensors, 0-dim fp32 / Python-float coefficients, so EVERY tensor operation
@@ -758,62 +736,26 @@ __device__ __forceinline__ f16 lcm_one(f16 xh, f16 eu, f16 et, f16 nz, float c_s
     return r16(__fadd_rn((float)a, (float)b));
 }
 
-template <bool VEC, bool CFG>
-__global__ void __launch_bounds__(256) lcm_step_kernel(const f16* __restrict__ x, const f16* __restrict__ eps,
-                                                        const f16* __restrict__ noise, f16* __restrict__ out,
-                                                        const float* __restrict__ params, long per_sample, int batch) {
-    const long total = per_sample * batch;
-    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
-        const float* row = params + (long)b * LB_STEP_STRIDE;
-        const float c_skip = row[1], sa_p = row[2], g = row[3], sb_t = row[4], sb_p = row[5], inv_sa_t = row[6], c_out = row[7];
-        const bool last = sb_p == 0.f || noise == nullptr;        // (uniform over the block: blockIdx.y is the sample)
-        const long base = (long)b * per_sample;
-        const long nvec = VEC ? per_sample >> 3 : 0;
-        const long stride = (long)gridDim.x * blockDim.x;
-        const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-            const long o = base + i * 8;
-            const f16x8 xv = *reinterpret_cast<const f16x8*>(x + o);
-            const f16x8 eu = *reinterpret_cast<const f16x8*>(eps + o);
-            const f16x8 et = CFG ? *reinterpret_cast<const f16x8*>(eps + total + o) : zero8;
-            const f16x8 nz = last ? zero8 : *reinterpret_cast<const f16x8*>(noise + o);
-            f16x8 r;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) r[j] = lcm_one(xv[j], eu[j], et[j], nz[j], c_skip, c_out, inv_sa_t, sa_p, sb_t, sb_p, g, CFG, last);
-            *reinterpret_cast<f16x8*>(out + o) = r;
-        }
-        for (long i = (nvec << 3) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < per_sample; i += stride) {
-            const long o = base + i;
-            out[o] = lcm_one(x[o], eps[o], CFG ? eps[o + total] : (f16)0.f, last ? (f16)0.f : noise[o], c_skip, c_out, inv_sa_t, sa_p,
-                             sb_t, sb_p, g, CFG, last);
-        }
+struct LcmStep {
+    static constexpr bool EPS = true, NOISE = true;
+    static constexpr int X_PLANES = 1, OUT_PLANES = 1;
+    float c_skip, sa_p, g, sb_t, sb_p, inv_sa_t, c_out;
+    bool renoise;                     // not a last step, and there is noise to read
+    static __device__ __forceinline__ LcmStep load(const float* row, const f16* noise) {
+        return {row[1], row[2], row[3], row[4], row[5], row[6], row[7], row[5] != 0.f && noise != nullptr};
     }
-}
+    __device__ __forceinline__ bool reads_noise() const { return renoise; }
+    template <bool CFG>
+    __device__ __forceinline__ void one(f16 xh, f16 eu, f16 et, f16 nz, f16, f16& y, f16&) const {
+        y = lcm_one(xh, eu, et, nz, c_skip, c_out, inv_sa_t, sa_p, sb_t, sb_p, g, CFG, !renoise);
+    }
+};
 
-// `ancestral` is a MODE: 0 = Euler, 1 = Euler-ancestral (needs noise), 2 = latent-consistency step (params rows as above).
-// Mode 2 only: bit 1 of `cfg` is the host's statement that EVERY row is a last step (slot 5 == 0) - only then may `noise` be
-// null.  Bit 0 of `cfg` is the CFG flag in every mode.
-extern "C" int lb_euler_step_f16(const void* x, const void* eps, const void* noise, void* out,
-                                 const float* params_dev, long per_sample, int batch, int cfg,
-                                 int ancestral, void* stream) {
-    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_euler_step_f16: sizes");
-    LB_REQUIRE(ancestral >= 0 && ancestral <= 2, "lb_euler_step_f16: mode (0 Euler, 1 Euler-ancestral, 2 LCM)");
-    LB_REQUIRE(ancestral != 1 || noise != nullptr, "lb_euler_step_f16: ancestral step needs noise");
-    if (ancestral == 2) {
-        LB_REQUIRE((cfg & ~3) == 0, "lb_euler_step_f16: cfg bits (LCM mode: bit 0 CFG, bit 1 every row is a last step)");
-        LB_REQUIRE((cfg & 2) || noise != nullptr, "lb_euler_step_f16: LCM step with a row that is not a last step needs noise");
-        const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out) && (noise == nullptr || aligned16(noise));
-        const int c = cfg & 1;
-        const dim3 grid = sample_grid(per_sample, batch), block(256);
-#define LB_LCM(V, C) hipLaunchKernelGGL((lcm_step_kernel<V, C>), grid, block, 0, s, (const f16*)x, (const f16*)eps, (const f16*)noise, \
-                                        (f16*)out, params_dev, per_sample, batch)
-        LB_DISPATCH_STMT("lb_euler_step_f16",
-                         if (vec && c) LB_LCM(true, true); else if (vec) LB_LCM(true, false);
-                         else if (c) LB_LCM(false, true); else LB_LCM(false, false));
-#undef LB_LCM
-    }
-    const bool vec = per_sample % 8 == 0 && aligned16(x) && aligned16(eps) && aligned16(out) && (!ancestral || aligned16(noise));
-    LB_DISPATCH_STMT("lb_euler_step_f16",
-                     if (vec) euler_launch<true>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s);
-                     else euler_launch<false>(x, eps, noise, out, params_dev, per_sample, batch, cfg, ancestral, s));
+// `all_last` is the host's statement that EVERY row is a last step (slot 5 == 0) - only then may `noise` be null.  `cfg`: 0 or 1.
+extern "C" int lb_lcm_step_f16(const void* x, const void* eps, const void* noise, void* out, const float* params_dev,
+                               long per_sample, int batch, int cfg, int all_last, void* stream) {
+    LB_REQUIRE(per_sample > 0 && batch > 0, "lb_lcm_step_f16: sizes");
+    LB_REQUIRE(cfg == 0 || cfg == 1, "lb_lcm_step_f16: cfg bits (cfg is 0 or 1)");
+    LB_REQUIRE(all_last || noise != nullptr, "lb_lcm_step_f16: LCM step with a row that is not a last step needs noise");
+    LB_DISPATCH_STMT("lb_lcm_step_f16", step_launch<LcmStep>(x, eps, noise, out, params_dev, per_sample, batch, cfg, s));
 }

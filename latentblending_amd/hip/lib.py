@@ -190,6 +190,8 @@ SIGNATURES = {
     "lb_scale_model_input_f16": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp], _L),
     "lb_euler_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp], _L),
     "lb_ddim_step_f16": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp], _L),
+    "lb_lcm_step_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _vp], _L),
+    "lb_dpmpp2m_step_f16": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _vp], _L),
     "lb_counter_noise_f16": (_i, [_vp, _vp, _l, _i, _i, _vp], _L),
     "lb_gemm_f16": (_i, [_pp, _vp], _L),
     "lb_gemm_workspace_bytes": (_l, [_i, _i], _V),

@@ -128,16 +128,12 @@ def euler_step(x, eps, params, noise=None, cfg=False, ancestral=False) -> torch.
         noise = _operand("euler_step", noise, noise.contiguous())
     out = torch.empty_like(x)
     api.lb_euler_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
-                          x[0].numel(), x.shape[0], int(cfg), int(ancestral), stream_ptr())
+                          x[0].numel(), x.shape[0], int(bool(cfg)), int(bool(ancestral)), stream_ptr())
     return out
 
 
-EULER_MODE_EULER, EULER_MODE_ANCESTRAL, EULER_MODE_LCM = 0, 1, 2      # ``ancestral`` argument of lb_euler_step_f16
-LCM_CFG_ALL_LAST = 2                                                  # bit 1 of its ``cfg`` argument (mode 2 only)
-
-
 def lcm_step(x, eps, params, noise=None, cfg=False, all_last: Optional[bool] = None) -> torch.Tensor:
-    """Latent-consistency step (mode 2 of ``lb_euler_step_f16``); ``params`` rows as NativeLCMScheduler.step_row builds them.
+    """Latent-consistency step (``lb_lcm_step_f16``); ``params`` rows as NativeLCMScheduler.step_row builds them.
     ``noise`` may be None only when EVERY row is a last step of its schedule (slot 5 == 0: the denoised latent is the result
     and the noise is not read).  That is decided on the host, never by reading the rows back: from the host mirror
     ``step_params`` leaves on the tensor it returns, or - for a view of such a tensor, which has none - from ``all_last``,
@@ -158,25 +154,21 @@ def lcm_step(x, eps, params, noise=None, cfg=False, all_last: Optional[bool] = N
     if noise is not None:
         assert noise.shape == x.shape and noise.dtype == F16, "lcm_step: noise must be an fp16 tensor of the latent's shape"
     out = torch.empty_like(x)
-    api.lb_euler_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
-                          x[0].numel(), x.shape[0], int(bool(cfg)) | (LCM_CFG_ALL_LAST if noise is None else 0),
-                          EULER_MODE_LCM, stream_ptr())
+    api.lb_lcm_step_f16(x.data_ptr(), eps.data_ptr(), _ptr(noise), out.data_ptr(), params.data_ptr(),
+                        x[0].numel(), x.shape[0], int(bool(cfg)), int(noise is None), stream_ptr())
     return out
 
 
 def ddim_step(x, eps, params, cfg=False) -> torch.Tensor:
     """DDIM step (eta = 0); ``params`` rows as NativeDDIMScheduler.step_row builds them."""
     out = torch.empty_like(x)
-    api.lb_ddim_step_f16(x.data_ptr(), eps.data_ptr(), out.data_ptr(), params.data_ptr(), x[0].numel(), x.shape[0], int(cfg),
-                         stream_ptr())
+    api.lb_ddim_step_f16(x.data_ptr(), eps.data_ptr(), out.data_ptr(), params.data_ptr(), x[0].numel(), x.shape[0],
+                         int(bool(cfg)), stream_ptr())
     return out
 
 
-DDIM_CFG_DPMPP_2M = 2                                                 # bit 1 of the ``cfg`` argument of lb_ddim_step_f16
-
-
 def dpmpp2m_step(state, eps, params, cfg=False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """DPM-Solver++ 2M step (bit 1 of ``cfg`` of ``lb_ddim_step_f16``); ``params`` rows as NativeDPMSolverPP2MScheduler.step_row
+    """DPM-Solver++ 2M step (``lb_dpmpp2m_step_f16``); ``params`` rows as NativeDPMSolverPP2MScheduler.step_row
     builds them.  ``state`` is ``[2, B, ...]`` fp16: plane 0 the latents, plane 1 the previous step's x0 prediction (not read for
     a first-order row).  Returns the new state - next latents and this step's x0 prediction - in ``out``, which must not share
     memory with ``state``; while a program records, the caller owns ``out``."""
@@ -195,8 +187,8 @@ def dpmpp2m_step(state, eps, params, cfg=False, out: Optional[torch.Tensor] = No
     nbytes = state.numel() * state.element_size()
     if out.data_ptr() < state.data_ptr() + nbytes and state.data_ptr() < out.data_ptr() + nbytes:
         raise ValueError("dpmpp2m_step: out aliases state (the step reads plane 1 of state while it writes plane 1 of out)")
-    api.lb_ddim_step_f16(state.data_ptr(), eps.data_ptr(), out.data_ptr(), params.data_ptr(), state[0, 0].numel(), B,
-                         int(bool(cfg)) | DDIM_CFG_DPMPP_2M, stream_ptr())
+    api.lb_dpmpp2m_step_f16(state.data_ptr(), eps.data_ptr(), out.data_ptr(), params.data_ptr(), state[0, 0].numel(), B,
+                            int(bool(cfg)), stream_ptr())
     return out
 
 

@@ -2,7 +2,7 @@
 Appendix B.2), DDIM (eta 0), the latent-consistency sampler (LCM) and DPM-Solver++ 2M on uniform or Karras sigmas.  Only the
 sigma / abar / timestep tables and the per-step scalar coefficients live here (``step_row``: Python floats, float64 numpy or
 0-dim fp32 tensors, as each sampler's diffusers counterpart forms them); the tensor work runs in ``lb_scale_model_input_f16``,
-``lb_euler_step_f16`` (Euler; mode 2 = LCM) and ``lb_ddim_step_f16`` (DDIM; bit 1 of ``cfg`` = DPM-Solver++ 2M).
+``lb_euler_step_f16``, ``lb_ddim_step_f16``, ``lb_lcm_step_f16`` and ``lb_dpmpp2m_step_f16`` - one entry point per sampler.
 
 Every sampler derives from :class:`NativeScheduler`, which owns what they share - the schedule bookkeeping, the diffusers-style
 ``scale_model_input`` / ``step`` pair the generic holder loop drives, the noise draws and the questions the native loops
@@ -303,7 +303,7 @@ class NativeLCMScheduler(NativeScheduler):
     ``LCMScheduler`` configures it for SDXL: scaled-linear betas, original_inference_steps = 50, timestep_scaling = 10,
     sigma_data = 0.5, epsilon prediction, no thresholding / clipping.  Restated from the published algorithm and that class's
     documented behaviour - not checked against diffusers itself.  Host side = the fp32 abar table (DDIM's), the timestep
-    selection and the per-step coefficients; the tensor work is mode 2 of ``lb_euler_step_f16``.  ``scale_model_input`` is the
+    selection and the per-step coefficients; the tensor work is ``lb_lcm_step_f16``.  ``scale_model_input`` is the
     identity and ``init_noise_sigma`` is 1.  Every step but the LAST of the schedule re-noises the denoised latent with one fresh
     fp16 draw (``noise_draws``)."""
     kind = "lcm"
@@ -411,7 +411,7 @@ class NativeDPMSolverPP2MScheduler(NativeScheduler):
     epsilon prediction, over uniform ("leading", steps_offset 1) or Karras (Karras et al. 2022, eq. 5, rho = 7) sigmas - what user
     interfaces call "DPM++ 2M" / "DPM++ 2M Karras".  Restated from the paper and that class's documented behaviour - not checked
     against diffusers itself.  Host side = the float64 sigma table (``_sigma_table``, as for Euler), the schedule and the per-step
-    coefficients, each rounded ONCE to fp32 on upload; the tensor work is bit 1 of ``cfg`` of ``lb_ddim_step_f16``.  The sampler
+    coefficients, each rounded ONCE to fp32 on upload; the tensor work is ``lb_dpmpp2m_step_f16``.  The sampler
     has a history (``multistep``): ``device_step`` takes and returns a two-plane state (latents, previous x0 prediction), and
     ``step_row`` heeds ``first`` - the first step a sample executes has no history and is first order, like the schedule's last
     step (whose target sigma is 0).  The reference's restartable loop calls ``set_timesteps`` at the start of every run, which

@@ -67,6 +67,7 @@ class Case:
         self.thunk = None
         self.mutate = None           # optional: writes new values into input buffers (params_dev) between replays
         self.decoy = None            # valid device memory the host pointer arrays are pointed at after recording
+        self.operands = {}           # optional: the builder's tensors by name, for a test that checks the results against a reference
 
     # -- building ---------------------------------------------------------------------------
     def guarded(self, name, rows, cols, ld, dtype, back_rows=256, full=True, fill=None, sentinel=None):
@@ -799,6 +800,91 @@ def _scheduler():
         params.copy_(o.step_params([(2.9, 1.8, 0.0, 5.0, -1.1)] * B, DEV))
         params_anc.copy_(o.step_params([(2.9, 1.3, 1.2, 5.0, -1.6)] * B, DEV))
         params_ddim.copy_(o.step_params([nd.step_row(7, 5.0)] * B, DEV))
+    c.mutate = mutate
+    return c.freeze()
+
+
+# per sample (schedule length, step index, guidance): the rows the LCM case records under, and the ones the protocol rewrites them to
+LCM_PLANS = {"recorded": [(4, 2, 3.0), (8, 4, 3.5)], "recorded_last": [(4, 3, 3.0), (8, 7, 3.5)],
+             "rewritten": [(4, 0, 3.0), (8, 0, 3.5)], "rewritten_last": [(8, 7, 2.0), (3, 2, 2.0)]}
+# per sample (schedule length, Karras?, step index, first step of its run?, guidance): a first-order row, a second-order row and a
+# schedule's last row in one batch; rewritten to second-order rows throughout
+DPMPP_PLANS = {"recorded": [(8, True, 3, True, 3.3), (20, True, 7, False, 4.0), (6, False, 5, False, 2.7)],
+               "rewritten": [(8, True, 3, False, 3.0), (20, True, 7, False, 3.3), (6, False, 2, False, 2.5)]}
+
+
+def _lcm_rows(plan):
+    from latentblending_amd.native.scheduler import NativeLCMScheduler
+    rows = []
+    for n, i, g in plan:
+        s = NativeLCMScheduler(device="cpu")
+        s.set_timesteps(n)
+        rows.append(s.step_row(i, g))
+    return rows
+
+
+def _dpmpp_rows(plan):
+    from latentblending_amd.native.scheduler import NativeDPMSolverPP2MScheduler
+    rows = []
+    for n, karras, i, first, g in plan:
+        s = NativeDPMSolverPP2MScheduler(use_karras_sigmas=karras, device="cpu")
+        s.set_timesteps(n)
+        rows.append(s.step_row(i, g, first=first))
+    return rows
+
+
+@case("lcm_steps", "lb_lcm_step_f16")
+def _lcm_steps():
+    """The latent-consistency step plain, under CFG, and on last-step rows with a null noise pointer (``all_last`` was recorded:
+    the rewritten rows of that launch stay last-step rows).  tests/test_lcm_gpu.py checks the direct launch against the
+    restatement; ``operands`` is what it needs for that."""
+    o, l = _ops(), _lib()
+    B, n = 2, 8 * 37 + 3
+    c = Case("lcm_steps", ["lb_lcm_step_f16"] * 3)
+    x, eps, noise = c.dev(_rnd(B, n, seed=15, scale=4.0)), c.dev(_rnd(2 * B, n, seed=16)), c.dev(_rnd(B, n, seed=17))
+    params = c.inp(o.step_params(_lcm_rows(LCM_PLANS["recorded"]), DEV))
+    params_last = c.inp(o.step_params(_lcm_rows(LCM_PLANS["recorded_last"]), DEV))
+    outs = {k: c.guarded(k, B, n, n, F16, back_rows=2) for k in ("lcm", "lcm_cfg", "lcm_last_null_noise")}
+    c.operands = dict(B=B, n=n, x=x, eps=eps, noise=noise, outs=outs)
+    P = lambda t: t.data_ptr()      # noqa: E731
+
+    def thunk():
+        a, s = l.api, _stream()
+        a.lb_lcm_step_f16(P(x), P(eps), P(noise), P(outs["lcm"]), P(params), n, B, 0, 0, s)
+        a.lb_lcm_step_f16(P(x), P(eps), P(noise), P(outs["lcm_cfg"]), P(params), n, B, 1, 0, s)
+        a.lb_lcm_step_f16(P(x), P(eps), None, P(outs["lcm_last_null_noise"]), P(params_last), n, B, 0, 1, s)
+    c.thunk = thunk
+
+    def mutate():
+        params.copy_(o.step_params(_lcm_rows(LCM_PLANS["rewritten"]), DEV))
+        params_last.copy_(o.step_params(_lcm_rows(LCM_PLANS["rewritten_last"]), DEV))
+    c.mutate = mutate
+    return c.freeze()
+
+
+@case("dpmpp_steps", "lb_dpmpp2m_step_f16")
+def _dpmpp_steps():
+    """The DPM-Solver++ 2M step on two-plane buffers: plain, under CFG, and chained (``out`` of op 0 is ``state`` of op 2).
+    tests/test_dpmpp_gpu.py checks the direct launches against the restatement; ``operands`` is what it needs for that."""
+    o, l = _ops(), _lib()
+    B, n = 3, 8 * 37
+    c = Case("dpmpp_steps", ["lb_dpmpp2m_step_f16"] * 3)
+    latents, m1 = _rnd(B, n, seed=15, scale=4.0).clamp(-15, 15), _rnd(B, n, seed=16, scale=1.5)
+    x, e = c.dev(torch.stack([latents, m1])), c.dev(_rnd(2 * B, n, seed=17))
+    params = c.inp(o.step_params(_dpmpp_rows(DPMPP_PLANS["recorded"]), DEV))
+    outs = {k: c.guarded(k, 2 * B, n, n, F16, back_rows=2) for k in ("dpmpp", "dpmpp_cfg", "dpmpp_chained")}
+    c.operands = dict(B=B, n=n, state=x, eps=e, outs=outs)
+    P = lambda t: t.data_ptr()      # noqa: E731
+
+    def thunk():
+        a, s = l.api, _stream()
+        a.lb_dpmpp2m_step_f16(P(x), P(e), P(outs["dpmpp"]), P(params), n, B, 0, s)
+        a.lb_dpmpp2m_step_f16(P(x), P(e), P(outs["dpmpp_cfg"]), P(params), n, B, 1, s)
+        a.lb_dpmpp2m_step_f16(P(outs["dpmpp"]), P(e), P(outs["dpmpp_chained"]), P(params), n, B, 0, s)
+    c.thunk = thunk
+
+    def mutate():
+        params.copy_(o.step_params(_dpmpp_rows(DPMPP_PLANS["rewritten"]), DEV))
     c.mutate = mutate
     return c.freeze()
 

@@ -193,12 +193,23 @@ def test_launcher_refuses_unknown_cfg_bits_and_bad_sizes():
     """Argument errors come back through the C-ABI error channel before anything is launched (fake aligned pointers)."""
     from latentblending_amd.hip import lib
     for bad in (4, 5, 8, -1):
-        with pytest.raises(RuntimeError, match="cfg bits"):
+        with pytest.raises(RuntimeError, match="lb_ddim_step_f16: cfg bits"):
+            lib.api.lb_ddim_step_f16(16, 16, 16, 16, 8, 1, bad, None)
+        with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16: cfg bits"):
+            lib.api.lb_dpmpp2m_step_f16(16, 16, 16, 16, 8, 1, bad, None)
+    for bad in (2, 3):
+        with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16: cfg bits"):
+            lib.api.lb_dpmpp2m_step_f16(16, 16, 16, 16, 8, 1, bad, None)
+        # the overloading is gone: what used to select the DPM-Solver++ 2M step is refused, and the message says where it went
+        with pytest.raises(RuntimeError, match="lb_ddim_step_f16: .*lb_dpmpp2m_step_f16"):
             lib.api.lb_ddim_step_f16(16, 16, 16, 16, 8, 1, bad, None)
     for per_sample, batch in ((0, 1), (8, 0), (-8, 1)):
         for cfg in (0, 2, 3):
-            with pytest.raises(RuntimeError, match="sizes"):
+            with pytest.raises(RuntimeError, match="lb_ddim_step_f16: sizes"):
                 lib.api.lb_ddim_step_f16(16, 16, 16, 16, per_sample, batch, cfg, None)
+        for cfg in (0, 1):
+            with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16: sizes"):
+                lib.api.lb_dpmpp2m_step_f16(16, 16, 16, 16, per_sample, batch, cfg, None)
 
 
 def test_wrapper_refuses_one_plane_state_aliasing_out_and_a_missing_out_while_recording():

@@ -1,4 +1,4 @@
-"""The second-order sampler on a real MI355X: the DPM-Solver++ 2M step kernel (bit 1 of ``cfg`` of lb_ddim_step_f16) bit for bit
+"""The second-order sampler on a real MI355X: the DPM-Solver++ 2M step kernel (lb_dpmpp2m_step_f16) bit for bit
 against the torch restatement in tests/_dpmpp_ref.py, its memory contract, a chain of steps, the unchanged DDIM bits of cfg 0 and
 1, recorded / replayed / graph launches, and whole branched transitions under ``scheduler="dpmpp_2m"`` / ``"dpmpp_2m_karras"``.
 
@@ -118,8 +118,8 @@ def test_dpmpp_step_kernel_matches_the_restatement_bit_for_bit(per_sample, off16
         xd, ed = put(poisoned), put(e)
         out, chk = guarded(2 * B, per_sample, per_sample, F16, DEV, back_rows=4)
         params = ops.step_params(native_rows(plan), DEV)
-        lib.api.lb_ddim_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), per_sample, B,
-                                 int(cfg) | 2, torch.cuda.current_stream().cuda_stream)
+        lib.api.lb_dpmpp2m_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), per_sample, B,
+                                    int(cfg), torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         chk.assert_intact("dpmpp out")
         chk.assert_fully_written("dpmpp out")
@@ -172,7 +172,7 @@ def test_three_step_chain_feeding_out_back_as_x(cfg):
 
 def test_ddim_cfg_0_and_1_keep_the_parent_commits_bits():
     """tests/golden/dpmpp_ddim_parent_bits.json: lb_ddim_step_f16 with cfg 0 and 1 (vector and scalar form) as the commit before
-    bit 1 existed computed them on an MI355X, on one fixed seeded input."""
+    the DPM-Solver++ 2M step existed computed them on an MI355X, on one fixed seeded input."""
     ops = ops_mod()
     with open(os.path.join(GOLD, "dpmpp_ddim_parent_bits.json")) as fh:
         gold = json.load(fh)
@@ -197,8 +197,15 @@ def test_unknown_cfg_bits_are_refused_before_any_launch():
     out, chk = guarded(2 * B, n, n, F16, DEV, back_rows=2)
     s = torch.cuda.current_stream().cuda_stream
     for bad in (4, 6, 7):
-        with pytest.raises(RuntimeError, match="cfg bits"):
+        with pytest.raises(RuntimeError, match="lb_ddim_step_f16: cfg bits"):
             lib.api.lb_ddim_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), n, B, bad, s)
+        with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16: cfg bits"):
+            lib.api.lb_dpmpp2m_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), n, B, bad, s)
+    for bad in (2, 3):              # what used to select this step on the DDIM symbol: refused there, and no CFG value here
+        with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16"):
+            lib.api.lb_ddim_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), n, B, bad, s)
+        with pytest.raises(RuntimeError, match="lb_dpmpp2m_step_f16: cfg bits"):
+            lib.api.lb_dpmpp2m_step_f16(xd.data_ptr(), ed.data_ptr(), out.data_ptr(), params.data_ptr(), n, B, bad, s)
     with pytest.raises(ValueError, match="aliases"):
         ops.dpmpp2m_step(xd, ed, params, out=xd)
     torch.cuda.synchronize()
@@ -207,31 +214,19 @@ def test_unknown_cfg_bits_are_refused_before_any_launch():
 
 # ================================================================== program layer
 def test_dpmpp_step_recorded_replayed_and_graph_launched():
-    """Bit 1 through the whole replay protocol of tests/_replay.py (two direct launches, a recording that launches nothing, eager
-    replay, every run_range split, hipGraph on two streams, time_ops, and new parameter rows in the same device buffers) - used as
-    a library: the case is built here and never enters its registry.  The op keeps the launcher's name."""
+    """The ``dpmpp_steps`` case of the registry in tests/_replay.py (plain, CFG, and ``out`` of op 0 as ``state`` of op 2) through
+    the whole replay protocol (two direct launches, a recording that launches nothing, eager replay, every run_range split,
+    hipGraph on two streams, time_ops, and new parameter rows in the same device buffers), recorded under the launcher's own
+    name - and then this file's own check: the direct launches the protocol compared everything with are the right answer."""
     import _replay as RP
-    from latentblending_amd.hip import lib
-    ops = ops_mod()
-    B, n = 3, 8 * 37
-    c = RP.Case("dpmpp_steps", ["lb_ddim_step_f16"] * 3)
+    c = RP.build_case("dpmpp_steps")
+    assert c.ops == ["lb_dpmpp2m_step_f16"] * 3
+    B, n, x, e, outs = (c.operands[k] for k in ("B", "n", "state", "eps", "outs"))
+    assert (B, n) == (3, 8 * 37) and sorted(outs) == ["dpmpp", "dpmpp_cfg", "dpmpp_chained"]
+    # (recorded on a mixed batch; rewritten to other steps of the schedules: every row second order then)
+    assert RP.DPMPP_PLANS["recorded"] == MIXED and RP.DPMPP_PLANS["rewritten"] == ALL_SECOND
     state, eps = inputs(B, n, seed=15)
-    x, e = c.dev(state), c.dev(eps)
-    params = c.inp(ops.step_params(native_rows(MIXED), DEV))
-    outs = {k: c.guarded(k, 2 * B, n, n, F16, back_rows=2) for k in ("dpmpp", "dpmpp_cfg", "dpmpp_chained")}
-    P = lambda t: t.data_ptr()      # noqa: E731
-
-    def thunk():
-        a, s = lib.api, torch.cuda.current_stream().cuda_stream
-        a.lb_ddim_step_f16(P(x), P(e), P(outs["dpmpp"]), P(params), n, B, 2, s)
-        a.lb_ddim_step_f16(P(x), P(e), P(outs["dpmpp_cfg"]), P(params), n, B, 3, s)
-        a.lb_ddim_step_f16(P(outs["dpmpp"]), P(e), P(outs["dpmpp_chained"]), P(params), n, B, 2, s)      # out of op 0 as x of op 2
-    c.thunk = thunk
-
-    def mutate():       # (other steps of the schedules: every row second order now)
-        params.copy_(ops.step_params(native_rows(ALL_SECOND), DEV))
-    c.mutate = mutate
-    c.freeze()
+    assert torch.equal(bits(x), bits(state)) and torch.equal(bits(e), bits(eps))
     rec = RP.run_protocol(c, RP.GpuDriver())
     print("[dpmpp] " + RP.format_record(rec))
     assert rec["eager"] == rec["graph"] == rec["graph_s2"] == rec["new_values"] == "equal"

@@ -16,7 +16,10 @@ lb_layernorm_f16, lb_groupnorm_nhwc, lb_groupnorm_from_stats, lb_slerp_pairs_f16
 lb_slerp_strided_f16, lb_lerp_f16 / _f32, lb_scale_model_input_f16, lb_euler_step_f16, lb_ddim_step_f16, lb_sinusoid_f16,
 lb_copy_cols_f16, lb_cast_f16_to_f32, lb_cast_f32_to_f16, lb_fill_f32, lb_nchw_to_nhwc_f16, lb_nhwc_to_nchw_f16,
 lb_postprocess_u8, lb_lpips_prep_u8, lb_maxpool3s2_nhwc_f16, lb_lpips_tap, lb_embed_tokens_f16, lb_gather_rows_f16,
-lb_frames_lerp_u8.
+lb_frames_lerp_u8.  The other two sampler steps have their guard-band tests beside their restatements: lb_lcm_step_f16 in
+tests/test_lcm_gpu.py::test_lcm_step_memory_contract (NaN noise behind the last-step rows), lb_dpmpp2m_step_f16 in
+tests/test_dpmpp_gpu.py::test_dpmpp_step_kernel_matches_the_restatement_bit_for_bit (two-plane ``out`` between guard bands, NaN
+history behind the first-order rows).
 """
 import ctypes as C
 import functools
@@ -604,7 +607,8 @@ def test_lerp_memory_contract(n, results_log):
 @pytest.mark.parametrize("n", MIX_N + [8 * 37 + 3])
 def test_scheduler_steps_memory_contract(n, results_log):
     """lb_scale_model_input_f16 (plain and duplicated for CFG), lb_euler_step_f16 (plain, ancestral, CFG combine) and
-    lb_ddim_step_f16 (plain, CFG) on [B, n] latents into guarded outputs: <= 1 fp16 ulp against the oracle schedulers."""
+    lb_ddim_step_f16 (plain, CFG) on [B, n] latents into guarded outputs: <= 1 fp16 ulp against the oracle schedulers.
+    (lb_lcm_step_f16 and lb_dpmpp2m_step_f16: see the module docstring.)"""
     from latentblending_amd.native.scheduler import NativeDDIMScheduler
     o, l = ops(), lib()
     B, g = 2, 3.5

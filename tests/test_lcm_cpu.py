@@ -237,14 +237,21 @@ def test_lcm_null_noise_and_unknown_modes_are_refused_before_any_launch():
         ops.lcm_step(x, x, mixed, noise=None, all_last=True)
     with pytest.raises(ValueError, match="cannot be established"):
         ops.lcm_step(x, x, torch.zeros(2, 8), noise=None)
-    with pytest.raises(RuntimeError, match="needs noise"):
-        lib.api.lb_euler_step_f16(16, 16, None, 16, 16, 8, 1, 0, 2, None)
+    with pytest.raises(RuntimeError, match="lb_lcm_step_f16: .*needs noise"):
+        lib.api.lb_lcm_step_f16(16, 16, None, 16, 16, 8, 1, 0, 0, None)
     with pytest.raises(RuntimeError, match="ancestral step needs noise"):
         lib.api.lb_euler_step_f16(16, 16, None, 16, 16, 8, 1, 0, 1, None)
-    with pytest.raises(RuntimeError, match="mode"):
+    with pytest.raises(RuntimeError, match="lb_euler_step_f16: ancestral is 0 or 1"):
         lib.api.lb_euler_step_f16(16, 16, 16, 16, 16, 8, 1, 0, 3, None)
-    with pytest.raises(RuntimeError, match="cfg bits"):
-        lib.api.lb_euler_step_f16(16, 16, 16, 16, 16, 8, 1, 4, 2, None)
+    for bad in (2, 3, 4):           # (2 was "every row is a last step" when this was a mode of the Euler step: an argument now)
+        with pytest.raises(RuntimeError, match="lb_lcm_step_f16: cfg bits"):
+            lib.api.lb_lcm_step_f16(16, 16, 16, 16, 16, 8, 1, bad, 0, None)
+    # the overloading is gone: what used to select the latent-consistency step is refused, and the message says where it went
+    for noise in (None, 16):
+        with pytest.raises(RuntimeError, match="lb_lcm_step_f16"):
+            lib.api.lb_euler_step_f16(16, 16, noise, 16, 16, 8, 1, 0, 2, None)
+    with pytest.raises(RuntimeError, match="lb_euler_step_f16: cfg is 0 or 1"):
+        lib.api.lb_euler_step_f16(16, 16, 16, 16, 16, 8, 1, 2, 0, None)
 
 
 def test_pipe_names_lcm_among_its_schedulers():

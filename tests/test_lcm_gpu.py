@@ -1,4 +1,4 @@
-"""The few-step path on a real MI355X: the latent-consistency step kernel (mode 2 of lb_euler_step_f16) bit for bit against the
+"""The few-step path on a real MI355X: the latent-consistency step kernel (lb_lcm_step_f16) bit for bit against the
 torch restatement in tests/_lcm_ref.py, its memory contract, recorded / replayed / graph launches, the refusal of a null noise
 pointer, the guidance-embedded UNet against the unchanged oracle, and the whole branched transition under ``scheduler="lcm"``.
 
@@ -170,8 +170,8 @@ def test_lcm_step_memory_contract(per_sample, cfg):
     nd = poisoned(noise, B, per_sample, per_sample, NAN, DEV, extra_rows=4)
     out, chk = guarded(B, per_sample, per_sample, F16, DEV, back_rows=4)
     params = ops.step_params(native_rows(plan), DEV)
-    lib.api.lb_euler_step_f16(xd.data_ptr(), ed.data_ptr(), nd.data_ptr(), out.data_ptr(), params.data_ptr(), per_sample, B,
-                              int(cfg), 2, torch.cuda.current_stream().cuda_stream)
+    lib.api.lb_lcm_step_f16(xd.data_ptr(), ed.data_ptr(), nd.data_ptr(), out.data_ptr(), params.data_ptr(), per_sample, B,
+                            int(cfg), 0, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     chk.assert_intact("lcm out")
     chk.assert_fully_written("lcm out")
@@ -181,32 +181,18 @@ def test_lcm_step_memory_contract(per_sample, cfg):
 
 # ================================================================== program layer
 def test_lcm_step_recorded_replayed_and_graph_launched():
-    """Mode 2 through the whole replay protocol of tests/_replay.py (two direct launches, a recording that launches nothing, eager
-    replay, every run_range split, hipGraph on two streams, time_ops, and new parameter rows in the same device buffers) - used as
-    a library: the case is built here and never enters its registry."""
+    """The ``lcm_steps`` case of the registry in tests/_replay.py (plain, CFG, last-step rows with a null noise pointer) through the
+    whole replay protocol (two direct launches, a recording that launches nothing, eager replay, every run_range split, hipGraph
+    on two streams, time_ops, and new parameter rows in the same device buffers), recorded under the launcher's own name - and
+    then this file's own check: the direct launch the protocol compared everything with is the right answer."""
     import _replay as RP
-    from latentblending_amd.hip import lib
-    ops = ops_mod()
-    B, n = 2, 8 * 37 + 3
-    c = RP.Case("lcm_steps", ["lb_euler_step_f16"] * 3)
-    x, eps, noise = c.dev(rnd(B, n, seed=15, scale=4.0)), c.dev(rnd(2 * B, n, seed=16)), c.dev(rnd(B, n, seed=17))
-    params = c.inp(ops.step_params(native_rows(step_indices(B, "middle")), DEV))
-    params_last = c.inp(ops.step_params(native_rows(step_indices(B, "last")), DEV))
-    outs = {k: c.guarded(k, B, n, n, F16, back_rows=2) for k in ("lcm", "lcm_cfg", "lcm_last_null_noise")}
-    P = lambda t: t.data_ptr()      # noqa: E731
-
-    def thunk():
-        a, s = lib.api, torch.cuda.current_stream().cuda_stream
-        a.lb_euler_step_f16(P(x), P(eps), P(noise), P(outs["lcm"]), P(params), n, B, 0, 2, s)
-        a.lb_euler_step_f16(P(x), P(eps), P(noise), P(outs["lcm_cfg"]), P(params), n, B, 1, 2, s)
-        a.lb_euler_step_f16(P(x), P(eps), None, P(outs["lcm_last_null_noise"]), P(params_last), n, B, 2, 2, s)
-    c.thunk = thunk
-
-    def mutate():       # (another step of each schedule; the null-noise launch keeps last-step rows: bit 1 of cfg was recorded)
-        params.copy_(ops.step_params(native_rows(step_indices(B, "first")), DEV))
-        params_last.copy_(ops.step_params(native_rows([(8, 7, 2.0), (3, 2, 2.0)]), DEV))
-    c.mutate = mutate
-    c.freeze()
+    c = RP.build_case("lcm_steps")
+    assert c.ops == ["lb_lcm_step_f16"] * 3
+    B, n, x, eps, noise, outs = (c.operands[k] for k in ("B", "n", "x", "eps", "noise", "outs"))
+    assert (B, n) == (2, 8 * 37 + 3) and sorted(outs) == ["lcm", "lcm_cfg", "lcm_last_null_noise"]
+    assert RP.LCM_PLANS["recorded"] == step_indices(B, "middle") and RP.LCM_PLANS["recorded_last"] == step_indices(B, "last")
+    # (rewritten to another step of each schedule; the null-noise launch keeps last-step rows: ``all_last`` was recorded)
+    assert RP.LCM_PLANS["rewritten"] == step_indices(B, "first") and RP.LCM_PLANS["rewritten_last"] == [(8, 7, 2.0), (3, 2, 2.0)]
     rec = RP.run_protocol(c, RP.GpuDriver())
     print("[lcm] " + RP.format_record(rec))
     assert rec["eager"] == rec["graph"] == rec["graph_s2"] == rec["new_values"] == "equal"
@@ -218,7 +204,7 @@ def test_lcm_step_recorded_replayed_and_graph_launched():
     assert ulp_diff_f16(outs["lcm"].contiguous(), want) <= 1
 
 
-# ================================================================== refusal, and the old modes
+# ================================================================== refusal, and the Euler step's bits
 def test_lcm_null_noise_with_a_non_last_row_is_refused_before_any_launch():
     from latentblending_amd.hip import lib
     from latentblending_amd.native.runtime import Program
@@ -238,19 +224,21 @@ def test_lcm_null_noise_with_a_non_last_row_is_refused_before_any_launch():
     assert prog.num_ops == 0
     out, chk = guarded(B, n, n, F16, DEV, back_rows=2)
     s = torch.cuda.current_stream().cuda_stream
-    with pytest.raises(RuntimeError, match="needs noise"):
-        lib.api.lb_euler_step_f16(xd.data_ptr(), ed.data_ptr(), None, out.data_ptr(), params.data_ptr(), n, B, 0, 2, s)
+    with pytest.raises(RuntimeError, match="lb_lcm_step_f16: .*needs noise"):
+        lib.api.lb_lcm_step_f16(xd.data_ptr(), ed.data_ptr(), None, out.data_ptr(), params.data_ptr(), n, B, 0, 0, s)
     with pytest.raises(RuntimeError, match="ancestral step needs noise"):
         lib.api.lb_euler_step_f16(xd.data_ptr(), ed.data_ptr(), None, out.data_ptr(), params.data_ptr(), n, B, 0, 1, s)
-    with pytest.raises(RuntimeError, match="mode"):
+    with pytest.raises(RuntimeError, match="lb_euler_step_f16: ancestral is 0 or 1"):
         lib.api.lb_euler_step_f16(xd.data_ptr(), ed.data_ptr(), None, out.data_ptr(), params.data_ptr(), n, B, 0, 3, s)
+    with pytest.raises(RuntimeError, match="lb_lcm_step_f16"):         # what used to select this step on the Euler symbol
+        lib.api.lb_euler_step_f16(xd.data_ptr(), ed.data_ptr(), None, out.data_ptr(), params.data_ptr(), n, B, 0, 2, s)
     torch.cuda.synchronize()
     chk.assert_untouched("out of the refused calls")
 
 
 def test_euler_modes_0_and_1_keep_the_parent_commits_bits():
-    """tests/golden/lcm_euler_modes.json: lb_euler_step_f16 in modes 0 and 1 (vector and scalar form, with and without CFG) as the
-    commit before the mode argument existed computed them on an MI355X, on one fixed input."""
+    """tests/golden/lcm_euler_modes.json: lb_euler_step_f16 plain and ancestral (vector and scalar form, with and without CFG) as the
+    commit before the latent-consistency step existed computed them on an MI355X, on one fixed input."""
     ops = ops_mod()
     with open(os.path.join(GOLD, "lcm_euler_modes.json")) as fh:
         gold = json.load(fh)

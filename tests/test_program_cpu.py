@@ -99,6 +99,8 @@ FAKE_CALLS = {
     "lb_scale_model_input_f16": lambda: api.lb_scale_model_input_f16(P[0], P[1], P[2], 64, 2, 0, None),
     "lb_euler_step_f16": lambda: api.lb_euler_step_f16(P[0], P[1], None, P[2], P[3], 64, 2, 0, 0, None),
     "lb_ddim_step_f16": lambda: api.lb_ddim_step_f16(P[0], P[1], P[2], P[3], 64, 2, 0, None),
+    "lb_lcm_step_f16": lambda: api.lb_lcm_step_f16(P[0], P[1], None, P[2], P[3], 64, 2, 0, 1, None),
+    "lb_dpmpp2m_step_f16": lambda: api.lb_dpmpp2m_step_f16(P[0], P[1], P[2], P[3], 64, 2, 1, None),
     "lb_counter_noise_f16": lambda: api.lb_counter_noise_f16(P[0], P[1], 64, 2, 0, None),
     "lb_gemm_f16": lambda: api.lb_gemm_f16(C.byref(gemm_params()), None),
     "lb_conv3x3_halo_f16": lambda: api.lb_conv3x3_halo_f16(C.byref(conv_params()), None),

@@ -1,5 +1,6 @@
 """rocprofv3 kernel durations of the three sampler step kernels on the same >= 1 GiB batch: the latent-consistency step
-(mode 2 of lb_euler_step_f16), the DDIM step and the Euler-ancestral step.
+(lb_lcm_step_f16), the DDIM step and the Euler-ancestral step - three instantiations of sampler_step_kernel (csrc/mix.hip),
+told apart by the policy name in the kernel symbol.
 
   rocprofv3 --kernel-trace --stats --output-format csv -d lcm_rocprof_out -- python tools/lcm_rocprof.py run lcm_rocprof_out
   python tools/lcm_rocprof.py fold lcm_rocprof_out lcm_rocprof_out/summary.json
@@ -38,13 +39,13 @@ def run(out_dir):
     st = torch.cuda.current_stream().cuda_stream
     P = lambda t: t.data_ptr()      # noqa: E731
     for _ in range(ITER):
-        api.lb_euler_step_f16(P(x), P(eps), P(noise), P(out), P(p_lcm), n, pairs, 0, 2, st)
+        api.lb_lcm_step_f16(P(x), P(eps), P(noise), P(out), P(p_lcm), n, pairs, 0, 0, st)
         api.lb_ddim_step_f16(P(x), P(eps), P(out), P(p_ddim), n, pairs, 0, st)
         api.lb_euler_step_f16(P(x), P(eps), P(noise), P(out), P(p_anc), n, pairs, 0, 1, st)
     torch.cuda.synchronize()
     os.makedirs(out_dir, exist_ok=True)
     json.dump({"pairs": pairs, "elements_per_pair": n, "iters": ITER,
-               "bytes": {"lcm_step_kernel": pairs * n * 8, "ddim_step_kernel": pairs * n * 6, "euler_step_kernel": pairs * n * 8}},
+               "bytes": {"LcmStep": pairs * n * 8, "DdimStep": pairs * n * 6, "EulerStep": pairs * n * 8}},      # (policy names)
               open(os.path.join(out_dir, META_NAME), "w"))
 
 

@@ -40,7 +40,7 @@ def run():
         api.lb_euler_step_f16(p0.data_ptr(), p1.data_ptr(), out.data_ptr(), out.data_ptr(), params.data_ptr(), n, pairs, 0, 1, st)
     torch.cuda.synchronize()
     meta = {"pairs": pairs, "elements_per_pair": n, "iters": ITER,
-            "bytes": {"slerp_strided_kernel": pairs * n * 6, "scale_input_kernel": pairs * n * 4, "euler_step_kernel": pairs * n * 8}}
+            "bytes": {"slerp_strided_kernel": pairs * n * 6, "ScaleInput": pairs * n * 4, "EulerStep": pairs * n * 8}}      # (sampler_step_kernel<policy>)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     json.dump(meta, open(os.path.join(ROOT, "gpurun_out", "mixing_rocprof_meta.json"), "w"))
 

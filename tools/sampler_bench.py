@@ -1,8 +1,8 @@
 """What the second-order sampler costs and buys on one MI355X (the figures of profiles/dpmpp.txt).
 
   python tools/sampler_bench.py --part kernel
-      the DPM-Solver++ 2M step kernel (bit 1 of ``cfg`` of lb_ddim_step_f16) on a 1 GiB batch of latents, timed beside the plain
-      DDIM step and the latent-consistency step (mode 2 of lb_euler_step_f16) in the same process: us per launch and GB/s over
+      the DPM-Solver++ 2M step kernel (lb_dpmpp2m_step_f16) on a 1 GiB batch of latents, timed beside the plain DDIM step
+      (lb_ddim_step_f16) and the latent-consistency step (lb_lcm_step_f16) in the same process: us per launch and GB/s over
       the algorithmic bytes (HIP events around ``--iters`` back-to-back launches, after a warm-up).
   python tools/sampler_bench.py --part transition --samplers euler:30,dpmpp_2m_karras:20
       one base-SDXL transition at full width (synthetic weights, 1024^2, guidance 4.0 with CFG, depth_strength 0.5, 15 branches:
@@ -61,12 +61,12 @@ def kernel_part(args) -> None:
     api = ops.api
     P = lambda t: t.data_ptr()      # noqa: E731
     cases = [
-        ("lb_ddim_step_f16 cfg 2: DPM-Solver++ 2M, second-order rows", 10, lambda: api.lb_ddim_step_f16(P(state), P(eps), P(out2), P(rows["dpm2"]), per_sample, B, 2, s)),
-        ("lb_ddim_step_f16 cfg 2: DPM-Solver++ 2M, first-order rows", 8, lambda: api.lb_ddim_step_f16(P(state), P(eps), P(out2), P(rows["dpm1"]), per_sample, B, 2, s)),
-        ("lb_ddim_step_f16 cfg 3: DPM-Solver++ 2M, second-order rows, CFG", 12, lambda: api.lb_ddim_step_f16(P(state), P(eps), P(out2), P(rows["dpm2"]), per_sample, B, 3, s)),
+        ("lb_dpmpp2m_step_f16 cfg 0: second-order rows", 10, lambda: api.lb_dpmpp2m_step_f16(P(state), P(eps), P(out2), P(rows["dpm2"]), per_sample, B, 0, s)),
+        ("lb_dpmpp2m_step_f16 cfg 0: first-order rows", 8, lambda: api.lb_dpmpp2m_step_f16(P(state), P(eps), P(out2), P(rows["dpm1"]), per_sample, B, 0, s)),
+        ("lb_dpmpp2m_step_f16 cfg 1: second-order rows, CFG", 12, lambda: api.lb_dpmpp2m_step_f16(P(state), P(eps), P(out2), P(rows["dpm2"]), per_sample, B, 1, s)),
         ("lb_ddim_step_f16 cfg 0: DDIM", 6, lambda: api.lb_ddim_step_f16(P(x), P(eps), P(out1), P(rows["ddim"]), per_sample, B, 0, s)),
         ("lb_ddim_step_f16 cfg 1: DDIM, CFG", 8, lambda: api.lb_ddim_step_f16(P(x), P(eps), P(out1), P(rows["ddim"]), per_sample, B, 1, s)),
-        ("lb_euler_step_f16 mode 2: latent-consistency step", 8, lambda: api.lb_euler_step_f16(P(x), P(eps), P(noise), P(out1), P(rows["lcm"]), per_sample, B, 0, 2, s)),
+        ("lb_lcm_step_f16 cfg 0: latent-consistency step", 8, lambda: api.lb_lcm_step_f16(P(x), P(eps), P(noise), P(out1), P(rows["lcm"]), per_sample, B, 0, 0, s)),
     ]
     for rnd in range(args.rounds):
         for name, bytes_per_element, fn in cases:
