@@ -206,6 +206,16 @@ typedef struct LbGemmParams {
                               * the launcher refuses any other value (the kernel's layout and the buffer cannot drift apart) */
     const float* gn_table;   /* LB_GEMM_GN_A: [B][Cin] float2 (scale, shift), else unused */
     int gn_silu;             /* LB_GEMM_GN_A: SiLU after the affine map */
+    int wrap;                /* wrap-around ("circular") padding of a "same" conv: bit 0 = the columns wrap (left and right edges
+                              * join), bit 1 = the rows wrap (top and bottom edges join).  On a wrapped axis a tap outside the
+                              * effective input grid (the nearest-2^ups upsampled input; the low-res grid of a sub-pixel conv)
+                              * reads coordinate c mod size of the SAME row / column of the SAME sample; on the other axis it
+                              * reads zero, as ever.  Defined for 3x3 / pad 1 / stride 1, 3x3 / pad 1 / stride 2 with an even
+                              * side on every wrapped axis, ups 0 or 1, and the 2x2 sub-pixel forms (scatter 1 and 2); every
+                              * launcher and plan call refuses any other conv (and a plain GEMM) with wrap != 0, and bits above
+                              * bit 1.  All conv kernels implement it (gemm.hip, gemm_glds.hip, conv3_halo.hip in every form,
+                              * conv3_narrow.hip, conv3_c64.hip): the route of a conv does not depend on it.  0 = the kernels of
+                              * ever (the wrapped forms are separate instantiations). */
 } LbGemmParams;
 
 int lb_gemm_f16(const LbGemmParams* params, void* stream);

@@ -11,7 +11,7 @@ void lb_set_error(const char* what, hipError_t e) {
 
 extern "C" const char* lb_last_error_string(void) { return g_err; }
 
-extern "C" int lb_version(void) { return 10001; }   // major*10000 + minor*100 + patch
+extern "C" int lb_version(void) { return 10100; }   // major*10000 + minor*100 + patch
 
 // Device facts the host layer wants without importing a second runtime.
 extern "C" int lb_device_info(int device, int* cu_count, long* lds_per_cu, char* arch, int arch_len) {

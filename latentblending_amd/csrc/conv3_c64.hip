@@ -43,6 +43,13 @@ __device__ __forceinline__ void c64_glds16(const void* gsrc, const f16* lds_ptr)
 #define C64_WTS (9 * 64 * 64)                     // halves of the resident weights: nine [64][64] tap tiles
 #define C64_SMEM ((C64_WTS + 2 * C64_HALO) * 2)   // bytes
 
+//
+// WRP (LbGemmParams.wrap != 0): wrap-around padding.  The loader decides per halo pixel where it comes from; on a wrapped axis a
+// coordinate of the OUTPUT grid (the upsampled one when ups = 1) outside it is taken modulo its side before the range test and before
+// the shift to the stored pixel, so it is a real pixel of the same row / column of the same sample; the other axis, and the overhang of
+// a ragged edge tile beyond the first wrapped pixel, keep the zero page or read a pixel that is never stored.  WRP = false is the
+// shipped code, instruction for instruction.
+template <bool WRP>
 __global__ void __launch_bounds__(512) conv3x3_c64_kernel(const LbGemmParams p) {
     extern __shared__ __attribute__((aligned(16))) f16 lds[];
     f16* const wlds = lds;
@@ -88,7 +95,11 @@ __global__ void __launch_bounds__(512) conv3x3_c64_kernel(const LbGemmParams p) 
             if (gidx < C64_HRG) {
                 const int row = gidx * 8 + r8;
                 const int hy = row / C64_HW, hx = row - hy * C64_HW;
-                const int y = t.y0 + hy - 1, x = t.x0 + hx - 1;                 // on the output grid
+                int y = t.y0 + hy - 1, x = t.x0 + hx - 1;                       // on the output grid
+                if constexpr (WRP) {
+                    if (p.wrap & 2) y = lb_wrap_coord(y, p.Hout);
+                    if (p.wrap & 1) x = lb_wrap_coord(x, p.Wout);
+                }
                 const bool ok = row < C64_HR && y >= 0 && y < p.Hout && x >= 0 && x < p.Wout;
                 // (branch-free: the address of a masked pixel is computed from clamped coordinates and then replaced)
                 const int ys = (ok ? y : t.y0) >> p.ups, xs = (ok ? x : t.x0) >> p.ups;
@@ -227,6 +238,7 @@ int lb_conv3_c64_check(const LbGemmParams& p) {
     LB_REQUIRE(p.conv == 1 && p.KH == 3 && p.KW == 3, "LB_GEMM_C64: needs a convolution (conv = 1) with KH = KW = 3");
     LB_REQUIRE(p.stride == 1, "LB_GEMM_C64: stride must be 1");
     LB_REQUIRE(p.pad == 1, "LB_GEMM_C64: pad must be 1");
+    LB_REQUIRE(lb_wrap_defined(p), "LB_GEMM_C64: " LB_WRAP_REFUSAL);
     LB_REQUIRE(p.scatter == 0, "LB_GEMM_C64: scatter must be 0 (no sub-pixel form)");
     LB_REQUIRE(p.Cin == 64, "LB_GEMM_C64: Cin must be 64");
     LB_REQUIRE(p.N == 64, "LB_GEMM_C64: N must be 64");
@@ -257,10 +269,13 @@ int lb_conv3_c64_launch(LbGemmParams p, hipStream_t stream) {      // (trusts it
     if (p.alpha == 0.f) p.alpha = 1.f;
     p.splitk = 1;
     static unsigned long long seen = 0;
-    LB_ONCE_PER_DEVICE(seen)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C64_SMEM);
+    LB_ONCE_PER_DEVICE(seen) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, C64_SMEM);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_c64_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, C64_SMEM);
+    }
     long items, grid;
     lb_conv3_c64_grid(p, items, grid);
-    hipLaunchKernelGGL(conv3x3_c64_kernel, dim3((unsigned)grid), dim3(512), C64_SMEM, stream, p);
+    if (p.wrap) hipLaunchKernelGGL(conv3x3_c64_kernel<true>, dim3((unsigned)grid), dim3(512), C64_SMEM, stream, p);
+    else hipLaunchKernelGGL(conv3x3_c64_kernel<false>, dim3((unsigned)grid), dim3(512), C64_SMEM, stream, p);
     return lb_check_launch("lb_gemm_f16(LB_GEMM_C64)");
 }

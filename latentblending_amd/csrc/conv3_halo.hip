@@ -118,7 +118,16 @@ template <int KS, int NR, int TAP> constexpr int halo_full_rounds_in_tap() {   /
 // (halo_gna_loads_in_tap), nothing else moves.  GNA = false is the shipped code, instruction for instruction.
 template <bool GNA, int TAP> constexpr int halo_gna_loads_in_tap() { return GNA && TAP == 0 ? 1 : 0; }
 
-template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false>
+//
+// WRP (LbGemmParams.wrap != 0, every form): wrap-around padding.  The only thing that changes is where a halo pixel comes from, and that
+// is decided in ONE place, once per tile: set_halo_offsets.  On a wrapped axis a halo coordinate outside the image is taken modulo the
+// image side (a halo reaches one pixel past the tile, so one conditional add) - the pixel of the SAME row / column of the SAME sample,
+// not the element-offset neighbour - and is then a real pixel like any other: h_off[j] >= 0, so under GNA it is mapped in LDS, and only
+// the true zero padding of the other axis stays untouched.  Under RAG the halo column just past the image's last column is column 0
+// (rows alike); pixels further into an overhang read whatever the modulo gives (a real pixel or the zero page) and are never stored.
+// For KS == 2 the wrap acts on the low-res grid.  Step loop, wait counts and epilogues do not move.
+// WRP = false is the shipped code, instruction for instruction.
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false, bool WRP = false>
 __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p) {
     static_assert(!RAG || KS == 3, "ragged tiles exist for the 3x3 form only");
     static_assert(!KSP || (KS == 3 && !RAG), "the K-split form exists for the whole-tile 3x3 form only");
@@ -205,7 +214,11 @@ __global__ void __launch_bounds__(512) conv3x3_halo_kernel(const LbGemmParams p)
             const int gidx = j * 8 + wave;
             const int row = gidx * 8 + r8;
             const int hy = row / HWP, hx = row - hy * HWP;
-            const int y = t.y0 + hy - org_y, x = t.x0 + hx - org_x;
+            int y = t.y0 + hy - org_y, x = t.x0 + hx - org_x;
+            if constexpr (WRP) {                        // (block-uniform switches; the range test below still holds for the other axis)
+                if (p.wrap & 2) y = lb_wrap_coord(y, p.Hin);
+                if (p.wrap & 1) x = lb_wrap_coord(x, p.Win);
+            }
             const bool ok = exists && (j < NR - 1 || wave < EXTRA) && row < HR && y >= 0 && y < p.Hin && x >= 0 && x < p.Win;
             h_off[j] = ok ? ((long)(t.b * p.Hin + y) * p.Win + x) * p.ldx + cl * 8 : -1;
         }
@@ -636,8 +649,10 @@ static int g_halo_gn_a_mode = 1, g_halo_gn_a_grid = 0;     // (lb_conv_halo_set_
 
 // `nblk` work items on `grid` blocks: halo_grid's answer (lb_upconv_halo_launch), or the LbHaloPlan's (lb_conv3x3_halo_launch: the K-split form
 // walks an even share of the units on ks_grid blocks)
-template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false>
+template <int BN, int TW, int KS = 3, bool RAG = false, bool KSP = false, bool GNA = false, bool WRP = false>
 static int launch_halo(const LbGemmParams& p, hipStream_t stream, long nblk, long grid) {
+    if constexpr (!WRP)                                 // (the one place a wrapped launch turns to its own instantiation)
+        if (p.wrap) return launch_halo<BN, TW, KS, RAG, KSP, GNA, true>(p, stream, nblk, grid);
     constexpr int TH = 256 / TW;
     constexpr int HRP = (((TH + KS - 1) * (TW + KS - 1) + 7) / 8) * 8;
     // (KSP: the "last arriver" word; GNA: 1 KiB of table per wave)
@@ -647,7 +662,7 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream, long nblk, lon
     // (a recording does not come here: the first call on a device happens at the first replay - inside the stream capture of
     //  lb_program_instantiate when a program is instantiated before any eager run)
     LB_ONCE_PER_DEVICE(seen)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA, WRP>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
     static_assert(BN == 128, "halo_grid assumes 128-channel blocks");
     // (nblk < 2^30: lb_conv3x3_halo_check / lb_upconv_halo_check)
@@ -661,13 +676,14 @@ static int launch_halo(const LbGemmParams& p, hipStream_t stream, long nblk, lon
 #ifdef LB_STUDY_BUILD
     pk.reserved_ = g_halo_study;
 #endif
-    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
+    hipLaunchKernelGGL((conv3x3_halo_kernel<BN, TW, KS, RAG, KSP, GNA, WRP>), dim3((unsigned)grid), dim3(512), SMEM, stream, pk);
     return lb_check_launch(KS == 2 ? "lb_upconv2x_halo_f16" : "lb_conv3x3_halo_f16");
 }
 
 // Sub-pixel upsampler (scatter == 2): 0 = not eligible, else the tile width
 int lb_upconv_halo_eligible(const LbGemmParams& p) {
     if (!p.conv || p.scatter != 2 || p.KH != 2 || p.KW != 2 || p.stride != 1 || p.ups) return 0;
+    if (!lb_wrap_defined(p)) return 0;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.Cin % 64 != 0 || p.K != 4 * p.Cin) return 0;
     if (p.zero_page == nullptr || (p.flags & (LB_GEMM_GEGLU | LB_GEMM_TRANS_OUT)) || p.N % 4 != 0 || p.residual != nullptr) return 0;
     if (p.M % (p.Hin * p.Win) != 0) return 0;
@@ -705,6 +721,7 @@ extern "C" int lb_upconv2x_halo_f16(const LbGemmParams* pp, void* stream) {
     p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_upconv2x_halo_f16: empty problem");
+    LB_REQUIRE(lb_wrap_defined(p), "lb_upconv2x_halo_f16: " LB_WRAP_REFUSAL);
     LB_REQUIRE(lb_upconv_halo_eligible(p) != 0,
                "lb_upconv2x_halo_f16: needs scatter = 2, KH = KW = 2, stride 1, Cin % 64 == 0, W % 16 == 0, zero page, no residual");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && p.ldc % 4 == 0, "lb_upconv2x_halo_f16: ldw / ldx multiples of 8, ldc multiple of 4");
@@ -716,6 +733,7 @@ extern "C" int lb_upconv2x_halo_f16(const LbGemmParams* pp, void* stream) {
 int lb_conv3x3_halo_eligible(const LbGemmParams& p) {
     if (!p.conv || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.ups || p.scatter) return 0;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.Cin % 64 != 0 || p.K != 9 * p.Cin) return 0;
+    if (!lb_wrap_defined(p)) return 0;
     if (p.zero_page == nullptr || (p.flags & LB_GEMM_GEGLU) || p.N % 4 != 0) return 0;
     if (p.M % (p.Hin * p.Win) != 0) return 0;
     if ((long)p.N * p.ldw * 2 >= (1l << 32)) return 0;         // (32-bit byte offsets into the weight matrix: LB_HALO_LEAN_ADDR)
@@ -860,6 +878,7 @@ extern "C" int lb_conv3x3_halo_f16(const LbGemmParams* pp, void* stream) {
     p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     p.reserved2_ = (g_lb_wide_store & 1) | (g_lb_lean_epilogue ? 2 : 0);
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_conv3x3_halo_f16: empty problem");
+    LB_REQUIRE(lb_wrap_defined(p), "lb_conv3x3_halo_f16: " LB_WRAP_REFUSAL);
     LB_REQUIRE(lb_conv3x3_halo_eligible(p) != 0,
                "lb_conv3x3_halo_f16: needs a 3x3 / stride 1 / pad 1 conv, Cin % 64 == 0, W % 16 == 0 (or LB_GEMM_HALO_RAGGED), zero page");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && (p.ldc % 4 == 0 || (p.flags & LB_GEMM_TRANS_OUT)),

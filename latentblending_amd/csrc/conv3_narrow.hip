@@ -34,7 +34,11 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // lane's 8 pairs of the chunk (its channels are fixed by cl) arrive by ordinary loads behind the same vmcnt(0), and between that
 // wait and the barrier every lane maps, in place, the pieces it requested itself; pieces from the zero page stay zero.
 // GNA = false is the shipped code, instruction for instruction.
-template <bool GNA>
+//
+// WRP (LbGemmParams.wrap != 0): wrap-around padding - on a wrapped axis a halo coordinate outside the image is taken modulo the image
+// side where h_off is set (once per block), so the piece is a real pixel of the same row / column of the same sample (mapped under GNA
+// like any other); the other axis keeps its zero padding.  WRP = false is the shipped code, instruction for instruction.
+template <bool GNA, bool WRP>
 __global__ void __launch_bounds__(256, 2) conv3x3_narrow_kernel(const LbGemmParams p) {
     __shared__ __attribute__((aligned(16))) f16 halo[NARROW_LDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -58,7 +62,11 @@ __global__ void __launch_bounds__(256, 2) conv3x3_narrow_kernel(const LbGemmPara
         const int gidx = j * 4 + wave;
         const int row = gidx * 8 + r8;
         const int hy = row / NARROW_HW, hx = row - hy * NARROW_HW;
-        const int y = y0 + hy - 1, x = x0 + hx - 1;
+        int y = y0 + hy - 1, x = x0 + hx - 1;
+        if constexpr (WRP) {
+            if (p.wrap & 2) y = lb_wrap_coord(y, p.Hin);
+            if (p.wrap & 1) x = lb_wrap_coord(x, p.Win);
+        }
         const bool ok = gidx < NARROW_HRG && row < NARROW_HR && y >= 0 && y < p.Hin && x >= 0 && x < p.Win;
         h_off[j] = ok ? (int)((((long)(b * p.Hin + y) * p.Win + x) * p.ldx >> 3) + cl) : -1;
     }
@@ -149,7 +157,7 @@ __global__ void __launch_bounds__(256, 2) conv3x3_narrow_kernel(const LbGemmPara
 int lb_conv3x3_narrow_eligible(const LbGemmParams& p) {
     if (!p.conv || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.ups || p.scatter) return 0;
     if (p.Hout != p.Hin || p.Wout != p.Win || p.Cin % 64 != 0 || p.K != 9 * p.Cin) return 0;
-    if (p.N > 16 || p.N % 4 != 0 || p.zero_page == nullptr) return 0;
+    if (p.N > 16 || p.N % 4 != 0 || p.zero_page == nullptr || !lb_wrap_defined(p)) return 0;
     // plain bias epilogue only (LB_GEMM_HALO_KSPLIT asks nothing of the epilogue: a hint for the halo kernel, which must not change
     // the route of a conv that kernel does not get - `partial` is never read here)
     if (p.flags & ~(LB_GEMM_OUT_F32 | LB_GEMM_HALO_KSPLIT | LB_GEMM_GN_A)) return 0;
@@ -174,8 +182,12 @@ int lb_conv3x3_narrow_check(const LbGemmParams& p) {
 int lb_conv3x3_narrow_launch(LbGemmParams p, hipStream_t stream) {     // (trusts its caller: lb_conv3x3_narrow_check passed)
     if (p.alpha == 0.f) p.alpha = 1.f;
     const long tiles = narrow_tiles(p);
-    if (p.flags & LB_GEMM_GN_A) hipLaunchKernelGGL(conv3x3_narrow_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(conv3x3_narrow_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    const bool gna = (p.flags & LB_GEMM_GN_A) != 0;
+    if (p.wrap) {
+        if (gna) hipLaunchKernelGGL((conv3x3_narrow_kernel<true, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((conv3x3_narrow_kernel<false, true>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    } else if (gna) hipLaunchKernelGGL((conv3x3_narrow_kernel<true, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((conv3x3_narrow_kernel<false, false>), dim3((unsigned)tiles), dim3(256), 0, stream, p);
     return lb_check_launch("lb_conv3x3_narrow_f16");
 }
 
@@ -183,6 +195,7 @@ extern "C" int lb_conv3x3_narrow_f16(const LbGemmParams* pp, void* stream) {
     LbGemmParams p = *pp;
     p.flags &= ~LB_GEMM_C64;                        // (a routing bit of lb_gemm_f16: ignored here)
     LB_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "lb_conv3x3_narrow_f16: empty problem");
+    LB_REQUIRE(lb_wrap_defined(p), "lb_conv3x3_narrow_f16: " LB_WRAP_REFUSAL);
     LB_REQUIRE(lb_conv3x3_narrow_eligible(p) != 0,
                "lb_conv3x3_narrow_f16: needs a 3x3 / stride 1 / pad 1 conv, N <= 16, Cin % 64 == 0, H and W multiples of 16, bias-only epilogue");
     LB_REQUIRE(p.ldw % 8 == 0 && p.ldx % 8 == 0 && p.ldc % 4 == 0, "lb_conv3x3_narrow_f16: ldw / ldx multiples of 8, ldc multiple of 4");

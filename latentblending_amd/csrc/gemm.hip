@@ -34,8 +34,12 @@
 
 template <int N> struct Int { static constexpr int value = N; };
 
-template <int BM, int BN, bool CONV, bool GEGLU, int D>
+// WRP (CONV only; LbGemmParams.wrap != 0): wrap-around padding in the gather - on a wrapped axis a tap coordinate outside the effective
+// input grid is taken modulo its side before the bounds test and the source address, so the request reads the pixel of the same row /
+// column of the same sample; the other axis keeps its zeros.  WRP = false is the gather of ever (a separate instantiation).
+template <int BM, int BN, bool CONV, bool GEGLU, int D, bool WRP = false>
 __global__ void __launch_bounds__(256) gemm_f16_kernel(const LbGemmParams p) {
+    static_assert(!WRP || CONV, "wrap-around padding: convolutions only");
     constexpr int AI = BM * 8 / 256;        // 16-B chunks of A per thread per K-tile
     constexpr int WI = BN * 8 / 256;
     constexpr int TM = BM / 32;             // 16-row fragments per wave along M
@@ -132,6 +136,7 @@ __global__ void __launch_bounds__(256) gemm_f16_kernel(const LbGemmParams p) {
     unsigned valid[D];                      // bit i: A chunk i real, bit 8+i: W chunk i real
     const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
     const int hin_eff = p.Hin << p.ups, win_eff = p.Win << p.ups;
+    const int wrap_y = WRP && (p.wrap & 2) ? hin_eff : 0, wrap_x = WRP && (p.wrap & 1) ? win_eff : 0;     // (block-uniform) period of a wrapped axis, else 0
 
     // Branch-free tile request into ring slot S (addresses of masked chunks fall back to offset 0
     // of the same operand, which is always mapped); advances this thread's k state by one K-tile.
@@ -143,7 +148,11 @@ __global__ void __launch_bounds__(256) gemm_f16_kernel(const LbGemmParams p) {
 #pragma unroll
         for (int i = 0; i < AI; ++i) {
             if (CONV) {
-                const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
+                int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
+                if constexpr (WRP) {
+                    iy += (iy < 0 ? wrap_y : 0) - (iy >= hin_eff ? wrap_y : 0);
+                    ix += (ix < 0 ? wrap_x : 0) - (ix >= win_eff ? wrap_x : 0);
+                }
                 const bool ok = a_ok[i] && k_ok && iy >= 0 && iy < hin_eff && ix >= 0 && ix < win_eff;
                 const long off = ok ? a_off[i] + ((long)(iy >> p.ups) * p.Win + (ix >> p.ups)) * p.ldx + ci : 0;
                 a_reg[S][i] = *reinterpret_cast<const f16x8*>(p.A + off);
@@ -303,7 +312,9 @@ __global__ void gemm_splitk_reduce_kernel(const LbGemmParams p) {
 template <int BM, int BN, int D>
 static void launch_variant(const LbGemmParams& p, dim3 grid, hipStream_t stream) {
     const bool geglu = (p.flags & LB_GEMM_GEGLU) != 0;
-    if (p.conv) {
+    if (p.conv && p.wrap) {
+        hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, true, false, D, true>), grid, dim3(256), 0, stream, p);
+    } else if (p.conv) {
         hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, true, false, D>), grid, dim3(256), 0, stream, p);
     } else if (geglu) {
         hipLaunchKernelGGL((gemm_f16_kernel<BM, BN, false, true, D>), grid, dim3(256), 0, stream, p);
@@ -567,6 +578,9 @@ int lb_conv_halo_gn_a_mode();
 extern "C" void lb_conv_halo_plan(const LbGemmParams* pp, int* kind, int* tile_w, long* items, long* grid);
 static int conv_plan(const LbGemmParams& p, LbConvPlan& o) {
     o = LbConvPlan{};
+    // (wrap-around padding: every conv kernel implements it, so the ladder below does not read `wrap` - a wrapped conv keeps the route,
+    //  tile and split of its zero-padded twin - and a geometry wrap is not defined for has no plan at all, on any route)
+    LB_REQUIRE(lb_wrap_defined(p), "lb_conv_plan / lb_gemm_plan: " LB_WRAP_REFUSAL);
     LbHaloPlan h;
     int rc = 0;
     switch (o.route = gemm_route(p, h)) {       // tile codes 12 / 8 / 6 name the kernels outside this file, blocks = their grids' work
@@ -646,6 +660,7 @@ extern "C" int lb_gemm_f16(const LbGemmParams* pp, void* stream) {
     // (every epilogue stores the transposed form as fp16 - lb_gemm_write4, lb_gemm_store4 - while a caller of the pair sizes an fp32 buffer)
     LB_REQUIRE(!((p.flags & LB_GEMM_TRANS_OUT) && (p.flags & LB_GEMM_OUT_F32)),
                "lb_gemm_f16: LB_GEMM_TRANS_OUT | LB_GEMM_OUT_F32 is not implemented: the transposed store is fp16 only");
+    LB_REQUIRE(lb_wrap_defined(p), "lb_gemm_f16: " LB_WRAP_REFUSAL);
     if (p.conv) {
         LB_REQUIRE(p.Cin % 8 == 0 && p.ldx % 8 == 0, "lb_gemm_f16: conv Cin/ldx must be multiples of 8");
         LB_REQUIRE(p.K == p.KH * p.KW * p.Cin, "lb_gemm_f16: conv K != KH*KW*Cin");

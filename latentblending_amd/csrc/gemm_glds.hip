@@ -70,9 +70,13 @@ __device__ __forceinline__ void ln_accumulate(const f16x8 (&af)[TM], float (&sum
 // dependent chain - wait, barrier, fragment reads, 8 MFMAs, four requests - ~950 cycles for 128 cycles of matrix work, and nothing else
 // is resident to fill the gaps; a second wave per SIMD working on the other half of K doubles what is in flight per CU without
 // another launch, another slab round trip or more blocks.  Not bit-identical to KG = 1 (two partial sums per output instead of one chain).
-template <int BM, int BN, bool CONV, bool GEGLU, int S, int WMW, int LNA = 0, int KG = 1>
+// WRP (CONV only; LbGemmParams.wrap != 0): wrap-around padding in the gather, as in gemm.hip - on a wrapped axis a tap coordinate outside
+// the effective input grid is taken modulo its side before the bounds test and the source address; the other axis keeps the zero page.
+// WRP = false is the gather of ever (a separate instantiation).
+template <int BM, int BN, bool CONV, bool GEGLU, int S, int WMW, int LNA = 0, int KG = 1, bool WRP = false>
 __global__ void __launch_bounds__(WMW * 128 * KG) gemm_f16_glds_kernel(const LbGemmParams p) {
     static_assert(KG == 1 || !CONV, "K-groups: plain / GEGLU GEMMs only");
+    static_assert(!WRP || CONV, "wrap-around padding: convolutions only");
     constexpr int NT = WMW * 128;           // threads per K-group (= per block when KG == 1)
     constexpr int RPI = NT / 8;             // tile rows covered by one round of wave instructions
     constexpr int AI = BM * 8 / NT;         // wave instructions (16-B chunks per thread) of A per K-tile
@@ -167,6 +171,7 @@ __global__ void __launch_bounds__(WMW * 128 * KG) gemm_f16_glds_kernel(const LbG
     }
     const lb_half* zero = reinterpret_cast<const lb_half*>(p.zero_page);
     const int hin_eff = p.Hin << p.ups, win_eff = p.Win << p.ups;
+    const int wrap_y = WRP && (p.wrap & 2) ? hin_eff : 0, wrap_x = WRP && (p.wrap & 1) ? win_eff : 0;     // (block-uniform) period of a wrapped axis, else 0
 
     // ---- round 6: LEAN requests for plain / GEGLU GEMMs whose K is a whole number of K-tiles (every Linear of the UNet / CLIP programs) ----
     // A request used to cost a 64-bit address, two selects against the zero page and a VALU chain for M0: 75 instructions around the 8 MFMAs
@@ -228,7 +233,11 @@ __global__ void __launch_bounds__(WMW * 128 * KG) gemm_f16_glds_kernel(const LbG
         if (idx < AI) {
             const int i = idx;
             if (CONV) {
-                const int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
+                int iy = a_iy[i] + ky, ix = a_ix[i] + kx;
+                if constexpr (WRP) {
+                    iy += (iy < 0 ? wrap_y : 0) - (iy >= hin_eff ? wrap_y : 0);
+                    ix += (ix < 0 ? wrap_x : 0) - (ix >= win_eff ? wrap_x : 0);
+                }
                 const bool ok = a_ok[i] && k_ok && iy >= 0 && iy < hin_eff && ix >= 0 && ix < win_eff;
                 src = ok ? p.A + a_off[i] + ((long)(iy >> p.ups) * p.Win + (ix >> p.ups)) * p.ldx + ci : zero;
             } else {
@@ -502,7 +511,8 @@ static int launch_glds_variant(const LbGemmParams& p, dim3 grid, hipStream_t str
     const bool geglu = (p.flags & LB_GEMM_GEGLU) != 0;
     const dim3 block(WMW * 128);
     const bool lna = (p.flags & LB_GEMM_LN_A) != 0;
-    if (p.conv) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, true, false, S, WMW>), grid, block, smem, stream, p);
+    if (p.conv && p.wrap) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, true, false, S, WMW, 0, 1, true>), grid, block, smem, stream, p);
+    else if (p.conv) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, true, false, S, WMW>), grid, block, smem, stream, p);
     else if (geglu && lna) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, false, true, S, WMW, 1>), grid, block, smem, stream, p);
     else if (geglu) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, false, true, S, WMW>), grid, block, smem, stream, p);
     else if (lna) hipLaunchKernelGGL((gemm_f16_glds_kernel<BM, BN, false, false, S, WMW, 1>), grid, block, smem, stream, p);
@@ -515,6 +525,8 @@ template <int BM, int BN, int S, int WMW = 2>
 static void allow_lds() {
     const int smem = S * glds_stage_rows<BM, BN, WMW>() * BK * (int)sizeof(f16);
     hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_glds_kernel<BM, BN, true, false, S, WMW>),
+                        hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_glds_kernel<BM, BN, true, false, S, WMW, 0, 1, true>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f16_glds_kernel<BM, BN, false, true, S, WMW>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, smem);

@@ -5,6 +5,22 @@
 
 typedef _Float16 lb_h2x __attribute__((ext_vector_type(2)));
 
+// LbGemmParams.wrap (include/lb_hip.h): the geometries wrap-around padding is defined for - "same" convs only.  Every launcher and plan
+// call asks this before anything else reads `wrap`; the kernels' wrapped forms trust it (a tap is at most one period outside the grid).
+static inline bool lb_wrap_defined(const LbGemmParams& p) {
+    if (p.wrap == 0) return true;
+    if ((p.wrap & ~3) || !p.conv || p.ups < 0 || p.ups > 1 || p.Hin <= 0 || p.Win <= 0) return false;
+    if (p.scatter)              // sub-pixel 2x2 forms: the wrap acts on the low-res grid
+        return (p.scatter == 1 || p.scatter == 2) && p.KH == 2 && p.KW == 2 && p.stride == 1 && p.ups == 0 && p.Hout == p.Hin && p.Wout == p.Win;
+    if (p.KH != 3 || p.KW != 3 || p.pad != 1 || (p.stride != 1 && p.stride != 2)) return false;
+    const int he = p.Hin << p.ups, we = p.Win << p.ups;
+    if (p.stride == 2 && (((p.wrap & 2) && he % 2) || ((p.wrap & 1) && we % 2))) return false;       // an odd side has no period under stride 2
+    return p.Hout == (he - 1) / p.stride + 1 && p.Wout == (we - 1) / p.stride + 1;
+}
+#define LB_WRAP_REFUSAL "wrap != 0 needs a 3x3 / pad 1 conv of stride 1 or 2 (even sides on the wrapped axes), ups 0 or 1, or a 2x2 sub-pixel conv; bits 0 (x) and 1 (y) only"
+// One coordinate of a wrapped axis (`size` = the axis' period; c in [-size, 2 size)): the pixel it reads
+__device__ __forceinline__ int lb_wrap_coord(int c, int size) { return c < 0 ? c + size : (c >= size ? c - size : c); }
+
 // v = 4 consecutive output columns n..n+3 of row m (fp32 accumulators).
 __device__ __forceinline__ void lb_gemm_store4(const LbGemmParams& p, int m, int n, int bidx, f32x4 v) {
     float o[4];

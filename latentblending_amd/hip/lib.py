@@ -34,7 +34,7 @@ class LbGemmParams(C.Structure):
         ("splitk", C.c_int), ("zero_page", C.c_void_p),
         ("scatter", C.c_int), ("sc_py", C.c_int), ("sc_px", C.c_int), ("reserved_", C.c_int),
         ("ln_colsum", C.c_void_p), ("ln_eps", C.c_float), ("reserved2_", C.c_int), ("ch_stats", C.c_void_p), ("ch_stats_rows", C.c_int),
-        ("gn_table", C.c_void_p), ("gn_silu", C.c_int),
+        ("gn_table", C.c_void_p), ("gn_silu", C.c_int), ("wrap", C.c_int),
     ]
 
 
@@ -89,34 +89,99 @@ class ConvGeom(_ConvGeomFields):
     frozen value.  ``ups``: the conv reads the nearest-2^ups upsampled input.  ``parity``: a sub-pixel upsampler conv on the low-res
     grid that scatters into the 2H x 2W output - ``(py, px)`` one of the four, ``"all"`` the four in one launch (W stacked
     [4][N][K]).  ``Hout`` / ``Wout`` are derived here and nowhere else: the rows and columns the launch computes per sample - of the
-    output, or of the low-res grid for a sub-pixel conv.  (A tuple underneath: the emitters build one per launch.)"""
+    output, or of the low-res grid for a sub-pixel conv.  (A tuple underneath: the emitters build one per launch.)
+
+    ``wrap``: wrap-around ("circular") padding, bit 0 = the columns wrap (left and right edges join), bit 1 = the rows wrap
+    (LbGemmParams.wrap, include/lb_hip.h).  Defined for the "same" geometries only - 3x3 / pad 1 at stride 1, at stride 2 with an even
+    effective side on every wrapped axis, ``ups`` 0 or 1, and the sub-pixel forms (on the low-res grid) - anything else raises
+    ``ValueError``.  It is a TRAILING element that exists only when it is not zero: a geometry built without it is the twelve-element
+    value it always was, a wrapped one carries a thirteenth - so equality and hash tell them apart, and ``g.wrap`` reads 0 or the bits.
+    (The shape is forced: the twelve-element value of an unwrapped geometry is pinned by the tests, and ``wrap`` has to take part in
+    equality and hash.)  Consequences: read a geometry through its attributes or ``g[:12]``, never by a twelve-way unpack of the
+    whole tuple; ``_asdict`` and ``_replace`` know about ``wrap`` (below), ``_make`` - which cannot tell the two shapes apart - is
+    refused."""
     __slots__ = ()
 
     def __new__(cls, Hin: int, Win: int, Cin: int, KH: int, KW: int, stride: int = 1, pad: int = 0, ups: int = 0,
-                ldx: Optional[int] = None, parity=None):
+                ldx: Optional[int] = None, parity=None, wrap: int = 0):
         if parity is None:
             Hout, Wout = ((Hin << ups) + 2 * pad - KH) // stride + 1, ((Win << ups) + 2 * pad - KW) // stride + 1
         else:
             Hout, Wout = Hin, Win
-        return tuple.__new__(cls, (Hin, Win, Cin, KH, KW, stride, pad, ups, Cin if ldx is None else ldx, parity, Hout, Wout))
+        g = tuple.__new__(cls, (Hin, Win, Cin, KH, KW, stride, pad, ups, Cin if ldx is None else ldx, parity, Hout, Wout))
+        return g.with_wrap(wrap)
+
+    def with_wrap(self, wrap: int) -> "ConvGeom":
+        """This geometry with ``wrap`` (0: without any); ``ValueError`` where wrap-around padding is not defined (see the class)."""
+        wrap = int(wrap)
+        if not wrap:
+            return self if len(self) == 12 else tuple.__new__(type(self), self[:12])
+        why = self.wrap_refusal(wrap)
+        if why:
+            raise ValueError(f"ConvGeom: wrap={wrap} {why}")
+        return tuple.__new__(type(self), self[:12] + (wrap,))
+
+    def wrap_refusal(self, wrap: int) -> Optional[str]:
+        """Why this geometry cannot wrap with these bits (None: it can) - the host twin of lb_wrap_defined (csrc/lb_gemm.h)."""
+        if wrap & ~3 or wrap < 0:
+            return "has bits other than 0 (x: the columns wrap) and 1 (y: the rows wrap)"
+        if self.parity is not None:
+            return None if (self.KH, self.KW, self.stride, self.ups) == (2, 2, 1, 0) else "needs the 2x2 sub-pixel form"
+        if (self.KH, self.KW, self.pad) != (3, 3, 1) or self.stride not in (1, 2) or self.ups not in (0, 1):
+            return f"is defined for 3x3 / pad 1 convs of stride 1 or 2 only (got {self.KH}x{self.KW}, stride {self.stride}, pad {self.pad}, ups {self.ups})"
+        if self.stride == 2 and ((wrap & 2 and (self.Hin << self.ups) % 2) or (wrap & 1 and (self.Win << self.ups) % 2)):
+            return f"at stride 2 needs an even side on every wrapped axis (got {self.Hin << self.ups} x {self.Win << self.ups})"
+        return None
+
+    @property
+    def wrap(self) -> int:
+        return self[12] if len(self) > 12 else 0
+
+    def _asdict(self) -> dict:
+        d = dict(zip(self._fields, self))
+        if self.wrap:
+            d["wrap"] = self.wrap
+        return d
+
+    def _replace(self, **kw) -> "ConvGeom":
+        """A geometry with the named CONSTRUCTOR fields (``Hin`` .. ``parity``, ``wrap``) replaced; ``Hout`` / ``Wout`` are derived
+        anew, so they cannot be named.  (A ``down3x3`` geometry, whose ``Hout`` a symmetric pad cannot express, is refused.)"""
+        args = ("Hin", "Win", "Cin", "KH", "KW", "stride", "pad", "ups", "ldx", "parity")
+        bad = set(kw) - set(args) - {"wrap"}
+        if bad:
+            raise ValueError(f"ConvGeom._replace: cannot replace {sorted(bad)} (Hout / Wout are derived)")
+        cur = {k: getattr(self, k) for k in args}
+        if self[:12] != type(self)(**cur)[:12]:
+            raise ValueError("ConvGeom._replace: this geometry was not built by the general constructor (down3x3)")
+        cur.update({k: v for k, v in kw.items() if k != "wrap"})
+        return type(self)(**cur, wrap=kw.get("wrap", self.wrap))
 
     @classmethod
-    def conv3x3(cls, H: int, W: int, cin: int, stride: int = 1, ups: int = 0, ldx: Optional[int] = None) -> "ConvGeom":
-        return cls(H, W, cin, 3, 3, stride, 1, ups, ldx)
+    def _make(cls, iterable):
+        raise TypeError("ConvGeom._make: build a geometry through ConvGeom(...), conv3x3, down3x3 or subpixel")
+
+    def __repr__(self) -> str:
+        body = ", ".join(f"{n}={v!r}" for n, v in zip(self._fields, self))
+        return f"ConvGeom({body}" + (f", wrap={self.wrap})" if self.wrap else ")")
+
+    @classmethod
+    def conv3x3(cls, H: int, W: int, cin: int, stride: int = 1, ups: int = 0, ldx: Optional[int] = None, wrap: int = 0) -> "ConvGeom":
+        return cls(H, W, cin, 3, 3, stride, 1, ups, ldx, wrap=wrap)
 
     @classmethod
     def down3x3(cls, H: int, W: int, cin: int, ldx: Optional[int] = None) -> "ConvGeom":
         """The SDXL VAE encoder's downsampler: 3x3 / stride 2 / pad 0 over the input padded by one zero row at the bottom and one
         zero column at the right ONLY (``F.pad(x, (0, 1, 0, 1))``).  Output (oy, ox) reads rows 2 oy .. 2 oy + 2, so the last output
         row and column reach one pixel past the image: the implicit-GEMM gather masks them (``iy < Hin``, ``ix < Win``).  ``Hout`` =
-        H / 2 is what a symmetric ``pad`` cannot express; H and W must be even (an odd side would need no far pad at all)."""
+        H / 2 is what a symmetric ``pad`` cannot express; H and W must be even (an odd side would need no far pad at all).
+        (It pads one side only: wrap-around padding is not defined for it, and ``with_wrap`` refuses it.)"""
         if H <= 0 or W <= 0 or H % 2 or W % 2:
             raise ValueError(f"ConvGeom.down3x3: H and W must be positive and even (got {H} x {W})")
         return tuple.__new__(cls, (H, W, cin, 3, 3, 2, 0, 0, cin if ldx is None else ldx, None, H // 2, W // 2))
 
     @classmethod
-    def subpixel(cls, H: int, W: int, cin: int, parity, ldx: Optional[int] = None) -> "ConvGeom":
-        return cls(H, W, cin, 2, 2, ldx=ldx, parity=parity)
+    def subpixel(cls, H: int, W: int, cin: int, parity, ldx: Optional[int] = None, wrap: int = 0) -> "ConvGeom":
+        return cls(H, W, cin, 2, 2, ldx=ldx, parity=parity, wrap=wrap)
 
     @property
     def scatter(self) -> int:
@@ -149,7 +214,9 @@ def gemm_params(*, M: int, N: int, K: int, ldw: int, ldc: int, lda: int = 0, A: 
     p.alpha, p.flags, p.zero_page = alpha, flags, zero_page
     if conv is not None:
         p.conv = 1
-        p.Hin, p.Win, p.Cin, p.KH, p.KW, p.stride, p.pad, p.ups, p.ldx, parity, p.Hout, p.Wout = conv
+        p.Hin, p.Win, p.Cin, p.KH, p.KW, p.stride, p.pad, p.ups, p.ldx, parity, p.Hout, p.Wout = conv[:12]
+        if conv.wrap:
+            p.wrap = conv.wrap
         if parity is not None:
             p.scatter = conv.scatter
             if parity != "all":
@@ -325,8 +392,8 @@ def conv_plan(p: LbGemmParams) -> LbConvPlan:
     return plan
 
 
-def conv_probe(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, flags: int = 0, zero_page: int = 64) -> LbGemmParams:
+def conv_probe(B: int, H: int, W: int, cin: int, cout: int, ks: int = 3, flags: int = 0, zero_page: int = 64, wrap: int = 0) -> LbGemmParams:
     """The parameter block of a 3x3 / stride 1 / pad 1 conv (``ks`` = 3) or a one-launch sub-pixel upsampler conv (``ks`` = 2) of
     this geometry, for the plan calls: host arithmetic only reads whether ``zero_page`` is set."""
-    g = ConvGeom.conv3x3(H, W, cin) if ks == 3 else ConvGeom(H, W, cin, ks, ks, parity="all")
+    g = ConvGeom.conv3x3(H, W, cin, wrap=wrap) if ks == 3 else ConvGeom(H, W, cin, ks, ks, parity="all", wrap=wrap)
     return gemm_params(M=g.M(B), N=cout, K=g.K, ldw=0, ldc=0, conv=g, alpha=0.0, flags=flags, zero_page=zero_page)

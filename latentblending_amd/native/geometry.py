@@ -22,6 +22,21 @@ Size = Union[int, Tuple[int, int]]
 HALO_RAGGED_MIN_FILL = 0.0
 
 
+TILEABLE_WRAP = {"": 0, "x": 1, "y": 2, "xy": 3}     # the ``tileable`` setting -> ``ConvGeom.wrap`` bits (bit 0: columns, bit 1: rows)
+
+
+def check_tileable(value, who: str = "NativeSDXLPipe") -> str:
+    """The ``tileable`` setting as the pipe keeps it: None / False / "" -> "" (off); "x", "y", "xy" (case-insensitive) ->
+    themselves; True -> "xy".  Anything else raises a ``ValueError`` that names the valid values."""
+    if value is None or value is False:
+        return ""
+    if value is True:
+        return "xy"
+    if isinstance(value, str) and value.strip().lower() in TILEABLE_WRAP:
+        return value.strip().lower()
+    raise ValueError(f"{who}: tileable must be None / False / '' (off), 'x', 'y', 'xy' or True (= 'xy'), got {value!r}")
+
+
 def latent_hw(size: Size) -> Tuple[int, int]:
     """A side ``L`` (meaning L x L) or a pair ``(H, W)`` in latent pixels -> ``(H, W)``."""
     if isinstance(size, (tuple, list)):

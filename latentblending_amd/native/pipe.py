@@ -34,7 +34,7 @@ from PIL import Image
 from ..hip import ops
 from ..hip.lib import api
 from .frames import DeviceImage
-from .geometry import program_key
+from .geometry import program_key, check_tileable, TILEABLE_WRAP
 from .lpips import NativeLPIPS
 from ..planner import noise_draws_per_run
 from .noise import CounterNoise
@@ -172,8 +172,15 @@ class StableDiffusionXLPipeline:
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
                  scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
                  tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream", encoders=None, loras=None,
-                 encoder: str = "tiny", vae_encoder_native: Optional[NativeVAEEncoder] = None):
-        """``loras``: [(src, scale), ...] = LoRA adapters loaded right after construction, in order (``load_lora``).
+                 encoder: str = "tiny", vae_encoder_native: Optional[NativeVAEEncoder] = None, tileable=None):
+        """``tileable``: seamless renders - None / False / "" (default) = off; "x" = the left and right edges of a frame join (a 360
+        degree strip), "y" = top and bottom, "xy" (or True) = all four (a tileable texture); anything else raises ``ValueError``.
+        Every 3x3 conv, downsampler and upsampler of the UNet and of the active decoder (full or tiny) then pads by wrap-around
+        instead of zeros (``ConvGeom.wrap``), which makes the networks functions on a cylinder / torus: the zero padding is the
+        only position cue they have.  The ENCODERS (image anchors) and the LPIPS metric stay zero-padded: a picture one anchors on
+        need not tile, and the metric is the metric.  ``pipe.tileable`` switches it afterwards (the cached UNet / decoder programs
+        are dropped); a pipe that never sets it records the programs it always recorded.
+        ``loras``: [(src, scale), ...] = LoRA adapters loaded right after construction, in order (``load_lora``).
         ``encoders``: a ``clip.NativeTextEncoders``; its ``encode`` becomes ``text_encoder_fn`` (unless one is given) and, when it
         carries the providers its towers were packed from, LoRA adapters reach the text towers too.  Adapters are merged from the
         providers the pipe was built with (``unet_provider``, ``encoders.providers``): a pipe given a ready-made ``unet_native``
@@ -212,6 +219,7 @@ class StableDiffusionXLPipeline:
         self.scheduler = make_scheduler(scheduler, turbo, torch.device(device))
         self._decoder = self._check_decoder(decoder)
         self._encoder = self._check_encoder(encoder)
+        self._tileable = self._check_tileable(tileable)
         self._vae_provider, self._vae_seed = vae_provider, seed + 1
         self._vae_native_given = vae_native is not None
         self.vae_encoder_native = vae_encoder_native
@@ -647,6 +655,31 @@ class StableDiffusionXLPipeline:
                     del cache[k]
 
     @staticmethod
+    def _check_tileable(value) -> str:
+        """None / False / "" -> "" (off); "x", "y", "xy" (case-insensitive) -> themselves; True -> "xy" (``geometry.check_tileable``)."""
+        return check_tileable(value)
+
+    @property
+    def tileable(self) -> str:
+        """"" (off), "x", "y" or "xy": the axes along which rendered frames join (see the constructor)."""
+        return self._tileable
+
+    @tileable.setter
+    def tileable(self, value):
+        value = self._check_tileable(value)
+        if value != self._tileable:
+            self._tileable = value
+            caches = (self._unet_programs, self._vae_programs, self._tiny_vae_programs)        # (the encoders never wrap)
+            if any(caches):
+                torch.cuda.synchronize(self.device)
+            for cache in caches:
+                cache.clear()
+
+    @property
+    def _wrap(self) -> int:
+        return TILEABLE_WRAP[self._tileable]
+
+    @staticmethod
     def _check_decoder(name) -> str:
         if not isinstance(name, str) or name.strip().lower() not in ("full", "tiny"):
             raise ValueError(f"NativeSDXLPipe: decoder must be 'full' or 'tiny' (got {name!r})")
@@ -753,7 +786,7 @@ class StableDiffusionXLPipeline:
     def unet_program(self, B: int, L) -> UNetProgram:
         """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named)."""
         def build():
-            prog = self.unet_native.build(B, L, ragged_halo=self._ragged_halo)
+            prog = self.unet_native.build(B, L, ragged_halo=self._ragged_halo, wrap=self._wrap)
             if self._use_graphs:
                 prog.enable_graphs()
             return prog
@@ -764,8 +797,8 @@ class StableDiffusionXLPipeline:
         tiny = self._decoder == "tiny"
 
         def build():
-            prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64) if tiny else \
-                self.vae_native.build(B, L, ragged_halo=self._ragged_halo)
+            prog = self._tiny_net().build(B, L, c64=self._tiny_conv_c64, wrap=self._wrap) if tiny else \
+                self.vae_native.build(B, L, ragged_halo=self._ragged_halo, wrap=self._wrap)
             if self._use_graphs:
                 prog.enable_graphs()
             return prog

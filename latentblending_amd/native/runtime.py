@@ -201,6 +201,22 @@ class Emitter:
         # (LB_GEMM_GN_A: ``gemm(..., gn=...)``) where the library's own plan says so (the GN_A part of lb_conv_plan's record); False:
         # the GroupNorm launch and its output buffer as ever
         self.gn_a = True
+        # wrap-around padding of every "same" conv this emitter launches (``ConvGeom.wrap`` bits: 1 = the columns wrap, 2 = the rows,
+        # 3 = both): set by ``RecordedProgram(..., wrap=...)`` for the programs of a tileable render.  Applied in ONE place, ``_geom``,
+        # which ``gemm``, ``gn_operand``, ``upconv`` and the probes go through: 3x3 / pad 1 convs (stride 1 and 2, ``ups``) and the
+        # sub-pixel upsampler forms get the bits, every other conv (1x1, pad 0, the encoder's ``down3x3``, LPIPS' 11x11 / 5x5) and
+        # every plain GEMM is left alone.  0 (default): the geometries, blocks and ops of ever.
+        self.wrap = 0
+
+    def _geom(self, conv: Optional[lib.ConvGeom]) -> Optional[lib.ConvGeom]:
+        """``conv`` as this emitter launches it: a "same" conv - 3x3 / pad 1, or a sub-pixel form - gets the emitter's ``wrap``;
+        every other conv is left alone.  A same conv that cannot take the bits (stride 2 over an odd side of a wrapped axis) raises
+        ``ValueError``: a program that calls itself tileable never records a zero-padded 3x3 conv."""
+        if not self.wrap or conv is None or conv.wrap:
+            return conv
+        if conv.parity is None and (conv.KH, conv.KW, conv.pad) != (3, 3, 1):
+            return conv
+        return conv.with_wrap(self.wrap)
 
     def _conv_plan(self, p: LbGemmParams) -> lib.LbConvPlan:
         """The one planning step of a conv: ONE lb_conv_plan call says where lb_gemm_f16 takes ``p`` and in which form.  Sets the
@@ -272,6 +288,7 @@ class Emitter:
         ``gn`` = what ``gn_operand`` returned for this very conv (A = the raw tensor): the conv consumes GroupNorm(A), either through
         the affine table (LB_GEMM_GN_A) or from the scratch buffer the GroupNorm launch filled; both go back to the arena here."""
         fold = gn is not None and gn.table is not None      # (the fold was decided by gn_operand; a flagged conv is never split along K)
+        conv = self._geom(conv)
         p = self._gemm_params(A if gn is None or fold else gn.scratch, W, out, M=M, bias=bias, residual=residual, rowvec=rowvec,
                               rows_per_batch=rows_per_batch, flags=flags, alpha=alpha, lda=lda, ldc=ldc, ldr=ldr, ld_rowvec=ld_rowvec,
                               conv=conv, ln=ln, ch_stats=ch_stats, gn=(gn.table, gn.args["silu"]) if fold else None)
@@ -301,6 +318,7 @@ class Emitter:
         (lb_groupnorm_affine_from_stats) and the conv will carry LB_GEMM_GN_A and read the raw x: no normalised buffer, no
         lb_groupnorm_from_stats.  Everywhere else: the GroupNorm launch into a scratch buffer, exactly as ever."""
         op = GnOperand(x, dict(gn))
+        conv = self._geom(conv)
         p = self._gemm_params(x, W, x, M=M, residual=x if has_residual else None, flags=flags, conv=conv)     # (pointers: only their nullness counts)
         # only with producer statistics and an fp16 stream tensor whose channels are the conv's (no padding in between)
         able = self.gn_a and gn.get("ch_stats") is not None and x.dtype == F16 and p.Cin == int(gn["C_"]) and p.ldx == p.Cin and \
@@ -341,7 +359,7 @@ class Emitter:
         GroupNorm statistics of what it stores - else 0 (the consumer then runs the two-pass GroupNorm)."""
         if ks == 2 and not self.upconv_one_launch(B, H, W, cin, cout):
             return 0
-        p = lib.conv_probe(B, H, W, cin, cout, ks, zero_page=self.zero_page.data_ptr())
+        p = lib.conv_probe(B, H, W, cin, cout, ks, zero_page=self.zero_page.data_ptr(), wrap=self.wrap)
         return self._conv_plan(p).stat_rows     # the library's own routing + tile constants, with the bits ``gemm`` will set (0: not a halo launch)
 
     @staticmethod
@@ -449,13 +467,17 @@ class RecordedProgram:
     ``L``: latent side or ``(H, W)`` -> ``.H`` / ``.W`` always, ``.L`` for square programs (else None); ``ragged_halo``: a
     non-square program may send 3x3 convs whose level does not divide into halo tiles to the ragged-tile form of the halo kernel
     (``geometry.use_ragged_halo``); a square program records what it always recorded.  ``L=None``: a program without geometry.
+    ``wrap``: wrap-around padding of every 3x3 conv, downsampler and upsampler the program emits (``Emitter.wrap``; 0: none).
     A subclass allocates its buffers, then records each ``Program`` it owns inside ``with self._recording(prog):``; its emitting
     code calls ``_mark`` at the end of every unit it wants to be seen.  ``programs``: the recorded ``Program``s in order."""
 
-    def __init__(self, net, B: int, L=None, ragged_halo: bool = True, journal: bool = False):
+    def __init__(self, net, B: int, L=None, ragged_halo: bool = True, journal: bool = False, wrap: int = 0):
         self.net, self.B = net, B
         self.arena = Arena(net.device, journal=journal)
         self.em = Emitter(self.arena)
+        if int(wrap) & ~3 or int(wrap) < 0:
+            raise ValueError(f"RecordedProgram: wrap must be 0, 1 (x), 2 (y) or 3 (both), got {wrap!r}")
+        self.wrap = self.em.wrap = int(wrap)
         if L is not None:
             self.H, self.W = latent_hw(L)
             self.L = self.H if self.H == self.W else None

@@ -141,18 +141,18 @@ class NativeTinyVAEDecoder(_TinyNet):
             else:       # the decoder's final ``2 x - 1`` goes into the last conv
                 pk.conv(p, 64, cfg.out_channels, 3, gain=0.5, bias_shift=0.5 if synthetic else 0.0, fold=True)
 
-    def build(self, B: int, L, c64: bool = True) -> "TinyVAEProgram":
+    def build(self, B: int, L, c64: bool = True, wrap: int = 0) -> "TinyVAEProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels.  ``c64``: LB_GEMM_C64 on the 64 -> 64 convs where ``use_c64``
-        says so (False: the same launches without the bit)."""
-        return TinyVAEProgram(self, B, L, c64=c64)
+        says so (False: the same launches without the bit).  ``wrap``: wrap-around padding of every conv (``RecordedProgram``)."""
+        return TinyVAEProgram(self, B, L, c64=c64, wrap=wrap)
 
 
 class _TinyProgram(RecordedProgram):
     """What the programs of the two halves share: the 64 -> 64 conv with its LB_GEMM_C64 rule, and the residual block.  (A
     non-square program's unflagged 3x3 convs may take the ragged halo form, as in ``VAEProgram``.)"""
 
-    def __init__(self, net: _TinyNet, B: int, L, c64: bool = True):
-        super().__init__(net, B, L)
+    def __init__(self, net: _TinyNet, B: int, L, c64: bool = True, wrap: int = 0):
+        super().__init__(net, B, L, wrap=wrap)
         self.c64 = bool(c64)
         self.c64_launches = 0                   # convs recorded with the bit
 
@@ -184,8 +184,8 @@ class _TinyProgram(RecordedProgram):
 class TinyVAEProgram(_TinyProgram):
     """One recorded tiny decode for a fixed (batch, latent size); the surface of ``VAEProgram``."""
 
-    def __init__(self, net: NativeTinyVAEDecoder, B: int, L, c64: bool = True):
-        super().__init__(net, B, L, c64)
+    def __init__(self, net: NativeTinyVAEDecoder, B: int, L, c64: bool = True, wrap: int = 0):
+        super().__init__(net, B, L, c64, wrap=wrap)
         cfg, H, W, dev = net.cfg, self.H, self.W, net.device
         SH, SW = H * cfg.scale_factor, W * cfg.scale_factor
         self.z_in = torch.zeros(B, cfg.latent_channels, H, W, dtype=F16, device=dev)

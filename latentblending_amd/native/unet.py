@@ -214,25 +214,26 @@ class NativeUNet(Reloadable):
         return sum(t.numel() * t.element_size() for t in self.w.values())
 
     # ------------------------------------------------------------------ program -----------
-    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "UNetProgram":
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0) -> "UNetProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
-        keeps its alloc / release journal (``Arena``); the recorded ops are the same."""
-        return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
+        keeps its alloc / release journal (``Arena``); the recorded ops are the same.  ``wrap``: wrap-around padding of conv_in, every
+        resnet conv, downsampler, upsampler and conv_out (bit 0: the columns wrap, bit 1: the rows; ``RecordedProgram``)."""
+        return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
 
 
 class UNetProgram(RecordedProgram):
     """One recorded forward for a fixed (batch, latent size).  Inputs are device buffers the
-    caller fills (torch copies on the launch stream); ``run`` replays the launches.  ``L`` / ``ragged_halo``: ``RecordedProgram``.
+    caller fills (torch copies on the launch stream); ``run`` replays the launches.  ``L`` / ``ragged_halo`` / ``wrap``: ``RecordedProgram``.
     ``marks``: one ``Mark`` per emission unit (``aug`` and ``ctx_kv`` of the conditioning program; ``temb_all``, ``conv_in``, every
     resnet / transformer / downsampler / upsampler by its weight prefix, and ``eps``); ``tap_names`` maps the block taps of the
     oracle (``conv_in``, ``down0`` .., ``mid``, ``up0`` ..) to the unit whose output they are.  ``capture()`` fills ``taps`` from the
     inputs ``set_conditioning`` / ``forward`` left in the buffers (fp16, NHWC for feature maps) and leaves ``eps`` as a ``forward`` would."""
 
-    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False):
+    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0):
         cfg = net.cfg
         H, W = latent_hw(L)
         check_unet_latent_size(H, W, len(cfg.block_channels))
-        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
         # LayerNorm handling of THIS program ("auto": fold into the consumers only where the program is launch-bound)
         self.ln_mode = net.fuse_layernorm if net.fuse_layernorm != "auto" else (B * max(H // 4, 1) * max(W // 4, 1) <= 1024)
         dev = net.device

@@ -116,18 +116,18 @@ class NativeVAEDecoder(_VAENet):
         pk.conv("decoder.conv_out", rev[-1], cfg.out_channels, 3, gain=0.5)
         self._stream_biases()
 
-    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False) -> "VAEProgram":
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0) -> "VAEProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
         keeps its alloc / release journal (``Arena``); the recorded ops are the same."""
-        return VAEProgram(self, B, L, ragged_halo=ragged_halo, journal=journal)
+        return VAEProgram(self, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
 
 
 class _VAEStreamProgram(RecordedProgram):
     """What the programs of the two halves share: the residual stream in its two formats (module docstring) and the units built on it -
     stream convs with their GroupNorm operands and producer statistics, resnets, the mid-block attention."""
 
-    def __init__(self, net: _VAENet, B: int, L, ragged_halo: bool = True, journal: bool = False):
-        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+    def __init__(self, net: _VAENet, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0):
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
         cfg = net.cfg
         self.scaled = bool(cfg.stream_fp16_scaled)
         self.fuse_gn_stats = bool(getattr(cfg, "fuse_gn_stats", True))
@@ -272,13 +272,13 @@ class _VAEStreamProgram(RecordedProgram):
 
 
 class VAEProgram(_VAEStreamProgram):
-    """One recorded decode for a fixed (batch, latent size); ``L`` / ``ragged_halo``: ``RecordedProgram``.
+    """One recorded decode for a fixed (batch, latent size); ``L`` / ``ragged_halo`` / ``wrap``: ``RecordedProgram``.
     ``marks``: one ``Mark`` per emission unit (``conv_in`` = post_quant_conv + conv_in, every resnet and upsampler by its weight
     prefix, ``mid_attention``, ``image_f32``); ``tap_names`` maps the oracle's block taps (``mid``, ``up0`` ..) to units;
     ``capture()`` fills ``taps``."""
 
-    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False):
-        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal)
+    def __init__(self, net: NativeVAEDecoder, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0):
+        super().__init__(net, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
         cfg, H, W = net.cfg, self.H, self.W
         dev = net.device
         SH, SW = H * cfg.scale_factor, W * cfg.scale_factor

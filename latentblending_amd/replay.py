@@ -10,12 +10,14 @@ trajectories and the part files are what the scripts produce), plus reader / wri
 the gradio UI saves (``gradio_ui.py:168-190``):
 
     [ {"settings": "sdxl", "width": W, "height": H, "num_inference_steps": S, "loras": [{"path": ..., "scale": ...}],
-       "image_encoder": "full"},
+       "image_encoder": "full", "tileable": "xy"},
       {"iteration": i, "seed": s, "prompt": "...", "negative_prompt": "...", "preview_image": ...}, ... ]
 
 ``"loras"`` is optional: the LoRA adapters the whole movie is rendered under (paths relative to the JSON file).
 ``"image_encoder"`` is optional too: the native pipe's ``encoder`` ("tiny" / "full") the movie's image key frames are encoded with;
 a file without it leaves the pipe as it stands, and ``save_movie_json`` writes the key only when it is not the default ("tiny").
+``"tileable"`` is optional as well: "x" / "y" / "xy" = the movie is rendered seamless along those axes (the native pipe's
+``tileable``); ``save_movie_json`` writes the key only when the setting is not off, so a default movie's file is the file it always was.
 An item may also carry ``"image"`` (a picture file, path relative to the JSON file) and ``"image_strength"`` (default 0.5): that
 key frame is an image anchor (``BlendingEngine.set_anchor_image1`` / ``2``) instead of a picture invented from its prompt.
 
@@ -68,11 +70,13 @@ DEFAULT_IMAGE_ENCODER = "tiny"
 
 
 def save_movie_json(fp_json: str, be, items: Sequence[Dict], loras: Optional[Sequence] = None,
-                    image_encoder: Optional[str] = None) -> None:
+                    image_encoder: Optional[str] = None, tileable=None) -> None:
     """Write the file the UI writes (gradio_ui.py:168-173): header from the engine's holder, then the items.  ``loras``
     (``[(path, scale), ...]``) goes into the header as ``"loras": [{"path": ..., "scale": ...}]`` - what ``run_movie_json`` loads.
     ``image_encoder``: "tiny" / "full" (None: the native pipe's ``encoder`` as it stands, "tiny" for any other pipe); written as
-    ``"image_encoder"`` only when it is not the default, so a movie of the default encoder is the file it always was."""
+    ``"image_encoder"`` only when it is not the default, so a movie of the default encoder is the file it always was.
+    ``tileable``: "x" / "y" / "xy" / True (None: the native pipe's ``tileable`` as it stands, off for any other pipe); written as
+    ``"tileable"`` only when it is not off."""
     header = {"settings": "sdxl", "width": be.dh.width_img, "height": be.dh.height_img,
               "num_inference_steps": be.dh.num_inference_steps}
     if loras:
@@ -83,6 +87,10 @@ def save_movie_json(fp_json: str, be, items: Sequence[Dict], loras: Optional[Seq
         raise ValueError(f"save_movie_json: image_encoder must be 'tiny' or 'full' (got {image_encoder!r})")
     if image_encoder.strip().lower() != DEFAULT_IMAGE_ENCODER:
         header["image_encoder"] = image_encoder.strip().lower()
+    from .native.geometry import check_tileable         # (here: the native package imports this module)
+    tileable = check_tileable(getattr(be.dh.pipe, "tileable", "") if tileable is None else tileable, "save_movie_json")
+    if tileable:
+        header["tileable"] = tileable
     with open(fp_json, "w") as fh:
         json.dump([header] + [dict(it) for it in items], fh, indent=4)
 
@@ -95,7 +103,7 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
                          list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None,
                          noise: Optional[str] = None, loras: Optional[Sequence] = None,
-                         image_encoder: Optional[str] = None) -> List[List]:
+                         image_encoder: Optional[str] = None, tileable=None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -127,12 +135,14 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     scales would be a picture of another model.
     ``image_encoder``: "tiny" / "full" = the native pipe's ``encoder`` for this chain - what the image key frames are encoded with
     (None: as the pipe stands); the previous value is restored afterwards.
+    ``tileable``: "x" / "y" / "xy" / True / False = the native pipe's ``tileable`` for this chain - seamless frames along those axes
+    (None: as the pipe stands); the previous value is restored afterwards.  ``ValueError`` on a pipe without the setting.
     """
     images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
     if images is not None and pipeline_keyframes:
         raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
                          "it cannot be combined with image key frames (list_images)")
-    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras), _encoder_as(be, image_encoder):
+    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras), _encoder_as(be, image_encoder), _tileable_as(be, tileable):
         try:
             return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
                                          keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
@@ -185,6 +195,23 @@ def _encoder_as(be, encoder: Optional[str]):
         yield
     finally:
         pipe.encoder = previous
+
+
+@contextlib.contextmanager
+def _tileable_as(be, tileable):
+    """Run the body with the engine's native pipe on ``tileable`` (None: untouched), then put the previous value back."""
+    if tileable is None:
+        yield
+        return
+    pipe = be.dh.pipe
+    if not hasattr(type(pipe), "tileable"):
+        raise ValueError("tileable=... needs the native pipe (NativeSDXLPipe)")
+    previous = pipe.tileable
+    pipe.tileable = tileable
+    try:
+        yield
+    finally:
+        pipe.tileable = previous
 
 
 @contextlib.contextmanager
@@ -301,13 +328,16 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
                    decoder: Optional[str] = None, noise: Optional[str] = None, loras: Optional[Sequence] = None,
-                   image_encoder: Optional[str] = None) -> List[List]:
+                   image_encoder: Optional[str] = None, tileable=None) -> List[List]:
     """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder``, ``noise`` as there).
     Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames.
     The header's ``"loras": [{"path": ..., "scale": ...}]`` (paths relative to the JSON file) are the chain's LoRA adapters; ``loras=``
     given here replaces them.  The header's ``"image_encoder"`` selects the encoder of the image key frames for this movie (the pipe
-    is restored afterwards); ``image_encoder=`` given here replaces it; neither: the pipe as it stands."""
+    is restored afterwards); ``image_encoder=`` given here replaces it; neither: the pipe as it stands.  The header's ``"tileable"``
+    ("x" / "y" / "xy") renders the movie seamless along those axes, likewise; ``tileable=`` given here replaces it."""
     header, items = load_movie_json(fp_json)
+    if tileable is None:
+        tileable = header.get("tileable")
     if image_encoder is None:
         image_encoder = header.get("image_encoder")
     if loras is None and header.get("loras"):
@@ -325,4 +355,4 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
                                 movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
-                                list_image_strengths=strengths, noise=noise, loras=loras, image_encoder=image_encoder)
+                                list_image_strengths=strengths, noise=noise, loras=loras, image_encoder=image_encoder, tileable=tileable)

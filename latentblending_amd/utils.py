@@ -150,6 +150,33 @@ def resize_frames_host(list_imgs, size_hw, filter: str = "bicubic") -> list:
             for im in list_imgs]
 
 
+def tile_preview(img, nx: int = 2, ny: int = 2):
+    """The ``nx`` x ``ny`` mosaic of one frame - the frame repeated ``nx`` times side by side and ``ny`` times down - for looking at
+    the seams of a tileable render (``NativeSDXLPipe(tileable=...)``): a frame that tiles shows no edge inside the mosaic.  ``img``:
+    a PIL image, a device frame (``DeviceImage``), an H x W [x C] array or tensor; returns a PIL image for a PIL image, else the
+    same kind of array / tensor (a device frame comes back as its uint8 device tensor)."""
+    nx, ny = int(nx), int(ny)
+    if nx < 1 or ny < 1:
+        raise ValueError(f"tile_preview: nx and ny must be at least 1 (got {nx} x {ny})")
+    dev = getattr(img, "_lb_u8", None)
+    if dev is not None:
+        img = dev
+    if isinstance(img, torch.Tensor):
+        if img.dim() not in (2, 3):
+            raise ValueError(f"tile_preview: a frame is H x W or H x W x C (got shape {tuple(img.shape)})")
+        return img.repeat(ny, nx, *([1] * (img.dim() - 2)))
+    try:
+        from PIL import Image
+    except ImportError:                 # (no Pillow: arrays only)
+        Image = None
+    if Image is not None and isinstance(img, Image.Image):
+        return Image.fromarray(np.tile(np.asarray(img), (ny, nx) + (1,) * (np.asarray(img).ndim - 2)))
+    a = np.asarray(img)
+    if a.ndim not in (2, 3):
+        raise ValueError(f"tile_preview: a frame is H x W or H x W x C (got shape {a.shape})")
+    return np.tile(a, (ny, nx) + (1,) * (a.ndim - 2))
+
+
 def add_frames_linear_interp(list_imgs: List[np.ndarray],
                              fps_target: Optional[Number] = None,
                              duration_target: Optional[Number] = None,
