@@ -21,6 +21,7 @@ What is different underneath:
 """
 from __future__ import annotations
 
+import base64
 import contextlib
 import os
 import platform
@@ -131,6 +132,8 @@ class BlendingEngine:
         self.anchor_image2 = None
         self.anchor_image_strength1 = 0.5
         self.anchor_image_strength2 = 0.5
+        self.control_image = None           # ControlNet hint (set_control_image): held fixed through the whole tree - and the whole movie
+        self.control_scale = 1.0
         self.negative_prompt = None
         self.stats = {}
         self._preset_anchor_frames = None      # (frame of anchor 1, frame of anchor 2) for the next transition: see preset_anchors
@@ -289,6 +292,28 @@ class BlendingEngine:
         self.anchor_image1 = self.anchor_image2 = None
         self.anchor_image_strength1 = self.anchor_image_strength2 = 0.5
 
+    def set_control_image(self, image, scale: float = 1.0):
+        """Guide every UNet evaluation - both anchors and every branch - by a ControlNet on the hint ``image`` (a PIL image or uint8
+        [H, W, 3]: depth, edges, pose ... as the loaded ControlNet expects; resized with LANCZOS to the render size) at conditioning
+        scale ``scale``.  A hint pins the composition of every frame, so the prompts can differ far more before the picture starts to
+        move.  It belongs to the MOVIE, not to a key frame: ``swap_forward`` leaves it, ``get_state_dict`` carries it.  The pipe must
+        have a ControlNet (``NativeSDXLPipe(controlnet=...)`` / ``load_controlnet``; any other pipe: a ``controlnet`` attribute) -
+        checked when the next run starts.  Under a multi-rank farm EVERY rank must set the same hint."""
+        arr = image if isinstance(image, Image.Image) else np.asarray(image)
+        if not isinstance(arr, Image.Image) and (arr.ndim != 3 or arr.shape[-1] != 3 or arr.dtype != np.uint8):
+            raise ValueError(f"control image: expected a PIL image or a uint8 [H, W, 3] picture (got {arr.dtype} {arr.shape})")
+        self.control_image, self.control_scale = image, float(scale)
+
+    def clear_control_image(self):
+        """No hint: the uncontrolled frames again, bit for bit."""
+        self.control_image, self.control_scale = None, 1.0
+
+    def _sync_control(self):
+        """Hand the hint (or its absence) to the holder before anything is denoised; a holder that has it already does nothing."""
+        image = getattr(self, "control_image", None)
+        if image is not None or getattr(self.dh, "control_image", None) is not None:
+            self.dh.set_control(image, getattr(self, "control_scale", 1.0))
+
     def set_num_inference_steps(self, num_inference_steps=None):
         if num_inference_steps is None:
             num_inference_steps = 4 if self.dh.is_sdxl_turbo else 30
@@ -341,6 +366,7 @@ class BlendingEngine:
 
         steps = self.num_inference_steps
         self._apply_noise_setting()
+        self._sync_control()
         use_frontier = self.frontier_width > 1 or self.farm is not None
         if (self.anchor_image1 is not None or self.anchor_image2 is not None) and self._farm_on():
             # (under counter-based noise there is no stream to align, but that was never the only obstacle: see the message)
@@ -576,6 +602,7 @@ class BlendingEngine:
         steps, n = self.num_inference_steps, len(embeddings)
         self.dh.set_num_inference_steps(steps)
         self._apply_noise_setting()
+        self._sync_control()
         pipe = self.dh.pipe
         farm = self.farm if self._farm_on() else None
         ancestral = self._draws_noise(getattr(pipe, "scheduler", None))      # (any sampler that draws per-step noise)
@@ -1105,6 +1132,7 @@ class BlendingEngine:
                       return_image: Optional[bool] = False):
         """Pass-through to the holder; ``list_conditionings[0]`` is the embedding 4-tuple."""
         self.dh.set_num_inference_steps(self.num_inference_steps)
+        self._sync_control()
         assert type(list_conditionings) is list, "list_conditionings need to be a list"
         return self.dh.run_diffusion_sd_xl(
             text_embeddings=list_conditionings[0], latents_start=latents_start,
@@ -1230,6 +1258,10 @@ class BlendingEngine:
         state['guidance_scale_base'] = float(self.guidance_scale_base)
         state['list_idx_injection'] = [int(i) for i in self.list_idx_injection]
         state['list_nmb_stems'] = [int(s) for s in self.list_nmb_stems]
+        if self.control_image is not None:      # (only then: a state without a hint is the dict it always was)
+            pic = self.control_image.convert("RGB") if isinstance(self.control_image, Image.Image) else Image.fromarray(np.asarray(self.control_image))
+            state['control_image'] = {'width': pic.size[0], 'height': pic.size[1], 'rgb_base64': base64.b64encode(pic.tobytes()).decode("ascii")}
+            state['control_scale'] = float(self.control_scale)
         return state
 
     def load_state_dict(self, state):
@@ -1267,6 +1299,13 @@ class BlendingEngine:
         if 'list_idx_injection' in state and 'list_nmb_stems' in state:
             self.list_idx_injection = [int(i) for i in state['list_idx_injection']]
             self.list_nmb_stems = [int(s) for s in state['list_nmb_stems']]
+        hint = state.get('control_image')
+        if hint is None:
+            self.clear_control_image()
+        else:
+            if isinstance(hint, dict):
+                hint = Image.frombytes("RGB", (int(hint['width']), int(hint['height'])), base64.b64decode(hint['rgb_base64']))
+            self.set_control_image(hint, float(state.get('control_scale', 1.0)))
 
     def swap_forward(self):
         """Keyframe two becomes keyframe one (multi-transition chains)."""
@@ -1277,6 +1316,7 @@ class BlendingEngine:
         # an image anchor travels with its key frame: the second anchor's picture and strength become the first's
         self.anchor_image1, self.anchor_image_strength1 = self.anchor_image2, self.anchor_image_strength2
         self.anchor_image2, self.anchor_image_strength2 = None, 0.5
+        # (the ControlNet hint stays: it belongs to the movie, not to a key frame)
 
     # ------------------------------------------------------------------ metric ------------
     def get_lpips_similarity(self, imgA, imgB):

@@ -45,6 +45,11 @@ class DiffusersHolder:
         self.height_latent = latent_side
         self.width_img = latent_side * self.pipe.vae_scale_factor
         self.height_img = latent_side * self.pipe.vae_scale_factor
+        # ControlNet hint (set_control): the picture as given, and what the generic loop feeds pipe.controlnet
+        self.control_image = None
+        self.control_scale = 1.0
+        self._control_token = None
+        self._control_cond = None
 
     # ---------------------------------------------------------------- configuration -------
     def init_types(self):
@@ -79,6 +84,40 @@ class DiffusersHolder:
         """Only one negative prompt is supported: a string or the first entry of a list."""
         as_list = [negative_prompt] if isinstance(negative_prompt, str) else negative_prompt
         self.negative_prompt = as_list[:1] if len(as_list) > 1 else as_list
+
+    def set_control(self, image, scale: float = 1.0):
+        """Hold ``image`` (a PIL image or uint8 [H, W, 3]; None: no control) as the ControlNet hint of every UNet evaluation, at
+        conditioning scale ``scale``.  Native pipe: ``pipe.set_control_image`` / ``clear_control`` (the controlled launch programs).
+        Any other pipe: the generic loop calls ``pipe.controlnet(...)`` the way diffusers' ControlNet pipeline does - the picture
+        resized with LANCZOS to the holder's size, float in [0, 1] (not normalised to +-1), the same hint for both CFG halves.
+        Calling it again with the same picture, scale and size does nothing."""
+        token = None if image is None else (id(image), float(scale), self.width_img, self.height_img)
+        if token == self._control_token and (image is None or image is self.control_image):
+            return
+        pipe = self.pipe
+        if image is not None and not (callable(getattr(pipe, "controlnet", None)) or hasattr(pipe, "set_control_image")):
+            raise ValueError(f"set_control: the pipe ({type(pipe).__name__}) has no controlnet")
+        if _is_native(pipe):        # the controlled launch programs (the generic loop below, on a native pipe, goes through its facades)
+            if image is None:
+                if hasattr(pipe, "clear_control"):
+                    pipe.clear_control()
+            else:
+                pipe.set_control_image(image, float(scale))
+        if image is not None:
+            from PIL import Image
+            pic = image.convert("RGB") if isinstance(image, Image.Image) else None
+            if pic is None:
+                arr = np.asarray(image)
+                if arr.ndim != 3 or arr.shape[-1] != 3 or arr.dtype != np.uint8:
+                    raise ValueError(f"control image: expected a PIL image or a uint8 [H, W, 3] picture (got {arr.dtype} {arr.shape})")
+                pic = Image.fromarray(arr)
+            if pic.size != (self.width_img, self.height_img):
+                pic = pic.resize((self.width_img, self.height_img), Image.LANCZOS)
+            u8 = torch.from_numpy(np.asarray(pic, dtype=np.uint8).copy())
+            self._control_cond = (u8.permute(2, 0, 1)[None].to(torch.float32) / 255.0).to(pipe._execution_device)
+        if image is None:
+            self._control_cond = None
+        self.control_image, self.control_scale, self._control_token = image, float(scale), token
 
     # ---------------------------------------------------------------- pipeline helpers ----
     def get_text_embedding(self, prompt):
@@ -256,11 +295,18 @@ class DiffusersHolder:
             cfg = pipe.do_classifier_free_guidance
             model_in = torch.cat([latents] * 2) if cfg else latents
             model_in = pipe.scheduler.scale_model_input(model_in, t)
+            added = {"text_embeds": text_embeds, "time_ids": time_ids}
+            control = {}
+            if self._control_cond is not None:      # diffusers' ControlNet pipeline: the ControlNet sees the UNet's own inputs
+                cond = self._control_cond.to(model_in.dtype)
+                down, mid = pipe.controlnet(
+                    model_in, t, encoder_hidden_states=prompt_embeds, controlnet_cond=torch.cat([cond] * 2) if cfg else cond,
+                    conditioning_scale=self.control_scale, added_cond_kwargs=added, return_dict=False)
+                control = {"down_block_additional_residuals": down, "mid_block_additional_residual": mid}
             eps = pipe.unet(
                 model_in, t, encoder_hidden_states=prompt_embeds, timestep_cond=timestep_cond,
                 cross_attention_kwargs=pipe.cross_attention_kwargs,
-                added_cond_kwargs={"text_embeds": text_embeds, "time_ids": time_ids},
-                return_dict=False)[0]
+                added_cond_kwargs=added, return_dict=False, **control)[0]
             if cfg:
                 eps_uncond, eps_text = eps.chunk(2)
                 eps = eps_uncond + pipe.guidance_scale * (eps_text - eps_uncond)

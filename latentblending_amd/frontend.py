@@ -165,13 +165,15 @@ class BlendingVariableHolder:
 
     # ---- gradio_ui.py:222-262: the chain over the edited list, one part per segment, concatenated ----
     def generate_movie(self, t_per_segment=10, fps: int = 30, movie_encoder: Optional[str] = None, movie_size=None,
-                       movie_resample: Optional[str] = None, noise: Optional[str] = None, loras=None, tileable=None):
+                       movie_resample: Optional[str] = None, noise: Optional[str] = None, loras=None, tileable=None,
+                       control_image=None, control_scale: Optional[float] = None):
         """``movie_encoder``: "host" / "device" for the parts' ``write_movie_transition``; ``movie_size`` / ``movie_resample``: its
         ``size_output=(W, H)`` / ``resample=`` (None: the session's settings); ``noise``: "stream" / "counter" = the native pipe's
         sampler noise for this movie (None: the session's ``noise``, else as the pipe stands); ``loras``: ``[(path, scale), ...]`` =
         the LoRA adapters of this movie (None: the holder's ``loras``, which ``write_json`` also puts into the JSON header);
         ``tileable``: "x" / "y" / "xy" = seamless frames along those axes for this movie (the native pipe's ``tileable``; None: as
-        the pipe stands)."""
+        the pipe stands); ``control_image`` / ``control_scale``: a ControlNet hint held through the whole movie (None: the session's
+        hint as it stands)."""
         from .replay import run_multi_transition
         if len(self.data) < 2:
             raise ValueError("generate_movie: the movie needs at least two images (add_image_to_video)")
@@ -182,7 +184,8 @@ class BlendingVariableHolder:
                                  duration_single_trans=t_per_segment,
                                  list_negative_prompts=[it["negative_prompt"] for it in self.data], fps=fps, dp_parts=self.dp_out,
                                  movie_encoder=movie_encoder, movie_size=movie_size, movie_resample=movie_resample, noise=noise,
-                                 loras=self.loras if loras is None else loras, tileable=tileable)
+                                 loras=self.loras if loras is None else loras, tileable=tileable, control_image=control_image,
+                                 control_scale=control_scale)
         print(f"DONE! MOVIE SAVED IN {self.fp_movie}")
         return self.fp_movie
 

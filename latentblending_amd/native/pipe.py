@@ -34,12 +34,13 @@ from PIL import Image
 from ..hip import ops
 from ..hip.lib import api
 from .frames import DeviceImage
-from .geometry import program_key, check_tileable, TILEABLE_WRAP
+from .geometry import latent_hw, program_key, check_tileable, TILEABLE_WRAP
 from .lpips import NativeLPIPS
 from ..planner import noise_draws_per_run
 from .noise import CounterNoise
 from .scheduler import make_scheduler
 from .unet import NativeUNet, UNetConfig, UNetProgram
+from .controlnet import ControlNetConfig, ControlNetProgram, HintProgram, NativeControlNet, check_cfg_fits, hint_tensor
 from .tiny_vae import NativeTinyVAEDecoder, NativeTinyVAEEncoder, TinyEncoderProgram, TinyVAEConfig, TinyVAEProgram
 from .vae import NativeVAEDecoder, NativeVAEEncoder, VAEConfig, VAEEncoderProgram, VAEProgram, sample_moments
 from ..replay import lora_entries
@@ -70,19 +71,62 @@ class _UNetFacade:
                                       time_cond_proj_dim=c.time_cond_proj_dim)
 
     def __call__(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None,
-                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=False):
+                 cross_attention_kwargs=None, added_cond_kwargs=None, return_dict=False,
+                 down_block_additional_residuals=None, mid_block_additional_residual=None):
+        """``down_block_additional_residuals`` / ``mid_block_additional_residual`` (NCHW, what ``pipe.controlnet`` returns): added to
+        the skip copies and to the mid block's output (``UNetProgram.forward_with_residuals``; always on the PLAIN program)."""
         pipe = self._pipe
         if self.config.time_cond_proj_dim is not None and timestep_cond is None:
             raise ValueError("NativeSDXLPipe.unet: this UNet is guidance-embedded (time_cond_proj_dim = "
                              f"{self.config.time_cond_proj_dim}); timestep_cond is required "
                              "(pipe.get_guidance_scale_embedding(guidance_scale - 1, embedding_dim=time_cond_proj_dim))")
         B, _, H, W = sample.shape
-        prog = pipe.unet_program(B, (H, W))
+        prog = pipe.unet_program(B, (H, W), control=False)
         prog.set_conditioning(encoder_hidden_states, added_cond_kwargs["text_embeds"],
                               added_cond_kwargs["time_ids"],
                               timestep_cond=None if timestep_cond is None else timestep_cond.to(sample.device, F16))
         t = torch.as_tensor(timestep, dtype=F32).reshape(-1).expand(B)
-        return (prog.forward(sample.to(F16), t.to(sample.device)).clone(),)
+        if down_block_additional_residuals is None and mid_block_additional_residual is None:
+            return (prog.forward(sample.to(F16), t.to(sample.device)).clone(),)
+        nhwc = lambda r: r.to(pipe.device, F16).permute(0, 2, 3, 1).contiguous()          # noqa: E731
+        down = [nhwc(r) for r in (down_block_additional_residuals or ())]
+        mid = None if mid_block_additional_residual is None else nhwc(mid_block_additional_residual)
+        return (prog.forward_with_residuals(sample.to(F16), t.to(sample.device), down, mid).clone(),)
+
+
+class _ControlNetFacade:
+    """diffusers' ``ControlNetModel`` call on the pipe's loaded ControlNet: ``(down_block_res_samples, mid_block_res_sample)`` in NCHW.
+    ``controlnet_cond``: [B or 1, 3, H, W] in [0, 1] (the FIRST picture serves every sample: the native programs hold one hint)."""
+
+    def __init__(self, pipe):
+        self._pipe = pipe
+
+    @property
+    def config(self):
+        net = self._pipe._require_controlnet("pipe.controlnet")
+        return SimpleNamespace(conditioning_channels=net.cfg.cond_channels, global_pool_conditions=False)
+
+    @torch.no_grad()
+    def __call__(self, sample, timestep, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=1.0,
+                 added_cond_kwargs=None, guess_mode=False, return_dict=False, **_):
+        pipe = self._pipe
+        net = pipe._require_controlnet("pipe.controlnet")
+        if guess_mode:
+            raise NotImplementedError("pipe.controlnet: guess mode is not implemented")
+        if controlnet_cond is None:
+            raise ValueError("pipe.controlnet: controlnet_cond is required")
+        B, _, H, W = sample.shape
+        pipe.set_control_scale(conditioning_scale)
+        cond = controlnet_cond[:1].to(pipe.device, F32).permute(0, 2, 3, 1)
+        emb = pipe._hint_program((int(cond.shape[1]), int(cond.shape[2]))).embed(cond)
+        prog = pipe._controlnet_program(B, (H, W))
+        prog.set_hint(emb)
+        prog.set_conditioning(encoder_hidden_states, added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"])
+        t = torch.as_tensor(timestep, dtype=F32).reshape(-1).expand(B)
+        down, mid = prog.forward(sample.to(F16), t.to(sample.device))
+        nchw = lambda r: r.permute(0, 3, 1, 2).contiguous()          # noqa: E731
+        out = ([nchw(d) for d in down], nchw(mid))
+        return out if not return_dict else SimpleNamespace(down_block_res_samples=out[0], mid_block_res_sample=out[1])
 
 
 class _VAEFacade:
@@ -172,8 +216,11 @@ class StableDiffusionXLPipeline:
                  vae_native: Optional[NativeVAEDecoder] = None, allow_synthetic: Optional[bool] = None,
                  scheduler: Optional[str] = None, decoder: str = "full", tiny_vae_provider=None,
                  tiny_vae_native: Optional[NativeTinyVAEDecoder] = None, noise: str = "stream", encoders=None, loras=None,
-                 encoder: str = "tiny", vae_encoder_native: Optional[NativeVAEEncoder] = None, tileable=None):
-        """``tileable``: seamless renders - None / False / "" (default) = off; "x" = the left and right edges of a frame join (a 360
+                 encoder: str = "tiny", vae_encoder_native: Optional[NativeVAEEncoder] = None, tileable=None, controlnet=None):
+        """``controlnet``: a ControlNet loaded right after construction (``load_controlnet``: a ``NativeControlNet``, a
+        ``ControlNetConfig`` - seeded synthetic weights, announced -, a provider, a ``(config, provider)`` pair or the path of a
+        diffusers ControlNet folder); None (default): none - and with one loaded, nothing changes until ``set_control_image``.
+        ``tileable``: seamless renders - None / False / "" (default) = off; "x" = the left and right edges of a frame join (a 360
         degree strip), "y" = top and bottom, "xy" (or True) = all four (a tileable texture); anything else raises ``ValueError``.
         Every 3x3 conv, downsampler and upsampler of the UNet and of the active decoder (full or tiny) then pads by wrap-around
         instead of zeros (``ConvGeom.wrap``), which makes the networks functions on a cylinder / torus: the zero padding is the
@@ -296,8 +343,136 @@ class StableDiffusionXLPipeline:
         self._side_stream = None            # lazily created: conditioning programs of big batches run here beside the small anchor steps
         self._noise = "stream"
         self.noise = noise
+        # ControlNet (load_controlnet / set_control_image): the controlled UNet programs live in a cache of their own, so the plain
+        # programs - and everything a pipe without a hint does - stay what they were
+        self._seed = seed
+        self.controlnet_native: Optional[NativeControlNet] = None
+        self.controlnet = _ControlNetFacade(self)
+        self._control_hint: Optional[torch.Tensor] = None       # the control image as given ([1, H0, W0, 3] uint8 on the host), or None
+        self._control_scale = 1.0
+        self._control_emb: Dict[Tuple[int, int], torch.Tensor] = {}     # latent (H, W) -> the embedded hint (one size at a time)
+        self._control_programs: "OrderedDict[Tuple[int, ...], UNetProgram]" = OrderedDict()
+        self._controlnet_programs: "OrderedDict[Tuple[int, ...], ControlNetProgram]" = OrderedDict()     # (the facade's)
+        self._hint_programs: "OrderedDict[Tuple[int, ...], HintProgram]" = OrderedDict()
+        if controlnet is not None:
+            self.load_controlnet(controlnet)
         for src, scale in lora_entries(loras):
             self.load_lora(src, scale)
+
+    # ---- ControlNet -----------------------------------------------------------------------
+    def _require_controlnet(self, who: str) -> NativeControlNet:
+        if self.controlnet_native is None:
+            raise ValueError(f"{who}: no ControlNet is loaded (NativeSDXLPipe(controlnet=...) or pipe.load_controlnet(src))")
+        return self.controlnet_native
+
+    def _drop_control_programs(self, hint_too: bool = True) -> None:
+        caches = (self._control_programs, self._controlnet_programs) + ((self._hint_programs,) if hint_too else ())
+        if any(caches):
+            torch.cuda.synchronize(self.device)
+        for cache in caches:
+            cache.clear()
+        self._control_emb.clear()
+
+    def load_controlnet(self, src) -> NativeControlNet:
+        """Load a ControlNet: a ready ``NativeControlNet``; a ``ControlNetConfig`` (seeded synthetic weights, announced like the other
+        stand-ins); a provider (the config that fits the UNet, the UNet's transformer depths); a ``(config, provider)`` pair; or the
+        path of a diffusers ControlNet folder (``config.json`` + ``*.safetensors``).  Replaces a loaded one; a control image that is
+        set stays set.  Until ``set_control_image`` nothing the pipe renders changes."""
+        fuse = self.unet_native.fuse_layernorm
+        kw = dict(device=self.device, fuse_layernorm=fuse, scale=self._control_scale)
+        if isinstance(src, NativeControlNet):
+            net = src
+            net.set_scale(self._control_scale)
+        elif isinstance(src, (str, os.PathLike)):
+            net = NativeControlNet.from_dir(os.fspath(src), **kw)
+        else:
+            cfg, provider = src if isinstance(src, tuple) else ((src, None) if isinstance(src, ControlNetConfig) else (None, src))
+            if cfg is None:
+                cfg = ControlNetConfig.for_unet(self.unet_cfg)
+            check_cfg_fits(cfg, self.unet_cfg)          # (before a gigabyte of weights is packed)
+            if provider is None:
+                self._synthetic_notice("ControlNet weights (the hint then guides nothing meaningful)",
+                                       "pass controlnet=<folder of a diffusers ControlNet> or a (config, provider) pair")
+                provider = SyntheticProvider(self._seed + 3)
+            net = NativeControlNet(cfg, provider, **kw)
+        net.check_fits(self.unet_native)
+        self._drop_control_programs()
+        self.controlnet_native = net
+        return net
+
+    def unload_controlnet(self) -> None:
+        """Drop the ControlNet, its programs and the control image."""
+        self._drop_control_programs()
+        self.controlnet_native, self._control_hint = None, None
+
+    @property
+    def control_active(self) -> bool:
+        """A ControlNet is loaded AND a control image is set: the native loops run the controlled programs."""
+        return self.controlnet_native is not None and self._control_hint is not None
+
+    @property
+    def control_scale(self) -> float:
+        return self._control_scale
+
+    def set_control_image(self, image, scale: Optional[float] = 1.0) -> None:
+        """Hold ``image`` - a PIL image or uint8 [H, W, 3] - as the hint of every UNet evaluation from now on: resized with LANCZOS to
+        the render size, fp16 in [0, 1] (not normalised to +-1), the same hint for both CFG halves and every sample.  ``scale``:
+        the conditioning scale (``set_control_scale``; None keeps the current one).  The hint is embedded once per render size."""
+        self._require_controlnet("set_control_image")
+        self._control_hint = (hint_tensor(image) * 255.0).round().to(torch.uint8)      # (validated; kept at its own size: re-embedded per render size)
+        self._control_emb.clear()
+        if scale is not None:
+            self.set_control_scale(scale)
+
+    def set_control_scale(self, scale: float) -> None:
+        """The conditioning scale: rewritten into the packed zero convs in place - no program is dropped, graphs keep replaying."""
+        scale = float(scale)
+        if self.controlnet_native is not None and (scale != self._control_scale or scale != self.controlnet_native.scale):
+            self.controlnet_native.set_scale(scale)
+        self._control_scale = scale
+
+    def clear_control(self) -> None:
+        """No hint: the plain programs again, bit for bit (the ControlNet stays loaded, the controlled programs stay cached)."""
+        self._control_hint = None
+        self._control_emb.clear()
+
+    def _hint_program(self, size_hw) -> HintProgram:
+        net = self._require_controlnet("control image")
+
+        def build():
+            prog = net.build_hint(size_hw, ragged_halo=self._ragged_halo, wrap=self._wrap)
+            if self._use_graphs:
+                prog.enable_graphs()
+            return prog
+        return self._cached(self._hint_programs, program_key(1, tuple(size_hw)), build)
+
+    def _controlnet_program(self, B: int, L) -> ControlNetProgram:
+        net = self._require_controlnet("pipe.controlnet")
+
+        def build():
+            prog = net.build(B, L, ragged_halo=self._ragged_halo, wrap=self._wrap)
+            if self._use_graphs:
+                prog.enable_graphs()
+            return prog
+        return self._cached(self._controlnet_programs, program_key(B, L), build)
+
+    def _control_embedding(self, LH: int, LW: int) -> torch.Tensor:
+        """The hint embedded for a latent grid of ``LH x LW`` (a clone of the hint program's output); one size is kept - another
+        render size drops the controlled programs of the old one and embeds the hint again."""
+        emb = self._control_emb.get((LH, LW))
+        if emb is None:
+            stale = [k for k in self._control_programs if k != program_key(k[0], (LH, LW))]
+            if stale:
+                torch.cuda.synchronize(self.device)
+            for k in stale:
+                del self._control_programs[k]
+            self._control_emb.clear()
+            f = self.vae_scale_factor
+            hint = hint_tensor(self._control_hint[0].numpy(), (LH * f, LW * f))
+            emb = self._control_emb[(LH, LW)] = self._hint_program((LH * f, LW * f)).embed(hint).clone()
+            for k, prog in self._control_programs.items():
+                prog.set_hint(emb)
+        return emb
 
     # ---- LoRA adapters --------------------------------------------------------------------
     @property
@@ -653,6 +828,7 @@ class StableDiffusionXLPipeline:
                     torch.cuda.synchronize(self.device)
                 for k in stale:
                     del cache[k]
+            self._drop_control_programs()
 
     @staticmethod
     def _check_tileable(value) -> str:
@@ -674,6 +850,7 @@ class StableDiffusionXLPipeline:
                 torch.cuda.synchronize(self.device)
             for cache in caches:
                 cache.clear()
+            self._drop_control_programs()           # (the ControlNet's convs and the hint embedding wrap with the UNet's)
 
     @property
     def _wrap(self) -> int:
@@ -783,8 +960,28 @@ class StableDiffusionXLPipeline:
             return prog
         return self._cached(self._tiny_encoder_programs, program_key(B, L), build)
 
-    def unet_program(self, B: int, L) -> UNetProgram:
-        """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named)."""
+    def unet_program(self, B: int, L, control: Optional[bool] = None) -> UNetProgram:
+        """``L``: latent side or ``(H, W)``.  A size the UNet's levels do not divide raises ``ValueError`` (nearest valid sizes named).
+        ``control``: None (default) = the controlled program - both networks in one step program, the hint in place - while a
+        control image is active (``control_active``), else the plain one; False = the plain program whatever is set.  The two
+        kinds are cached under different keys."""
+        if control is None:
+            control = self.control_active
+        if control:
+            net = self._require_controlnet("unet_program(control=True)")
+            if self._control_hint is None:
+                raise ValueError("unet_program(control=True): no control image is set (set_control_image)")
+            LH, LW = latent_hw(L)
+            emb = self._control_embedding(LH, LW)
+
+            def build_controlled():
+                prog = self.unet_native.build(B, L, ragged_halo=self._ragged_halo, wrap=self._wrap, control=net)
+                prog.set_hint(emb)
+                if self._use_graphs:
+                    prog.enable_graphs()
+                return prog
+            return self._cached(self._control_programs, program_key(B, L), build_controlled)
+
         def build():
             prog = self.unet_native.build(B, L, ragged_halo=self._ragged_halo, wrap=self._wrap)
             if self._use_graphs:
@@ -808,7 +1005,7 @@ class StableDiffusionXLPipeline:
         self._use_graphs = bool(flag)
         if flag:
             for cache in (self._unet_programs, self._vae_programs, self._tiny_vae_programs, self._tiny_encoder_programs,
-                          self._vae_encoder_programs):
+                          self._vae_encoder_programs, self._control_programs, self._controlnet_programs, self._hint_programs):
                 for p in cache.values():
                     p.enable_graphs()
 

@@ -20,7 +20,7 @@ MI355X-specific here:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -58,19 +58,13 @@ class UNetConfig:
         return self.pooled_dim + 6 * self.add_time_dim
 
 
-class NativeUNet(Reloadable):
-    def __init__(self, cfg: UNetConfig, provider, device="cuda", fuse_layernorm="auto"):
-        """``fuse_layernorm``: fold the three LayerNorms of every transformer block into the GEMMs that consume them
-        (LB_GEMM_LN_A: no LayerNorm launch, no normalised copy of the hidden state).
-        ``"auto"`` (default): per launch program - folded (``True`` form) when the program is LAUNCH-bound, i.e. at most 1024
-        tokens at the deepest level (the B = 2 anchor program at 512^2: 916 -> 706 launches, 12.40 -> 11.94 ms per forward),
-        stand-alone LayerNorms otherwise (B = 17: the fold costs 38.1 -> 42.0 ms; profiles/r03_ln_inloop_ab.txt).  Both
-        weight forms stay resident (+2.4 GB of 288 GB).
-        ``True``: row statistics accumulated inside the consumer's K loop.  Not for MFMA-bound programs: on MI355X the 64 v_dot2 per
-        K-tile and wave cost the MFMA loop more than the 6 us LayerNorm launch they replace
-        (profiles/r02_ln_gemm_bench.txt: QKV 57.1 + 6.4 us separate vs 70.0 us fused at B=17; GEGLU 132 + 6 vs 166).
-        (A third form - row statistics written by the PRODUCING GEMM's epilogue - was measured slower than the stand-alone
-        LayerNorm at B = 2 and B = 17 alike and removed in round 3: profiles/r02_ln_stats_ab.txt.)"""
+class EncoderPacking(Reloadable):
+    """Weight packing of the UNet's encoder half - conv_in, the two embedding MLPs, the down blocks and the mid block - and of the two
+    fused projections (``temb_proj``, ``ctx_kv``) over whatever resnets and cross-attention blocks a model packed: shared by
+    ``NativeUNet`` and ``controlnet.NativeControlNet``, whose encoder is the UNet's over again.  A subclass sets ``cfg``, ``device``,
+    ``w``, ``fuse_layernorm`` / ``keep_ln_weights`` and the two slice tables before it packs."""
+
+    def _init_packing(self, cfg, device, fuse_layernorm):
         assert cfg.head_dim == 64, "attention kernel is specialised for head_dim 64"
         assert fuse_layernorm in (False, True, "auto")
         self.cfg, self.device = cfg, torch.device(device)
@@ -79,7 +73,6 @@ class NativeUNet(Reloadable):
         self.w: Dict[str, torch.Tensor] = {}
         self.temb_slices: Dict[str, Tuple[int, int]] = {}      # resnet -> (offset, cout) in the fused projection
         self.ctx_slices: Dict[str, Tuple[int, int]] = {}       # transformer block -> (offset, C) in fused ctx K / V
-        self._load(provider)
 
     # ------------------------------------------------------------------ weights -----------
     def _ln_linear(self, pk, norm_name, key, w: torch.Tensor, bias: Optional[torch.Tensor], c: int):
@@ -153,24 +146,12 @@ class NativeUNet(Reloadable):
                 skips.append(c)
         return skips
 
-    def up_plan(self):
-        skips = self.skip_channels()
-        plan, hidden = [], self.cfg.block_channels[-1]
-        for c in reversed(self.cfg.block_channels):
-            cins = []
-            for _ in range(self.cfg.layers_per_block + 1):
-                cins.append((hidden, skips.pop()))
-                hidden = c
-            plan.append((c, cins))
-        return plan
-
-    def _load(self, pv):
-        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
+    def _load_encoder(self, pk, temb_acc, ctx_acc):
+        """conv_in, the embedding MLPs, the down blocks and the mid block, in the order the state dict lists them."""
+        cfg = self.cfg
         ch, T = cfg.block_channels, cfg.time_embed_dim
-        temb_acc = {"w": [], "b": [], "n": 0}
-        ctx_acc = {"k": [], "v": [], "n": 0}
         pk.conv("conv_in", cfg.in_channels, ch[0], 3)
-        if cfg.time_cond_proj_dim is not None:
+        if getattr(cfg, "time_cond_proj_dim", None) is not None:
             # guidance-distilled UNets (LCM-SDXL and its kin): the guidance-scale embedding is projected onto the timestep
             # sinusoid in front of linear_1 (diffusers TimestepEmbedding.cond_proj: Linear(time_cond_proj_dim, C0, bias=False))
             if cfg.time_cond_proj_dim <= 0 or cfg.time_cond_proj_dim % 8:
@@ -193,6 +174,52 @@ class NativeUNet(Reloadable):
         self._resnet(pk, "mid_block.resnets.0", c, c, temb_acc)
         self._transformer(pk, "mid_block.attentions.0", c, cfg.transformer_depth[-1], ctx_acc)
         self._resnet(pk, "mid_block.resnets.1", c, c, temb_acc)
+
+    def _load_fused(self, pk, temb_acc, ctx_acc):
+        """The two fused projections over everything packed so far."""
+        self.w["temb_proj.weight"] = pk.dev(torch.cat(temb_acc["w"], 0), F16)
+        self.w["temb_proj.bias"] = pk.dev(torch.cat(temb_acc["b"], 0), F32)
+        # every cross-attention K projection, then every V projection, of the text context: ONE [2 n_ctx, X] weight
+        self.w["ctx_kv.weight"] = pk.dev(torch.cat(ctx_acc["k"] + ctx_acc["v"], 0), F16)
+        self.n_temb, self.n_ctx = temb_acc["n"], ctx_acc["n"]
+
+    def weight_bytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.w.values() if t is not None)
+
+
+class NativeUNet(EncoderPacking):
+    def __init__(self, cfg: UNetConfig, provider, device="cuda", fuse_layernorm="auto"):
+        """``fuse_layernorm``: fold the three LayerNorms of every transformer block into the GEMMs that consume them
+        (LB_GEMM_LN_A: no LayerNorm launch, no normalised copy of the hidden state).
+        ``"auto"`` (default): per launch program - folded (``True`` form) when the program is LAUNCH-bound, i.e. at most 1024
+        tokens at the deepest level (the B = 2 anchor program at 512^2: 916 -> 706 launches, 12.40 -> 11.94 ms per forward),
+        stand-alone LayerNorms otherwise (B = 17: the fold costs 38.1 -> 42.0 ms; profiles/r03_ln_inloop_ab.txt).  Both
+        weight forms stay resident (+2.4 GB of 288 GB).
+        ``True``: row statistics accumulated inside the consumer's K loop.  Not for MFMA-bound programs: on MI355X the 64 v_dot2 per
+        K-tile and wave cost the MFMA loop more than the 6 us LayerNorm launch they replace
+        (profiles/r02_ln_gemm_bench.txt: QKV 57.1 + 6.4 us separate vs 70.0 us fused at B=17; GEGLU 132 + 6 vs 166).
+        (A third form - row statistics written by the PRODUCING GEMM's epilogue - was measured slower than the stand-alone
+        LayerNorm at B = 2 and B = 17 alike and removed in round 3: profiles/r02_ln_stats_ab.txt.)"""
+        self._init_packing(cfg, device, fuse_layernorm)
+        self._load(provider)
+
+    def up_plan(self):
+        skips = self.skip_channels()
+        plan, hidden = [], self.cfg.block_channels[-1]
+        for c in reversed(self.cfg.block_channels):
+            cins = []
+            for _ in range(self.cfg.layers_per_block + 1):
+                cins.append((hidden, skips.pop()))
+                hidden = c
+            plan.append((c, cins))
+        return plan
+
+    def _load(self, pv):
+        cfg, pk = self.cfg, Packer(pv, self.w, self.device)
+        ch = cfg.block_channels
+        temb_acc = {"w": [], "b": [], "n": 0}
+        ctx_acc = {"k": [], "v": [], "n": 0}
+        self._load_encoder(pk, temb_acc, ctx_acc)
         depths = list(reversed(cfg.transformer_depth))
         for ui, (c, cins) in enumerate(self.up_plan()):
             for li, (hid, skip) in enumerate(cins):
@@ -203,22 +230,25 @@ class NativeUNet(Reloadable):
                 pk.upconv(f"up_blocks.{ui}.upsamplers.0.conv", c)
         pk.norm("conv_norm_out", ch[0])
         pk.conv("conv_out", ch[0], cfg.out_channels, 3, gain=0.5)
-        # fused projections
-        self.w["temb_proj.weight"] = pk.dev(torch.cat(temb_acc["w"], 0), F16)
-        self.w["temb_proj.bias"] = pk.dev(torch.cat(temb_acc["b"], 0), F32)
-        # every cross-attention K projection, then every V projection, of the text context: ONE [2 n_ctx, X] weight
-        self.w["ctx_kv.weight"] = pk.dev(torch.cat(ctx_acc["k"] + ctx_acc["v"], 0), F16)
-        self.n_temb, self.n_ctx = temb_acc["n"], ctx_acc["n"]
-
-    def weight_bytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in self.w.values())
+        self._load_fused(pk, temb_acc, ctx_acc)
 
     # ------------------------------------------------------------------ program -----------
-    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0) -> "UNetProgram":
+    def build(self, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0, control=None) -> "UNetProgram":
         """``L``: latent side, or a pair ``(H, W)`` in latent pixels (an int means ``(L, L)``).  ``journal``: the program's arena
         keeps its alloc / release journal (``Arena``); the recorded ops are the same.  ``wrap``: wrap-around padding of conv_in, every
-        resnet conv, downsampler, upsampler and conv_out (bit 0: the columns wrap, bit 1: the rows; ``RecordedProgram``)."""
-        return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap)
+        resnet conv, downsampler, upsampler and conv_out (bit 0: the columns wrap, bit 1: the rows; ``RecordedProgram``).
+        ``control``: a ``NativeControlNet`` whose residuals the step program adds (``UNetProgram``); None: the plain program."""
+        return UNetProgram(self, B, L, ragged_halo=ragged_halo, journal=journal, wrap=wrap, control=control)
+
+
+class _Side:
+    """One network of a UNet program as the shared emitters read it: the packed model (weights, the layouts of its two fused
+    projections), the outputs of its conditioning units (``aug``, ``ctx_kv``), its ``temb_all`` once emitted, and the prefix its
+    marks carry ("" for the UNet, "control." for a ControlNet)."""
+
+    def __init__(self, net, prefix: str, aug: torch.Tensor, ctx_kv: Optional[torch.Tensor], timestep_cond=None):
+        self.net, self.prefix, self.aug, self.ctx_kv, self.timestep_cond = net, prefix, aug, ctx_kv, timestep_cond
+        self.temb_all: Optional[torch.Tensor] = None
 
 
 class UNetProgram(RecordedProgram):
@@ -227,9 +257,15 @@ class UNetProgram(RecordedProgram):
     ``marks``: one ``Mark`` per emission unit (``aug`` and ``ctx_kv`` of the conditioning program; ``temb_all``, ``conv_in``, every
     resnet / transformer / downsampler / upsampler by its weight prefix, and ``eps``); ``tap_names`` maps the block taps of the
     oracle (``conv_in``, ``down0`` .., ``mid``, ``up0`` ..) to the unit whose output they are.  ``capture()`` fills ``taps`` from the
-    inputs ``set_conditioning`` / ``forward`` left in the buffers (fp16, NHWC for feature maps) and leaves ``eps`` as a ``forward`` would."""
+    inputs ``set_conditioning`` / ``forward`` left in the buffers (fp16, NHWC for feature maps) and leaves ``eps`` as a ``forward`` would.
 
-    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0):
+    ``control``: a ``controlnet.NativeControlNet`` - the step program then holds BOTH networks.  The ControlNet's encoder and mid block
+    run first on ``x_in`` (its conv_in adds ``hint_emb``, the embedded control image: ``set_hint``) and keep their hidden maps; after
+    the UNet's own mid block one GEMM per skip computes the zero conv and adds it to the UNet's skip copy in place (``control.zero.k``;
+    ``control.zero.mid`` into the mid block's output), then the up path runs.  Its units are marked ``control.<name>``; the
+    conditioning program also computes ``control.aug`` and ``control.ctx_kv``.  ``None``: the program of ever, op for op."""
+
+    def __init__(self, net: NativeUNet, B: int, L, ragged_halo: bool = True, journal: bool = False, wrap: int = 0, control=None):
         cfg = net.cfg
         H, W = latent_hw(L)
         check_unet_latent_size(H, W, len(cfg.block_channels))
@@ -250,17 +286,34 @@ class UNetProgram(RecordedProgram):
         # ---- conditioning-program outputs (persistent) ----
         self.aug = torch.zeros(B, T, dtype=F16, device=dev)
         self.ctx_kv = torch.zeros(B * CTX_PAD, 2 * net.n_ctx, dtype=F16, device=dev)   # [K of all blocks | V of all blocks]
+        self.side = self._unet_side = _Side(net, "", self.aug, self.ctx_kv, self.timestep_cond)
+        self.control, self._control_side, self.hint_emb = control, None, None
+        if control is not None:
+            control.check_fits(net)
+            self.hint_emb = torch.zeros(B, H, W, cfg.block_channels[0], dtype=F16, device=dev)     # the embedded hint, one copy per sample
+            self._control_side = _Side(control, "control.", torch.zeros(B, T, dtype=F16, device=dev),
+                                       torch.zeros(B * CTX_PAD, 2 * control.n_ctx, dtype=F16, device=dev) if control.n_ctx else None)
         self.prog_cond = Program("unet-cond")
         self.prog_step = Program("unet-step")
         with self._recording(self.prog_cond):
-            self._emit_cond()
+            self._emit_cond(self._unet_side)
+            if control is not None:
+                self._emit_cond(self._control_side)
         with self._recording(self.prog_step):
             self._emit_step()
+
+    def set_hint(self, emb: torch.Tensor) -> None:
+        """``emb`` [1, H, W, C0] fp16 (``controlnet.HintProgram.embed``): the same embedded hint for every sample of the batch."""
+        if self.hint_emb is None:
+            raise ValueError("UNetProgram.set_hint: this program was built without a ControlNet")
+        if tuple(emb.shape[-3:]) != tuple(self.hint_emb.shape[1:]):
+            raise ValueError(f"UNetProgram.set_hint: the embedded hint is {tuple(emb.shape)} but the program takes {tuple(self.hint_emb.shape[1:])}")
+        self.hint_emb.copy_(emb.reshape(1, *self.hint_emb.shape[1:]).expand_as(self.hint_emb))
 
     # ---- helpers ------------------------------------------------------------------------
     def _conv(self, x, name, B, H, W, cin, cout, *, stride=1, ups=0, rowvec=None, ld_rowvec=None,
               residual=None, out=None, flags=0, k=3, pad=1):
-        em, w = self.em, self.net.w
+        em, w = self.em, self.side.net.w
         cin_p, cout_p = pad_to(cin, 8), pad_to(cout, 4)
         g = lib.ConvGeom(H, W, cin_p, k, k, stride=stride, pad=pad, ups=ups)
         ho, wo = g.Hout, g.Wout
@@ -272,19 +325,20 @@ class UNetProgram(RecordedProgram):
 
     def _upconv(self, x, name, B, H, W, c):
         """nearest-2x upsample + 3x3 conv as sub-pixel 2x2 convs scattered into the 2H x 2W output (``Emitter.upconv``)."""
-        w = self.net.w
+        w = self.side.net.w
         out = self.arena.alloc((B, 2 * H, 2 * W, c))
         self.em.upconv(x, w, name + ".weight", out, B=B, H=H, W=W, c=c, bias=w[name + ".bias"])
         return out, 2 * H, 2 * W
 
     def _resnet(self, x, p, B, H, W, cin, cout):
-        em, w, ar, g = self.em, self.net.w, self.arena, self.net.cfg.norm_groups
+        s = self.side
+        em, w, ar, g = self.em, s.net.w, self.arena, s.net.cfg.norm_groups
         n1 = ar.alloc((B, H, W, cin))
         em.groupnorm(x, n1, w[p + ".norm1.weight"], w[p + ".norm1.bias"], B=B, HW=H * W, C_=cin, eps=1e-5,
                      silu=True, groups=g)
-        off, _ = self.net.temb_slices[p]
-        rv = self.temb_all[:, off:]                     # column slice: pointer offset + ld = n_temb
-        h, _, _ = self._conv(n1, p + ".conv1", B, H, W, cin, cout, rowvec=rv, ld_rowvec=self.net.n_temb)
+        off, _ = s.net.temb_slices[p]
+        rv = s.temb_all[:, off:]                        # column slice: pointer offset + ld = n_temb
+        h, _, _ = self._conv(n1, p + ".conv1", B, H, W, cin, cout, rowvec=rv, ld_rowvec=s.net.n_temb)
         ar.release(n1)
         n2 = ar.alloc((B, H, W, cout))
         em.groupnorm(h, n2, w[p + ".norm2.weight"], w[p + ".norm2.bias"], B=B, HW=H * W, C_=cout, eps=1e-5,
@@ -302,11 +356,12 @@ class UNetProgram(RecordedProgram):
         return out
 
     def _transformer(self, x, p, B, H, W, c, depth):
-        em, w, ar = self.em, self.net.w, self.arena
+        s = self.side
+        em, w, ar = self.em, s.net.w, self.arena
         M, S, heads = B * H * W, H * W, c // 64
         n = ar.alloc((M, c))
         em.groupnorm(x, n, w[p + ".norm.weight"], w[p + ".norm.bias"], B=B, HW=S, C_=c, eps=1e-6, silu=False,
-                     groups=self.net.cfg.norm_groups)
+                     groups=s.net.cfg.norm_groups)
         h = ar.alloc((M, c))
         mode = self.ln_mode
         em.gemm(n, w[p + ".proj_in.weight"], h, M=M, bias=w[p + ".proj_in.bias"])
@@ -340,11 +395,11 @@ class UNetProgram(RecordedProgram):
                 em.layernorm(h, ln, w[b + ".norm2.weight"], w[b + ".norm2.bias"], M=M, C_=c)
                 em.gemm(ln, w[b + ".attn2.to_q.weight"], q, M=M)
                 ar.release(ln)
-            off, _ = self.net.ctx_slices[b]
+            off, _ = s.net.ctx_slices[b]
             a = ar.alloc((M, c))
-            em.attention(q.data_ptr(), self.ctx_kv.data_ptr() + off * 2,
-                         self.ctx_kv.data_ptr() + (self.net.n_ctx + off) * 2, a, B=B, H=heads, Sq=S, Skv=CTX_PAD,
-                         valid=CTX_TOKENS, ldq=c, ldk=2 * self.net.n_ctx, ldv=2 * self.net.n_ctx, ldo=c)
+            em.attention(q.data_ptr(), s.ctx_kv.data_ptr() + off * 2,
+                         s.ctx_kv.data_ptr() + (s.net.n_ctx + off) * 2, a, B=B, H=heads, Sq=S, Skv=CTX_PAD,
+                         valid=CTX_TOKENS, ldq=c, ldk=2 * s.net.n_ctx, ldv=2 * s.net.n_ctx, ldo=c)
             ar.release(q)
             em.gemm(a, w[b + ".attn2.to_out.0.weight"], h, M=M, bias=w[b + ".attn2.to_out.0.bias"], residual=h)
             ar.release(a)
@@ -367,8 +422,9 @@ class UNetProgram(RecordedProgram):
         return out
 
     # ---- conditioning program: everything that depends on (text context, pooled, time ids) only
-    def _emit_cond(self):
-        cfg, em, w, ar, B = self.net.cfg, self.em, self.net.w, self.arena, self.B
+    def _emit_cond(self, s: _Side):
+        """``aug`` and ``ctx_kv`` of one network (the ControlNet has embedding MLPs and cross-attention blocks of its own)."""
+        cfg, em, w, ar, B = self.net.cfg, self.em, s.net.w, self.arena, self.B
         add_in = ar.alloc((B, cfg.add_in_dim))
         em.copy_cols(self.text_embeds, add_in, rows=B, cols=cfg.pooled_dim, ld_src=cfg.pooled_dim,
                      ld_dst=cfg.add_in_dim, dst_off=0)
@@ -377,24 +433,36 @@ class UNetProgram(RecordedProgram):
         a1 = ar.alloc((B, cfg.time_embed_dim))
         em.gemm(add_in, w["add_embedding.linear_1.weight"], a1, M=B, bias=w["add_embedding.linear_1.bias"],
                 flags=lib.GEMM_SILU)
-        em.gemm(a1, w["add_embedding.linear_2.weight"], self.aug, M=B, bias=w["add_embedding.linear_2.bias"])
+        em.gemm(a1, w["add_embedding.linear_2.weight"], s.aug, M=B, bias=w["add_embedding.linear_2.bias"])
         ar.release(add_in)
         ar.release(a1)
-        self._mark("aug", "aug", self.aug, "text_embeds", "time_ids")
+        self._mark(s.prefix + "aug", "aug", s.aug, "text_embeds", "time_ids")
+        if s.ctx_kv is None:        # (a ControlNet without any cross-attention block)
+            return
         ctx2d = self.ctx.view(B * CTX_PAD, cfg.cross_dim)
-        em.gemm(ctx2d, w["ctx_kv.weight"], self.ctx_kv, M=B * CTX_PAD)
-        self._mark("ctx_kv", "ctx_kv", self.ctx_kv, "ctx")
+        em.gemm(ctx2d, w["ctx_kv.weight"], s.ctx_kv, M=B * CTX_PAD)
+        self._mark(s.prefix + "ctx_kv", "ctx_kv", s.ctx_kv, "ctx")
 
     # ---- step program: depends on the latent and the timestep
-    def _emit_step(self):
-        net, cfg, em, w, ar, B = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B
+    def _emit_encoder(self, s: _Side, residual: Optional[torch.Tensor] = None):
+        """The encoder half of network ``s`` on ``x_in`` - time embedding, conv_in (+ ``residual``), the down blocks, the mid block -
+        shared by the UNet and a ControlNet.  Returns (skips = [(map, channels, unit)] in ``skip_channels()`` order, all still
+        allocated; the mid block's output; its unit; the deepest level's height and width)."""
+        self.side = s
+        try:
+            return self._emit_encoder_of(s, residual)
+        finally:
+            self.side = self._unet_side
+
+    def _emit_encoder_of(self, s: _Side, residual):
+        net, cfg, em, w, ar, B, px = s.net, s.net.cfg, self.em, s.net.w, self.arena, self.B, s.prefix
         ch, T = cfg.block_channels, cfg.time_embed_dim
         # time embedding: silu(temb + aug) feeds every resnet's projection -> one fused GEMM
         tsin = ar.alloc((B, ch[0]))
         api.lb_sinusoid_f16(self.tvals.data_ptr(), B, 1, 1, ch[0], tsin.data_ptr(), ch[0], 0, _stream())
-        if self.timestep_cond is not None:      # tsum = timestep_cond . Wc^T + tsin (diffusers: sample + cond_proj(condition))
+        if s.timestep_cond is not None:      # tsum = timestep_cond . Wc^T + tsin (diffusers: sample + cond_proj(condition))
             tsum = ar.alloc((B, ch[0]))
-            em.gemm(self.timestep_cond, w["time_embedding.cond_proj.weight"], tsum, M=B, residual=tsin)
+            em.gemm(s.timestep_cond, w["time_embedding.cond_proj.weight"], tsum, M=B, residual=tsin)
             ar.release(tsin)
             tsin = tsum
         t1 = ar.alloc((B, T))
@@ -402,57 +470,93 @@ class UNetProgram(RecordedProgram):
                 flags=lib.GEMM_SILU)
         emb = ar.alloc((B, T))
         em.gemm(t1, w["time_embedding.linear_2.weight"], emb, M=B, bias=w["time_embedding.linear_2.bias"],
-                residual=self.aug, flags=lib.GEMM_SILU)
-        self.temb_all = ar.alloc((B, net.n_temb))
-        em.gemm(emb, w["temb_proj.weight"], self.temb_all, M=B, bias=w["temb_proj.bias"])
+                residual=s.aug, flags=lib.GEMM_SILU)
+        s.temb_all = ar.alloc((B, net.n_temb))
+        em.gemm(emb, w["temb_proj.weight"], s.temb_all, M=B, bias=w["temb_proj.bias"])
         ar.release(tsin)
         ar.release(t1)
         ar.release(emb)
-        self.persistent.append(self.temb_all)
-        self._mark("temb_all", "temb_all", self.temb_all, "tvals", "aug", *(("timestep_cond",) if self.timestep_cond is not None else ()))
+        self.persistent.append(s.temb_all)
+        temb = self._mark(px + "temb_all", "temb_all", s.temb_all, "tvals", px + "aug", *(("timestep_cond",) if s.timestep_cond is not None else ()))
+        ctx_kv = px + "ctx_kv"
         # input: NCHW latent -> NHWC (channels padded to 8)
         cin_p = pad_to(cfg.in_channels, 8)
         x8 = ar.alloc((B, self.H, self.W, cin_p))
         api.lb_nchw_to_nhwc_f16(self.x_in.data_ptr(), x8.data_ptr(), B, cfg.in_channels, self.H * self.W, cin_p, 1.0, _stream())
-        h, _, _ = self._conv(x8, "conv_in", B, self.H, self.W, cfg.in_channels, ch[0])
+        h, _, _ = self._conv(x8, "conv_in", B, self.H, self.W, cfg.in_channels, ch[0], residual=residual)
         ar.release(x8)
-        at = self.tap_names["conv_in"] = self._mark("conv_in", "conv_in", h, "x_in")     # ``at``: the unit whose output h is
+        at = self._mark(px + "conv_in", "conv_in", h, "x_in", *(("hint_emb",) if residual is not None else ()))     # ``at``: the unit whose output h is
+        if not px:
+            self.tap_names["conv_in"] = at
         skips = [(h, ch[0], at)]
         sh, sw, prev = self.H, self.W, ch[0]                    # the current level's map is sh x sw
         for bi, c in enumerate(ch):
             for li in range(cfg.layers_per_block):
                 p = f"down_blocks.{bi}.resnets.{li}"
                 nxt = self._resnet(h, p, B, sh, sw, prev, c)
-                if not any(h is s for s, _, _ in skips):
+                if not any(h is k for k, _, _ in skips):
                     ar.release(h)
                 h = nxt
-                at = self._mark(p, "resnet", h, at, "temb_all")
+                at = self._mark(px + p, "resnet", h, at, temb)
                 if cfg.transformer_depth[bi]:
                     p = f"down_blocks.{bi}.attentions.{li}"
                     nxt = self._transformer(h, p, B, sh, sw, c, cfg.transformer_depth[bi])
                     ar.release(h)
                     h = nxt
-                    at = self._mark(p, "transformer", h, at, "ctx_kv")
+                    at = self._mark(px + p, "transformer", h, at, ctx_kv)
                 skips.append((h, c, at))
                 prev = c
             if bi < len(ch) - 1:
                 p = f"down_blocks.{bi}.downsamplers.0.conv"
                 h, sh, sw = self._conv(h, p, B, sh, sw, c, c, stride=2)
-                at = self._mark(p, "downsample", h, at)
+                at = self._mark(px + p, "downsample", h, at)
                 skips.append((h, c, at))
-            self.tap_names[f"down{bi}"] = at
+            if not px:
+                self.tap_names[f"down{bi}"] = at
         c = ch[-1]
         nxt = self._resnet(h, "mid_block.resnets.0", B, sh, sw, c, c)     # h is a skip: not released
         h = nxt
-        at = self._mark("mid_block.resnets.0", "resnet", h, at, "temb_all")
+        at = self._mark(px + "mid_block.resnets.0", "resnet", h, at, temb)
         nxt = self._transformer(h, "mid_block.attentions.0", B, sh, sw, c, cfg.transformer_depth[-1])
         ar.release(h)
         h = nxt
-        at = self._mark("mid_block.attentions.0", "transformer", h, at, "ctx_kv")
+        at = self._mark(px + "mid_block.attentions.0", "transformer", h, at, ctx_kv)
         nxt = self._resnet(h, "mid_block.resnets.1", B, sh, sw, c, c)
         ar.release(h)
         h = nxt
-        at = self.tap_names["mid"] = self._mark("mid_block.resnets.1", "resnet", h, at, "temb_all")
+        at = self._mark(px + "mid_block.resnets.1", "resnet", h, at, temb)
+        if not px:
+            self.tap_names["mid"] = at
+        return skips, h, at, sh, sw
+
+    def _emit_control_adds(self, c_skips, c_mid, c_mid_at, skips, h, at):
+        """One GEMM per residual: zero conv (1x1, weights and bias pre-scaled by the conditioning scale) of the ControlNet's hidden map,
+        added in the epilogue to the UNet's skip copy IN PLACE - every down-path reader of that copy has been emitted; the mid
+        residual goes into the mid block's output.  Returns (the skips under their new units, the mid unit)."""
+        em, cw, ar, B = self.em, self.control.w, self.arena, self.B
+        out = []
+        for k, ((ck, cc, c_at), (sk, sc, s_at)) in enumerate(zip(c_skips, skips)):
+            assert cc == sc and ck.shape == sk.shape
+            M = sk.numel() // sc
+            em.gemm(ck, cw[f"controlnet_down_blocks.{k}.weight"], sk, M=M, bias=cw[f"controlnet_down_blocks.{k}.bias"], residual=sk)
+            ar.release(ck)
+            out.append((sk, sc, self._mark(f"control.zero.{k}", "zero", sk, c_at, s_at)))
+        c = self.net.cfg.block_channels[-1]
+        em.gemm(c_mid, cw["controlnet_mid_block.weight"], h, M=h.numel() // c, bias=cw["controlnet_mid_block.bias"], residual=h)
+        ar.release(c_mid)
+        return out, self._mark("control.zero.mid", "zero", h, c_mid_at, at)
+
+    def _emit_step(self):
+        net, cfg, em, w, ar, B = self.net, self.net.cfg, self.em, self.net.w, self.arena, self.B
+        ch = cfg.block_channels
+        if self.control is not None:       # the ControlNet first: its ten hidden maps wait for the UNet's skips
+            c_skips, c_mid, c_mid_at, _, _ = self._emit_encoder(self._control_side, residual=self.hint_emb)
+        skips, h, at, sh, sw = self._emit_encoder(self._unet_side)
+        self.temb_all = self._unet_side.temb_all
+        self.skip_maps = [k for k, _, _ in skips]      # (valid between the mid block and the up path: ``run_with_residuals``)
+        self.mid_map, self.op_mid_end = h, self.prog_step.num_ops
+        if self.control is not None:
+            skips, at = self._emit_control_adds(c_skips, c_mid, c_mid_at, skips, h, at)
         depths = list(reversed(cfg.transformer_depth))
         for ui, (c, cins) in enumerate(net.up_plan()):
             for li, (hid, sc) in enumerate(cins):
@@ -520,4 +624,23 @@ class UNetProgram(RecordedProgram):
         self.x_in.copy_(x_in)
         self.tvals.copy_(tvals.reshape(-1, 1).to(F32))
         self.prog_step.launch()
+        return self.eps
+
+    def forward_with_residuals(self, x_in: torch.Tensor, tvals: torch.Tensor, down: Sequence[torch.Tensor], mid: Optional[torch.Tensor]) -> torch.Tensor:
+        """``forward`` with residuals GIVEN as tensors (diffusers' ``down_block_additional_residuals`` / ``mid_block_additional_residual``,
+        NHWC fp16 here): the step program runs up to the end of the mid block, the residuals are added to the skip copies and to the
+        mid block's output, the up path runs.  The compatibility path of the ``pipe.unet`` facade - eager between two halves of the
+        program, one more fp16 rounding than the fused form; the native loops use a program built with ``control=``."""
+        if self.control is not None:
+            raise ValueError("UNetProgram.forward_with_residuals: this program adds its own ControlNet's residuals already")
+        if len(down) != len(self.skip_maps):
+            raise ValueError(f"UNetProgram.forward_with_residuals: {len(down)} residuals for {len(self.skip_maps)} skips")
+        self.x_in.copy_(x_in)
+        self.tvals.copy_(tvals.reshape(-1, 1).to(F32))
+        self.prog_step.run_range(0, self.op_mid_end)
+        for skip, res in zip(self.skip_maps, down):
+            skip.add_(res.to(F16).reshape(skip.shape))
+        if mid is not None:
+            self.mid_map.add_(mid.to(F16).reshape(self.mid_map.shape))
+        self.prog_step.run_range(self.op_mid_end, self.prog_step.num_ops)
         return self.eps

@@ -275,6 +275,15 @@ class Reloadable:
             if (t is None) != (have is None) or (t is not None and (t.shape != have.shape or t.dtype != have.dtype)):
                 raise ValueError(f"{type(self).__name__}.reload: '{k}' is {None if t is None else (tuple(t.shape), t.dtype)} but the "
                                  f"live tensor is {None if have is None else (tuple(have.shape), have.dtype)}")
+        self._write_live(fresh)
+        fresh.clear()
+        t = have = None
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()
+
+    def _write_live(self, fresh) -> None:
+        """``copy_`` every tensor of ``fresh`` (name -> tensor or None) into the live tensor of that name, between two synchronisations."""
+        live = self.w
         cuda = self.device.type == "cuda"
         if cuda:
             torch.cuda.synchronize(self.device)         # launches that read the old weights may still be in flight
@@ -284,10 +293,6 @@ class Reloadable:
                     live[k].copy_(t)
         if cuda:
             torch.cuda.synchronize(self.device)
-        fresh.clear()
-        t = have = None
-        if cuda:
-            torch.cuda.empty_cache()
 
 
 def from_safetensors(path: str, prefix: str = "") -> DictProvider:

@@ -103,7 +103,8 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
                          movie_size=None, movie_resample: Optional[str] = None, decoder: Optional[str] = None,
                          list_images: Optional[Sequence] = None, list_image_strengths: Optional[Sequence] = None,
                          noise: Optional[str] = None, loras: Optional[Sequence] = None,
-                         image_encoder: Optional[str] = None, tileable=None) -> List[List]:
+                         image_encoder: Optional[str] = None, tileable=None, control_image=None,
+                         control_scale: Optional[float] = None) -> List[List]:
     """Chain ``len(list_prompts) - 1`` transitions, recycling the shared key frame of neighbouring segments.
 
     Engine calls are those of example_multi_trans.py:39-62; with ``list_negative_prompts`` the negative prompt
@@ -137,12 +138,15 @@ def run_multi_transition(be, list_prompts: Sequence[str], list_seeds: Sequence[i
     (None: as the pipe stands); the previous value is restored afterwards.
     ``tileable``: "x" / "y" / "xy" / True / False = the native pipe's ``tileable`` for this chain - seamless frames along those axes
     (None: as the pipe stands); the previous value is restored afterwards.  ``ValueError`` on a pipe without the setting.
+    ``control_image`` / ``control_scale``: a ControlNet hint held through the whole chain (``BlendingEngine.set_control_image``; scale
+    ``None`` = 1.0); the engine's previous hint and scale are put back afterwards.  None: the engine's hint as it stands.
     """
     images = _image_keyframes(list_images, list_image_strengths, len(list_prompts))
     if images is not None and pipeline_keyframes:
         raise ValueError("run_multi_transition: pipeline_keyframes=True precomputes every key frame from its prompt; "
                          "it cannot be combined with image key frames (list_images)")
-    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras), _encoder_as(be, image_encoder), _tileable_as(be, tileable):
+    with _decoder_as(be, decoder), _noise_as(be, noise), _loras_as(be, loras), _encoder_as(be, image_encoder), _tileable_as(be, tileable), \
+            _control_as(be, control_image, control_scale):
         try:
             return _run_multi_transition(be, list_prompts, list_seeds, fp_movie, duration_single_trans, list_negative_prompts, fps, dp_parts,
                                          keep_parts, on_segment, pipeline_keyframes, movie_encoder, movie_size, movie_resample, images)
@@ -212,6 +216,22 @@ def _tileable_as(be, tileable):
         yield
     finally:
         pipe.tileable = previous
+
+
+@contextlib.contextmanager
+def _control_as(be, image, scale: Optional[float]):
+    """Run the body with ``image`` as the engine's ControlNet hint (None: untouched), then put the previous hint and scale back."""
+    if image is None:
+        if scale is not None:
+            raise ValueError("control_scale=... needs a control_image")
+        yield
+        return
+    previous = (be.control_image, be.control_scale)
+    be.set_control_image(image, 1.0 if scale is None else float(scale))
+    try:
+        yield
+    finally:
+        be.control_image, be.control_scale = previous
 
 
 @contextlib.contextmanager
@@ -328,7 +348,8 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                    fps: int = 30, dp_parts: str = ".", keep_parts: bool = True, pipeline_keyframes: bool = False,
                    movie_encoder: Optional[str] = None, movie_size=None, movie_resample: Optional[str] = None,
                    decoder: Optional[str] = None, noise: Optional[str] = None, loras: Optional[Sequence] = None,
-                   image_encoder: Optional[str] = None, tileable=None) -> List[List]:
+                   image_encoder: Optional[str] = None, tileable=None, control_image=None,
+                   control_scale: Optional[float] = None) -> List[List]:
     """``example_multi_trans_json.py`` as a call: size and step count from the header, then the chain (``decoder``, ``noise`` as there).
     Items with an ``"image"`` key (path relative to the JSON file; ``"image_strength"``, default 0.5) are image key frames.
     The header's ``"loras": [{"path": ..., "scale": ...}]`` (paths relative to the JSON file) are the chain's LoRA adapters; ``loras=``
@@ -336,6 +357,13 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
     is restored afterwards); ``image_encoder=`` given here replaces it; neither: the pipe as it stands.  The header's ``"tileable"``
     ("x" / "y" / "xy") renders the movie seamless along those axes, likewise; ``tileable=`` given here replaces it."""
     header, items = load_movie_json(fp_json)
+    # the header's "control_image" (a path relative to the JSON file) and "control_scale": the movie's ControlNet hint;
+    # control_image= / control_scale= given here replace them
+    if control_image is None and header.get("control_image") is not None:
+        from PIL import Image
+        control_image = Image.open(os.path.join(os.path.dirname(os.path.abspath(fp_json)), header["control_image"])).convert("RGB")
+    if control_scale is None and control_image is not None and header.get("control_scale") is not None:
+        control_scale = float(header["control_scale"])
     if tileable is None:
         tileable = header.get("tileable")
     if image_encoder is None:
@@ -355,4 +383,5 @@ def run_movie_json(be, fp_json: str, fp_movie: Optional[str] = None, duration_si
                                 duration_single_trans, [it["negative_prompt"] for it in items], fps=fps,
                                 dp_parts=dp_parts, keep_parts=keep_parts, pipeline_keyframes=pipeline_keyframes, movie_encoder=movie_encoder,
                                 movie_size=movie_size, movie_resample=movie_resample, decoder=decoder, list_images=images,
-                                list_image_strengths=strengths, noise=noise, loras=loras, image_encoder=image_encoder, tileable=tileable)
+                                list_image_strengths=strengths, noise=noise, loras=loras, image_encoder=image_encoder, tileable=tileable,
+                                control_image=control_image, control_scale=control_scale)

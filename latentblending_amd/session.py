@@ -37,7 +37,8 @@ _ENGINE_FIELDS = ("prompt1", "prompt2", "text_embedding1", "text_embedding2", "n
                   "parental_crossfeed_power", "parental_crossfeed_range", "parental_crossfeed_decay",
                   "num_inference_steps", "list_idx_injection", "list_nmb_stems", "image1_lowres", "image2_lowres",
                   "multi_transition_img_first", "multi_transition_img_last", "_preset_anchor_frames", "stats", "movie_encoder",
-                  "movie_size", "movie_resample", "anchor_image1", "anchor_image2", "anchor_image_strength1", "anchor_image_strength2", "noise")
+                  "movie_size", "movie_resample", "anchor_image1", "anchor_image2", "anchor_image_strength1", "anchor_image_strength2", "noise",
+                  "control_image", "control_scale")
 # holder attributes that follow them
 _HOLDER_FIELDS = ("negative_prompt", "guidance_scale", "num_inference_steps", "width_img", "height_img", "width_latent",
                   "height_latent")
@@ -45,7 +46,7 @@ _HOLDER_FIELDS = ("negative_prompt", "guidance_scale", "num_inference_steps", "w
 
 # of those, what a finished or prepared RUN leaves behind (never part of a new user's defaults)
 _TRANSIENT_FIELDS = ("image1_lowres", "image2_lowres", "multi_transition_img_first", "multi_transition_img_last",
-                     "_preset_anchor_frames", "anchor_image1", "anchor_image2")
+                     "_preset_anchor_frames", "anchor_image1", "anchor_image2", "control_image")
 
 
 def _snapshot(be):
